@@ -20,9 +20,12 @@
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (fresh processes, before
 any GPU call) and relays rank 0's JSON line; under torchrun (WORLD_SIZE set) it is one rank.
 
-One JSON line on stdout (rank 0).  `roofline` is measured live with HIP events on the launch stream over the timed region;
-`verified` says the timed region's own output was checked against the CPU oracle after timing; `cpu_baseline` times the
-oracle's C restatement of nttUnrolled16Lazy + reducevec on the host cores (rank 0, N = 1)."""
+One JSON line on stdout (rank 0).  `roofline` is measured live with HIP events on the launch stream over the timed region.
+A plain run sets up, warms up, times the `--steps` steps, writes `--dump-outputs` if given and prints the line; `verified` is null.
+--full adds everything else, after the timed region: `verified` says the timed region's own output was checked against the CPU
+oracle; `cpu_baseline` times the oracle's C restatement of nttUnrolled16Lazy + reducevec on the host cores (rank 0, N = 1);
+`roofline.standalone_kernel_ms` and `roofline.power` (ntt workload) take runs of their own.
+--dump-outputs DIR: what the last timed step computed, as DIR/<name>.npy (see dump_outputs)."""
 import argparse
 import json
 import os
@@ -56,10 +59,13 @@ def parse():
     ap.add_argument("--logn", type=int, default=16)
     ap.add_argument("--limbs", type=int, default=16, help="ntt workload: limbs of the ring (Qi60[0:limbs])")
     ap.add_argument("--chunk", type=int, default=-1, help="polys per (column,tile) kernel pair; -1 = engine default")
+    ap.add_argument("--full", action="store_true", help="also verify against the oracle, time the CPU baseline, the standalone kernels and the "
+                                                       "power sample (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float32)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="target wall time of the CPU baseline sample")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-power", action="store_true", help="skip the clock / package-power sample under load (rocm-smi)")
-    ap.add_argument("--no-verify", action="store_true", help="skip the oracle check of the timed region's output")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-power", action="store_true", help="--full: skip the clock / package-power sample under load (rocm-smi)")
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the oracle check of the timed region's output")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, default) or gloo (rehearsal of the N>1 path on one GPU)")
     ap.add_argument("--single-device", action="store_true", help="rehearsal only: every rank uses cuda:0")
     ap.add_argument("--asm-cols", type=int, default=-1, help="hand-scheduled column stages (default on)")
@@ -72,7 +78,12 @@ def parse():
     ap.add_argument("--force-dist", action="store_true", help="pre-flight: with one rank, still create the process group and run every collective the N > 1 "
                                                               "path makes (all-reduce, barrier, all-gather of clocks, AND of flags, the --gather leg) -- RCCL with a world of 1")
     ap.add_argument("--rank-timeout", type=float, default=1500.0, help="--gpus N without a launcher: the parent gives up (and stops its ranks) after this many seconds")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_cpu = args.no_verify = args.no_power = True
+    return args
 
 
 def csrc_tree_hash():
@@ -342,6 +353,32 @@ def load_json(name):
         return None
 
 
+DUMP_MAX_WORDS = 1 << 21      # u64 words over all outputs of one dump: 16 bytes each as written -> 32 MiB at most
+
+
+def dump_outputs(outdir, outputs):
+    """--dump-outputs: `outputs` {name: int64 tensor of u64 residues} -> outdir/<name>.npy, float32, one more trailing axis of 4: the
+    word's 16-bit digits, most significant first.  Residues reach 2^61 and neither float type holds them; the digits are exact, and a
+    comparison with the default tolerances of numpy.allclose still tells any two words apart.  An output of more words than its share of
+    DUMP_MAX_WORDS is written as a fixed sample: the output cut into `share` equal stretches (flat order), one word from each, at an offset
+    drawn by a generator of constant seed."""
+    import numpy as np
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    share = DUMP_MAX_WORDS // len(outputs)
+    for name, t in outputs.items():
+        flat = t.reshape(-1)
+        if flat.numel() > share:
+            stride = flat.numel() // share
+            idx = np.arange(share, dtype=np.int64) * stride + np.random.default_rng(0xd0e5).integers(0, stride, size=share)
+            words = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy()
+        else:
+            words = t.cpu().numpy()
+        words = words.view(np.uint64)
+        digits = np.stack([(words >> np.uint64(s)) & np.uint64(0xffff) for s in (48, 32, 16, 0)], axis=-1).astype(np.float32)
+        np.save(os.path.join(outdir, name + ".npy"), digits)
+
+
 # ------------------------------------------------------------------------------------------------ workload: ntt
 def run_ntt(args):
     import numpy as np
@@ -373,13 +410,16 @@ def run_ntt(args):
         data[b0:b0 + blk.shape[0]] = blk % qs
     poly = rh.DevicePoly.from_torch(ring, data)
     spots = sorted({(0, 0), (min(B - 1, B // 2 + 1), min(L - 1, 7)), (B - 1, L - 1)})
-    saved = {s: data[s[0], s[1]].cpu().numpy().view(np.uint64).copy() for s in spots}      # every rank verifies its own batch
+    if not args.no_verify:
+        saved = {s: data[s[0], s[1]].cpu().numpy().view(np.uint64).copy() for s in spots}      # every rank verifies its own batch
 
     def step():
         ring.NTT(poly, poly)
 
     wall, dev_ms, per_rank = timed_region(step, args, dist, dev, stream)
     ring.sync()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"ntt_forward": data})
     # verification of the timed region's own output, on EVERY rank: the buffer has been transformed warmup + steps times in place
     verified = None
     if not args.no_verify:
@@ -430,7 +470,7 @@ def run_ntt(args):
 
     # per-kernel device time (HIP events on the same stream), outside the timed region
     kern = {}
-    if rank == 0 and args.logn > 12:
+    if rank == 0 and args.logn > 12 and args.full:
         for name, phase in (("ntt_fwd_cols", 1), ("ntt_fwd_tile", 2)):
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ring.ntt_phase(poly, poly, phase=phase)
@@ -570,6 +610,8 @@ def run_polymul(args):
     e1.record(stream); torch.cuda.synchronize()
     copy_ms = e0.elapsed_time(e1)
     ring.sync()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"polymul_c": tc})
     verified = None
     spots = sorted({(0, 0), (min(B - 1, B // 2 + 1), min(L - 1, 7)), (B - 1, L - 1)})
     if not args.no_verify:
@@ -675,6 +717,8 @@ def run_ctmul(args):
 
     wall, dev_ms, per_rank = timed_region(step, args, dist, dev, stream)
     ring.sync()
+    if args.dump_outputs and rank == 0:                         # before the verification, which runs one more step on the same buffers
+        dump_outputs(args.dump_outputs, {"ctmul_out%d" % c: tout[c] for c in range(3)})
     verified = None
     spots = sorted({(0, 0), (B - 1, L - 1)})
     if not args.no_verify:
@@ -799,6 +843,8 @@ def run_keyswitch(args):
                 be.GadgetProduct(nq - 1, npl - 1, pcx, evkQ.data_ptr(), evkP.data_ptr(), beta, p0, p1)
 
     wall, dev_ms, per_rank = timed_region(step, args, dist, dev, stream)
+    if args.dump_outputs and rank == 0:                         # this rank's polys and limbs (all of both on one GPU)
+        dump_outputs(args.dump_outputs, {"keyswitch_ct0": ct0, "keyswitch_ct1": ct1})
     exch = {"exchanges_per_product": ks.exchanges, "bytes_received_per_gpu_per_product": ks.exchange_words * 8} if limb else None
     verified = None
     if not args.no_verify:                                 # EVERY rank: first, middle and last poly of its share against the oracle composition

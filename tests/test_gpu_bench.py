@@ -1,6 +1,7 @@
 """GPU: bench.py end to end at reduced size -- the JSON contract, the self-started N > 1 ranks (`--gpus 2` with no launcher:
 two processes on this box's one GPU, gloo rendezvous on 127.0.0.1 = the rehearsal of the RCCL path), the limb-sharded
-key-switch workload, and the oracle check bench.py makes of its own timed output (`verified`)."""
+key-switch workload, the oracle check bench.py makes of its own timed output under --full (`verified`), the lean plain run and
+--dump-outputs."""
 import json
 import os
 import subprocess
@@ -22,7 +23,7 @@ def run_bench(*extra, timeout=900):
 
 
 def test_bench_one_gpu_line_and_self_check():
-    j = run_bench("--batch", "260", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1")
+    j = run_bench("--full", "--batch", "260", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
               "config", "roofline", "cpu_baseline", "verified"):
         assert k in j, k
@@ -32,15 +33,73 @@ def test_bench_one_gpu_line_and_self_check():
     assert j["cpu_baseline"]["kind"] == "port" and j["cpu_baseline"]["cores"] == 1 and j["cpu_baseline"]["value"] > 0
 
 
+def load_dump(d):
+    import numpy as np
+    return {f: np.load(os.path.join(str(d), f)) for f in sorted(os.listdir(str(d)))}
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_last_step(tmp_path):
+    # the plain line carries the headline fields and nothing that takes runs of its own; --dump-outputs writes the last timed step's output,
+    # the same on every run with the same arguments and the same as the --full run's (whose output the oracle check passes)
+    import numpy as np
+    args = ["--batch", "130", "--steps", "2", "--warmup", "1"]
+    j = run_bench(*args, "--dump-outputs", str(tmp_path / "a"))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in j, k
+    assert j["steps"] == 2 and j["warmup"] == 1 and j["unit"] == "NTT/s" and j["higher_is_better"] is True and j["dtype"] == "u64"
+    assert abs(j["value"] - 130 / (j["ms_per_step"] * 1e-3)) < 1e-6 * j["value"]
+    assert j["verified"] is None and "cpu_baseline" not in j and "power" not in j["roofline"] and j["roofline"]["standalone_kernel_ms"] == {}
+    a = load_dump(tmp_path / "a")
+    assert list(a) == ["ntt_forward.npy"]
+    x = a["ntt_forward.npy"]
+    assert x.dtype == np.float32 and x.ndim == 2 and x.shape[1] == 4 and 0 < x.nbytes <= 64 << 20
+    assert np.all((x >= 0) & (x < 65536) & (x == np.round(x)))
+    w = x.astype(np.uint64) @ np.array([1 << 48, 1 << 32, 1 << 16, 1], dtype=np.uint64)
+    assert np.all(w < np.uint64(max(bench_qi60()))) and len(np.unique(w)) > 0.99 * len(w)     # canonical residues, not a constant
+    run_bench(*args, "--dump-outputs", str(tmp_path / "b"))
+    jf = run_bench(*args, "--full", "--no-cpu", "--no-power", "--dump-outputs", str(tmp_path / "f"))
+    assert jf["verified"] is True
+    for other in ("b", "f"):
+        assert np.array_equal(load_dump(tmp_path / other)["ntt_forward.npy"], x), other
+    # --steps sets the number of in-place transforms: one more step, another output
+    run_bench("--batch", "130", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "c"))
+    assert not np.array_equal(load_dump(tmp_path / "c")["ntt_forward.npy"], x)
+
+
+def bench_qi60():
+    sys.path.insert(0, ROOT)
+    import bench
+    return bench.QI60
+
+
+@pytest.mark.parametrize("workload,extra,names", [
+    ("polymul", ["--logn", "13", "--batch", "4"], ["polymul_c.npy"]),
+    ("ctmul", ["--logn", "13", "--limbs", "2", "--batch", "2"], ["ctmul_out0.npy", "ctmul_out1.npy", "ctmul_out2.npy"]),
+    ("keyswitch", ["--logn", "13", "--batch", "2"], ["keyswitch_ct0.npy", "keyswitch_ct1.npy"])])
+def test_bench_dump_outputs_of_every_workload(tmp_path, workload, extra, names):
+    # small outputs are written whole: the poly layout plus the digit axis; the --full run (verified) leaves the same bytes
+    import numpy as np
+    args = ["--workload", workload, "--steps", "2", "--warmup", "1"] + extra
+    j = run_bench(*args, "--dump-outputs", str(tmp_path / "a"))
+    assert j["steps"] == 2 and j["verified"] is None and "cpu_baseline" not in j
+    jf = run_bench(*args, "--full", "--no-cpu", "--dump-outputs", str(tmp_path / "f"))
+    assert jf["verified"] is True
+    a, f = load_dump(tmp_path / "a"), load_dump(tmp_path / "f")
+    assert list(a) == names and list(f) == names
+    for n in names:
+        assert a[n].dtype == np.float32 and a[n].shape[-1] == 4 and a[n].shape[-2] == (3 << 13 if workload == "ctmul" else 1 << 13)
+        assert np.array_equal(a[n], f[n]), n
+
+
 def test_bench_gpus_2_starts_two_ranks():
     # the driver's N > 1 form without torchrun: the parent spawns the ranks; here both share cuda:0 and rendezvous over gloo
-    j = run_bench("--gpus", "2", "--single-device", "--dist-backend", "gloo", "--batch", "8", "--steps", "2", "--warmup", "1", "--no-cpu")
+    j = run_bench("--full", "--gpus", "2", "--single-device", "--dist-backend", "gloo", "--batch", "8", "--steps", "2", "--warmup", "1", "--no-cpu")
     assert j["n_gpus"] == 2 and j["config"]["dist_ranks"] == 2 and j["verified"] is True
     assert j["scaling"] == "weak" and "x2" in j["config"]["parallelism"]
 
 
 def test_bench_keyswitch_workload_two_ranks():
-    j = run_bench("--workload", "keyswitch", "--gpus", "2", "--single-device", "--dist-backend", "gloo", "--batch", "2", "--steps", "1", "--warmup", "1",
+    j = run_bench("--full", "--workload", "keyswitch", "--gpus", "2", "--single-device", "--dist-backend", "gloo", "--batch", "2", "--steps", "1", "--warmup", "1",
                   "--logn", "13")
     assert j["n_gpus"] == 2 and j["unit"] == "key-switch/s" and j["verified"] is True and j["scaling"] == "strong"
     assert j["config"]["dist_ranks"] == 2
@@ -48,21 +107,21 @@ def test_bench_keyswitch_workload_two_ranks():
 
 def test_bench_polymul_workload_one_gpu_and_two_ranks():
     # BASELINE config 3 through bench.py: the JSON contract with roofline + cpu_baseline at N = 1; two ranks batch-sharded, every rank verifies
-    j = run_bench("--workload", "polymul", "--batch", "40", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1")
+    j = run_bench("--full", "--workload", "polymul", "--batch", "40", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1")
     assert j["unit"] == "poly-mul/s" and j["n_gpus"] == 1 and j["verified"] is True and j["scaling"] == "weak" and "2^15" in j["metric"]
     r = j["roofline"]
     assert r["bound"] == "hbm" and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-12 and 0 < r["frac_vs_fused_lower_bound_24NL"] < r["frac"]
     assert j["cpu_baseline"]["kind"] == "port" and j["cpu_baseline"]["value"] > 0
-    j = run_bench("--workload", "polymul", "--gpus", "2", "--single-device", "--dist-backend", "gloo", "--batch", "6", "--steps", "1", "--warmup", "1", "--logn", "13", "--no-cpu")
+    j = run_bench("--full", "--workload", "polymul", "--gpus", "2", "--single-device", "--dist-backend", "gloo", "--batch", "6", "--steps", "1", "--warmup", "1", "--logn", "13", "--no-cpu")
     assert j["n_gpus"] == 2 and j["config"]["dist_ranks"] == 2 and j["verified"] is True and "2^13" in j["metric"]
 
 
 def test_bench_ctmul_workload_one_gpu_and_two_ranks():
     # BASELINE config 4 through bench.py at a reduced ring (N = 3*2^13, 3 limbs): contract fields, verification on every rank
-    j = run_bench("--workload", "ctmul", "--logn", "13", "--limbs", "3", "--batch", "3", "--steps", "2", "--warmup", "1")
+    j = run_bench("--full", "--workload", "ctmul", "--logn", "13", "--limbs", "3", "--batch", "3", "--steps", "2", "--warmup", "1")
     assert j["unit"] == "ct-mul/s" and j["n_gpus"] == 1 and j["verified"] is True and "N=24576" in j["metric"]
     assert j["roofline"]["bound"] == "hbm" and j["cpu_baseline"]["value"] > 0
-    j = run_bench("--workload", "ctmul", "--logn", "13", "--limbs", "2", "--batch", "2", "--steps", "1", "--warmup", "1", "--gpus", "2", "--single-device",
+    j = run_bench("--full", "--workload", "ctmul", "--logn", "13", "--limbs", "2", "--batch", "2", "--steps", "1", "--warmup", "1", "--gpus", "2", "--single-device",
                   "--dist-backend", "gloo", "--no-cpu")
     assert j["n_gpus"] == 2 and j["config"]["dist_ranks"] == 2 and j["verified"] is True
 
@@ -77,7 +136,7 @@ REHEARSE = int(os.environ.get("RH_BENCH_REHEARSE_RANKS", "5"))
 
 def test_bench_ntt_many_ranks_rehearsal_with_final_gather():
     n = REHEARSE
-    j = run_bench("--gpus", str(n), "--single-device", "--dist-backend", "gloo", "--batch", "4", "--steps", "2", "--warmup", "1", "--no-cpu", "--logn", "14",
+    j = run_bench("--full", "--gpus", str(n), "--single-device", "--dist-backend", "gloo", "--batch", "4", "--steps", "2", "--warmup", "1", "--no-cpu", "--logn", "14",
                   "--gather", "--gather-polys", "2")
     assert j["n_gpus"] == n and j["config"]["dist_ranks"] == n and j["verified"] is True
     pr = j["config"]["per_rank_device_ms_per_step"]
@@ -90,7 +149,7 @@ def test_bench_ntt_many_ranks_rehearsal_with_final_gather():
 @pytest.mark.parametrize("shard", ["limb", "batch"])
 def test_bench_keyswitch_many_ranks_rehearsal(shard):
     n = REHEARSE
-    j = run_bench("--workload", "keyswitch", "--shard", shard, "--gpus", str(n), "--single-device", "--dist-backend", "gloo", "--batch", "7", "--steps", "1",
+    j = run_bench("--full", "--workload", "keyswitch", "--shard", shard, "--gpus", str(n), "--single-device", "--dist-backend", "gloo", "--batch", "7", "--steps", "1",
                   "--warmup", "1", "--logn", "13")
     assert j["n_gpus"] == n and j["config"]["dist_ranks"] == n and j["verified"] is True and j["config"]["shard"] == shard
     assert len(j["config"]["per_rank_device_ms_per_step"]["device_ms_per_step"]) == n
@@ -183,7 +242,7 @@ def test_bench_drops_stale_counters(tmp_path):
 def test_bench_rccl_calls_with_a_world_of_one():
     # every collective the N > 1 run makes -- all-reduce of ones, barriers, all-gather of the per-rank clocks, AND of the verification flags, the
     # final gather as ONE all_gather_into_tensor on device memory -- through the REAL RCCL backend, with one rank on the box's one GPU
-    j = run_bench("--force-dist", "--dist-backend", "nccl", "--batch", "130", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-power", "--gather", "--gather-polys", "4")
+    j = run_bench("--full", "--force-dist", "--dist-backend", "nccl", "--batch", "130", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-power", "--gather", "--gather-polys", "4")
     assert j["n_gpus"] == 1 and j["config"]["dist_backend"] == "nccl" and j["config"]["rccl_ranks"] == 1 and j["verified"] is True
     g = j["final_gather"]
     assert g["verified"] is True and "RCCL" in g["what"] and g["bytes_received_per_gpu"] == 0

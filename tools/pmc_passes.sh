@@ -8,6 +8,6 @@ shift
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 i=0
 for g in "${groups[@]}"; do
-  rocprofv3 --kernel-trace --pmc $g -d "$out/p$i" -o p --output-format csv -- python3 bench.py --no-cpu "$@" > "$out.p$i.log" 2>&1 || { tail -5 "$out.p$i.log"; exit 1; }
+  rocprofv3 --kernel-trace --pmc $g -d "$out/p$i" -o p --output-format csv -- python3 bench.py --full --no-cpu "$@" > "$out.p$i.log" 2>&1 || { tail -5 "$out.p$i.log"; exit 1; }
   i=$((i+1))
 done
