@@ -7,6 +7,7 @@
 // (MulCoeffsMontgomeryLazy / ...LazyThenAddLazy of ringqp, ring/ringqp/operations.go:115-155).
 // Outputs are canonical (the reference ends with ring.Reduce and a full MRed in ModDown), so they are bit-identical.
 #include <hip/hip_runtime.h>
+#include <climits>
 #include <vector>
 #include "engine_internal.hpp"
 #include "bext_internal.hpp"
@@ -144,9 +145,14 @@ static int mac_all(rh_ring* r, const u64* c2, size_t digit_stride, const u64* ev
   return rh_gadget_mac_all(r, c2, digit_stride, evk, beta, overf, a0, a1, npoly, L, cx, nullptr, digit_limbs);
 }
 
-int rh_overflow_margin(const std::vector<u64>& m, int level) {     // QiOverflowMargin / PiOverflowMargin, core/rlwe/params.go
+// QiOverflowMargin / PiOverflowMargin, core/rlwe/params.go: floor(2^64 / max q_i), a 64-bit Go int.  Clamped to INT_MAX: below 2^33 the
+// quotient does not fit an int (the old (int) of the double was undefined there), and any margin >= 2^31 never reduces mid-loop at the digit
+// counts a ring allows, which is the reference's schedule.
+int rh_overflow_margin(const std::vector<u64>& m, int level) {
   u64 mx = 0; for (int i = 0; i <= level; ++i) if (m[i] > mx) mx = m[i];
-  return (int)(18446744073709551616.0 / (double)mx);
+  if (mx < 2) return INT_MAX;
+  const unsigned __int128 quo = ((unsigned __int128)1 << 64) / mx;
+  return quo > (unsigned __int128)INT_MAX ? INT_MAX : (int)quo;
 }
 
 // DecomposeSingleNTT (:455-478): digit i of cx -> c2Q (levelQ+1 limbs), c2P (levelP+1 limbs), NTT domain.

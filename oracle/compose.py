@@ -11,11 +11,13 @@ _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OPS = {m.group(1): int(m.group(2)) for m in re.finditer(r"RH_OP_([A-Z0-9_]+)\s*=\s*(\d+)", open(os.path.join(_ROOT, "include", "ringhip_ops.h")).read())}
 
 
-def gadget_product(N, Q, P, levelQ, levelP, cx, evkQ, evkP):
+def gadget_product(N, Q, P, levelQ, levelP, cx, evkQ, evkP, qiof=None, piof=None):
     """rlwe.Evaluator.GadgetProduct, NTT-domain input, levelP >= 1 (core/rlwe/evaluator_gadget_product.go:16-30):
     gadgetProductMultiplePLazy (:123-188) = INTT, per digit DecomposeSingleNTT (:455-478) + MulCoeffsMontgomeryLazy
     (ThenAddLazy) with the periodic Reduce, then ModDown NTT -> NTT (:33-46, ring/basis_extension.go:241-258).
-    cx: (levelQ+1, N); evkQ / evkP: (digits, 2, len(Q) / len(P), N).  Returns (ct0, ct1), each (levelQ+1, N)."""
+    cx: (levelQ+1, N); evkQ / evkP: (digits, 2, len(Q) / len(P), N).  Returns (ct0, ct1), each (levelQ+1, N).
+    qiof / piof: Reduce periods other than the reference's QiOverflowMargin>>1 / PiOverflowMargin>>1 (tests that show a wrong
+    schedule changes the result)."""
     LQ, LP = levelQ + 1, levelP + 1
     Ql, Pl = Q[:LQ], P[:LP]
     srQ = [orc.SubRingConsts(N, q) for q in Ql]
@@ -23,8 +25,8 @@ def gadget_product(N, Q, P, levelQ, levelP, cx, evkQ, evkP):
     beta = (levelQ + levelP + 1) // (levelP + 1)
     cxinv = np.stack([orc.intt(cx[i], srQ[i]) for i in range(LQ)])
     acc = {("Q", 0): None, ("Q", 1): None, ("P", 0): None, ("P", 1): None}
-    qiof = int(2.0 ** 64 / float(max(Ql))) >> 1
-    piof = int(2.0 ** 64 / float(max(Pl))) >> 1
+    qiof = qiof or int(2.0 ** 64 / float(max(Ql))) >> 1
+    piof = piof or int(2.0 ** 64 / float(max(Pl))) >> 1
     reduce = 0
 
     def red(which, mods):
@@ -101,17 +103,18 @@ def gadget_product_coeff(N, Q, P, levelQ, levelP, cx, evkQ, evkP):
     return out
 
 
-def gadget_product_single_p(N, Q, P, levelQ, levelP, cx, is_ntt, pw2, digits_per_limb, evkQ, evkP):
+def gadget_product_single_p(N, Q, P, levelQ, levelP, cx, is_ntt, pw2, digits_per_limb, evkQ, evkP, qiof=None, piof=None):
     """gadgetProductSinglePAndBitDecompLazy (core/rlwe/evaluator_gadget_product.go:190-324) + ModDown (:33-98), levelP in {0, -1}.
-    evkQ / evkP: (rows, 2, limbs, N), row = (digits before limb i) + j.  cx / results in the domain `is_ntt` names."""
+    evkQ / evkP: (rows, 2, limbs, N), row = (digits before limb i) + j.  cx / results in the domain `is_ntt` names.
+    qiof / piof: Reduce periods other than the reference's (as in gadget_product)."""
     LQ, LP = levelQ + 1, levelP + 1
     Ql, Pl = Q[:LQ], (P[:LP] if LP else [])
     srQ = [orc.SubRingConsts(N, q) for q in Ql]
     srP = [orc.SubRingConsts(N, p) for p in Pl]
     cxinv = np.stack([orc.intt(cx[i], srQ[i]) for i in range(LQ)]) if is_ntt else np.asarray(cx, dtype=np.uint64)
     mask = (1 << pw2) - 1 if pw2 else 0
-    qiof = int(2.0 ** 64 / float(max(Ql))) >> 1
-    piof = (int(2.0 ** 64 / float(max(Pl))) >> 1) if LP else 1
+    qiof = qiof or int(2.0 ** 64 / float(max(Ql))) >> 1
+    piof = piof or ((int(2.0 ** 64 / float(max(Pl))) >> 1) if LP else 1)
     accQ, accP = [None, None], [None, None]
     reduce = e = 0
     for i in range(LQ):
