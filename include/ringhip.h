@@ -356,6 +356,47 @@ int rh_bext_gadget_product_hoisted_then_add(rh_bext* be, int levelQ, int levelP,
                                             const uint64_t* evkQ_dev, const uint64_t* evkP_dev, int beta_key, const uint64_t* add0_dev,
                                             const uint64_t* add1_dev, uint64_t* ct0_dev, uint64_t* ct1_dev, int npoly);
 
+/* ---- BFV ciphertext multiply: scale-invariant tensoring (schemes/bgv/evaluator.go, the scheme of schemes/bfv) ----------------------
+ * rh_bfv pairs ringQ with ringQMul (bgv/params.go:98-108: ceil((bitlen(Q_max) + logN) / 61) NTT-friendly 61-bit primes, none shared
+ * with Q) and a plaintext modulus T: newEvaluatorPrecomp (:46-78).  Standard rings of the same degree N >= 16.  RH_ERR_ARG for T = 0,
+ * T > q_0, T equal to a modulus of Q, rings of different N or of another kind, a modulus in both chains; a call at a level whose
+ * levelQMul ringQMul does not have is refused where it is made.
+ * All blocks are device-resident, dense (npoly, level+1, N) for Q and (npoly, levelQMul+1, N) for QMul, NTT domain on entry and exit;
+ * calls are asynchronous on ringQ's stream (both rings' work goes there).  Scratch belongs to the handle and grows with the largest
+ * shape seen; rh_bfv_reserve sizes it up front (multiplies of npoly ciphertexts at the top level).  One handle per thread, like rh_bext;
+ * sharing one is safe and serial.
+ *   rh_bfv_level_qmul          levelQMul[level] = ceil((bitlen(q_0 .. q_level) + logN) / 61) - 1 (:51-56), negative status for a bad level
+ *   rh_bfv_tensor_lazy         tensorLowDeg (:1062-1102) in both rings with ONE launch: c0 = MRed(MForm(a0), b0), c2 = MRed(MForm(a1), b1),
+ *                              c1 = MRed(MForm(a0), b1) + MRed(MForm(a1), b0) left in [0, 2q) (MulCoeffsMontgomeryThenAddLazy); square != 0:
+ *                              the squaring case (:1079-1088), b* unused (NULL), c1 = 2 * MRed(MForm(a0), a1).  Any representative of
+ *                              the operands is accepted; outputs may alias inputs.
+ *   rh_bfv_quantize            quantize (:1104-1124) of npoly polys: INTTLazy in both rings, ModDownQPtoP, ModUpPtoQ, MulScalar by T
+ *                              (ring/operations.go:201-205), NTT.  cQ, cM: canonical or in [0, 2q), not modified; outQ may alias cQ.
+ *                              The middle runs as the three existing launches (rh_bext_moddown_qp_to_p, rh_bext_modup_p_to_q, MulScalar) on
+ *                              the handle's scratch, or -- on request, for level+1 <= 8 and levelQMul+1 <= 8 -- as ONE kernel with the QMul
+ *                              words in registers.  Same values.
+ *   rh_bfv_set_tuning          "fused_quantize" 0 (default: the fused kernel's measured gain was inside the run-to-run spread) / 1:
+ *                              shapes of at most 8 limbs a side take the fused kernel; larger ones (up to 32 a side) stay composed.
+ *                              Performance only.
+ *   rh_bfv_quantize_path       1: that level takes the fused kernel under the current tuning, 0: the composed sequence
+ *   rh_bfv_mul_scale_invariant tensorScaleInvariant (:975-1014) without relinearisation: (a0, a1) x (b0, b1) -> (c0, c1, c2) * T / Q.
+ *                              b0 = b1 = NULL (or b == a): the squaring case.  c0, c1, c2 may alias any input (ct0 == opOut, ct1 == opOut).
+ *                              Relinearisation (:1016-1035) is rh_bext_gadget_product_then_add on c2. */
+typedef struct rh_bfv rh_bfv;
+int rh_bfv_create(rh_bfv** out, rh_ring* ringQ, rh_ring* ringQMul, uint64_t t);
+void rh_bfv_destroy(rh_bfv* b);
+int rh_bfv_level_qmul(const rh_bfv* b, int level);
+int rh_bfv_reserve(rh_bfv* b, int npoly);
+int rh_bfv_set_tuning(rh_bfv* b, const char* key, long value);
+int rh_bfv_quantize_path(const rh_bfv* b, int level);
+int rh_bfv_tensor_lazy(rh_bfv* b, int level, const uint64_t* a0Q_dev, const uint64_t* a1Q_dev, const uint64_t* b0Q_dev, const uint64_t* b1Q_dev,
+                       const uint64_t* a0M_dev, const uint64_t* a1M_dev, const uint64_t* b0M_dev, const uint64_t* b1M_dev,
+                       uint64_t* c0Q_dev, uint64_t* c1Q_dev, uint64_t* c2Q_dev, uint64_t* c0M_dev, uint64_t* c1M_dev, uint64_t* c2M_dev,
+                       int npoly, int square);
+int rh_bfv_quantize(rh_bfv* b, int level, const uint64_t* cQ_dev, const uint64_t* cM_dev, uint64_t* outQ_dev, int npoly);
+int rh_bfv_mul_scale_invariant(rh_bfv* b, int level, const uint64_t* a0_dev, const uint64_t* a1_dev, const uint64_t* b0_dev,
+                               const uint64_t* b1_dev, uint64_t* c0_dev, uint64_t* c1_dev, uint64_t* c2_dev, int npoly);
+
 /* ---- limb-sharded hybrid key switch (BASELINE config 5): one process per GPU owns a subset of the limbs
  * of Q and P and the matching slice of the evaluation key.  Same arithmetic as rh_bext_gadget_product, cut where
  * reconstructRNS (ring/basis_extension.go:550-594) needs limbs of other owners; the exchange (an all-gather of the

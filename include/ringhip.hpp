@@ -282,6 +282,32 @@ class BasisExtender {
   std::shared_ptr<rh_bext> h_;
 };
 
+// bgv.Evaluator's scale-invariant (BFV) multiply (schemes/bgv/evaluator.go:975-1124): ringQ, ringQMul and the plaintext modulus
+class BfvEvaluator {
+ public:
+  BfvEvaluator(const Ring& q, const Ring& qmul, uint64_t t) { rh_bfv* h = nullptr; check(rh_bfv_create(&h, q.handle(), qmul.handle(), t)); h_.reset(h, rh_bfv_destroy); }
+  int LevelQMul(int level) const { int v = rh_bfv_level_qmul(h_.get(), level); if (v < 0) check(v); return v; }
+  void Reserve(int npoly) const { check(rh_bfv_reserve(h_.get(), npoly)); }
+  void SetTuning(const char* key, long value) const { check(rh_bfv_set_tuning(h_.get(), key, value)); }
+  bool QuantizeIsFused(int level) const { int v = rh_bfv_quantize_path(h_.get(), level); if (v < 0) check(v); return v != 0; }
+  // tensorLowDeg in both rings; b*: null pointers when squaring
+  void TensorLowDeg(int level, const Poly& a0Q, const Poly& a1Q, const Poly* b0Q, const Poly* b1Q, const Poly& a0M, const Poly& a1M, const Poly* b0M,
+                    const Poly* b1M, Poly& c0Q, Poly& c1Q, Poly& c2Q, Poly& c0M, Poly& c1M, Poly& c2M) const {
+    const bool sq = !b0Q;
+    check(rh_bfv_tensor_lazy(h_.get(), level, a0Q.data(), a1Q.data(), sq ? nullptr : b0Q->data(), sq ? nullptr : b1Q->data(), a0M.data(), a1M.data(),
+                             sq ? nullptr : b0M->data(), sq ? nullptr : b1M->data(), c0Q.data(), c1Q.data(), c2Q.data(), c0M.data(), c1M.data(),
+                             c2M.data(), a0Q.npoly(), sq ? 1 : 0));
+  }
+  void Quantize(int level, const Poly& cQ, const Poly& cM, Poly& outQ) const { check(rh_bfv_quantize(h_.get(), level, cQ.data(), cM.data(), outQ.data(), cQ.npoly())); }
+  // tensorScaleInvariant without relinearisation; b0 / b1 null: squaring; outputs may be the operands' blocks
+  void MulScaleInvariant(int level, const Poly& a0, const Poly& a1, const Poly* b0, const Poly* b1, Poly& c0, Poly& c1, Poly& c2) const {
+    check(rh_bfv_mul_scale_invariant(h_.get(), level, a0.data(), a1.data(), b0 ? b0->data() : nullptr, b1 ? b1->data() : nullptr, c0.data(), c1.data(),
+                                     c2.data(), a0.npoly()));
+  }
+ private:
+  std::shared_ptr<rh_bfv> h_;
+};
+
 // limb-sharded key switch (rh_kshard_*): this rank's limbs of the gadget product; the caller moves the
 // gathered source limbs (RCCL all-gather) between Digit / ModDown calls
 class KeySwitchShard {

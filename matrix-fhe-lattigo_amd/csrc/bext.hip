@@ -19,12 +19,8 @@
 #include <cstring>
 #include "engine_internal.hpp"
 #include "bext_internal.hpp"
+#include "bext_kernels.hip.hpp"
 #include "hostmath.hpp"
-
-// acc += a * b with the carry out of the 64-bit accumulator counted in cnt; b wave-uniform (a scalar-loaded constant)
-RH_DEV void mac_carry(u64& acc, u32& cnt, u32 a, u32 b) {
-  asm("v_mad_u64_u32 %0, vcc, %2, %3, %0\n\tv_addc_co_u32 %1, vcc, 0, %1, vcc" : "+v"(acc), "+v"(cnt) : "v"(a), "s"(b) : "vcc");
-}
 
 // NS: compile-time bound on the source-limb count (y_i live in registers, loops fully unrolled); EXACT: nsrc == NS.
 // NS == 0: generic fallback with the y_i in dynamic LDS ([limb][thread]).
@@ -51,13 +47,8 @@ RH_DEV void bext_body(const u64* in, int in_rows, int src_limb0, int nsrc, const
   u64 yr[NY];
   double vi = 0.0;
   auto source = [&](int i) {
-    const BextSource s = S[i];
-    u64 x = live ? in[((size_t)poly * in_rows + src_limb0 + i) * N + k] : 0;
-    if (add_mode == BEXT_ADD_CRED) x = cred(x + s.half, s.q);            // AddScalarBigint -> addscalarvec
-    else if (add_mode == BEXT_ADD_RAW) x = x + s.half;                    // reconstructRNSCentered :522
-    const u64 y = mred(x, s.qstar_inv, s.q, s.qinv);
-    vi += (double)y / (double)s.q;                                        // :576-593, one rounding per op
-    return y;
+    const u64 x = live ? in[((size_t)poly * in_rows + src_limb0 + i) * N + k] : 0;
+    return bext_source(x, S[i], add_mode, vi);
   };
   if constexpr (NS > 0) {
 #pragma unroll
@@ -74,33 +65,7 @@ RH_DEV void bext_body(const u64* in, int in_rows, int src_limb0, int nsrc, const
     const u64* cj = coef + (size_t)j * nsrc;
     u64 rlo, rhi;
     if constexpr (NS > 0) {
-      // multSum :612-649, the same 128-bit sum by columns: y = y1*2^32 + y0, c = c1*2^32 + c0 with y, c < 2^61, so
-      // y1, c1 < 2^29.  L = sum y0*c0 (carries counted in cL), M1 = sum y0*c1, M2 = sum y1*c0 (each term < 2^61: no
-      // overflow up to 8 terms, carries counted in cM beyond), H = sum y1*c1 (< 2^63 for 32 terms).  One multiply-add
-      // per partial product instead of a 128-bit add with compare-and-select carries per term.
-      u64 Lc = 0, M1 = 0, M2 = 0, H = 0;
-      u32 cL = 0, cM = 0;
-#pragma unroll
-      for (int i = 0; i < NS; ++i) {
-        if (EXACT || i < nsrc) {
-          const u64 cw = cj[i];
-          const u32 c0 = (u32)cw, c1 = (u32)(cw >> 32);
-          const u32 y0 = (u32)yr[i], y1 = (u32)(yr[i] >> 32);
-          mac_carry(Lc, cL, y0, c0);
-          if constexpr (NS <= 8) {
-            M1 += (u64)y0 * c1;
-            M2 += (u64)y1 * c0;
-          } else {
-            mac_carry(M1, cM, y0, c1);
-            mac_carry(M2, cM, y1, c0);
-          }
-          H += (u64)y1 * c1;
-        }
-      }
-      const u64 mid = M1 + M2;
-      const u64 cm = (u64)(mid < M1) + cM;                                // weight 2^96
-      rlo = Lc + (mid << 32);
-      rhi = H + cL + (mid >> 32) + (u64)(rlo < Lc) + (cm << 32);
+      bext_mult_sum<NS, EXACT>(yr, nsrc, cj, rlo, rhi);
     } else {
       u128 acc = (u128)ylds[tid] * cj[0];
       rlo = (u64)acc; rhi = (u64)(acc >> 64);
@@ -112,12 +77,11 @@ RH_DEV void bext_body(const u64* in, int in_rows, int src_limb0, int nsrc, const
         rlo = s;
       }
     }
-    const u64 hhi = mulhi64(rlo * t.pinv, t.p);
-    u64 r = rhi - hhi + t.p + vt_lds[j * (nsrc + 1) + (int)v];            // :651-672
-    if (post >= 1) r = cred(r + t.p - t.half, t.p);                       // SubScalarBigint -> subscalarvec
+    u64 r = bext_close(rlo, rhi, t, vt_lds[j * (nsrc + 1) + (int)v]);      // :651-672
+    if (post >= 1) r = bext_post_center(r, t);                            // SubScalarBigint -> subscalarvec
     if (post == 2) {
       const u64 y = live ? other[((size_t)poly * other_rows + t.limb) * N + k] : 0;
-      r = mred(2 * t.p - y + r, t.md_scalar, t.p, t.pinv);                // SubThenMulScalarMontgomeryTwoModulus
+      r = bext_post_moddown(r, y, t);                                     // SubThenMulScalarMontgomeryTwoModulus
     }
     if (live) outp[o] = r;
   };
@@ -554,6 +518,12 @@ u64 rh_half_product_mod(const std::vector<u64>& M, u64 m) { return half_product_
 void rh_gen_modup(const std::vector<u64>& Qs, const std::vector<u64>& tg, std::vector<u64>& qstar_inv_mont, std::vector<u64>& coef,
                   std::vector<u64>& vt) { gen_modup(Qs, tg, qstar_inv_mont, coef, vt); }
 u64 rh_moddown_const(const std::vector<u64>& Ps, u64 qi) { return moddown_const(Ps, qi); }
+int rh_bext_modup_plan(rh_bext* be, int kind, int dir, int lvlSrc, int lvlTgt, const BextPlan** out) {
+  BextPlan* p = nullptr;
+  if (int rc = get_modup_plan(be, kind, dir, lvlSrc, lvlTgt, &p)) return rc;
+  *out = p;
+  return 0;
+}
 int rh_bext_upload_plan(BextPlan& p, const std::vector<BextSource>& S, const std::vector<BextTarget>& T, const std::vector<u64>& coef,
                         const std::vector<u64>& vt) {
   p.nsrc = (int)S.size(); p.ntgt = (int)T.size();

@@ -32,6 +32,9 @@ u64 rh_half_product_mod(const std::vector<u64>& M, u64 m);
 void rh_gen_modup(const std::vector<u64>& Qs, const std::vector<u64>& tg, std::vector<u64>& qstar_inv_mont, std::vector<u64>& coef,
                   std::vector<u64>& vt);
 u64 rh_moddown_const(const std::vector<u64>& Ps, u64 qi);
+// the extender's cached ModUp plan src -> tgt at the given levels (built on first use, owned by the extender): kind 0 = centred ModUp
+// (post 1), 1 = ModUp + fused ModDown (post 2); dir 0 = Q -> P, 1 = P -> Q.  Callers hold the extender's lock (RhBextGuard).
+int rh_bext_modup_plan(rh_bext* be, int kind, int dir, int lvlSrc, int lvlTgt, const BextPlan** out);
 int rh_bext_upload_plan(BextPlan& p, const std::vector<BextSource>& S, const std::vector<BextTarget>& T, const std::vector<u64>& coef,
                         const std::vector<u64>& vt);
 int rh_bext_upload_sign_plan(BextPlan& p, const std::vector<SignTarget>& T, u64 qd);

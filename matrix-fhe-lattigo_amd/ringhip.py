@@ -130,6 +130,10 @@ def lib():
         "rh_bext_gadget_product_hoisted_lazy": (i, [vp, i, i, vp, vp, vp, vp, i, vp, vp, vp, vp, i]),
         "rh_bext_moddown_qp_to_q_ntt_pair": (i, [vp, i, i, vp, vp, vp, vp, vp, vp, i]),
         "rh_bext_gadget_product_hoisted_then_add": (i, [vp, i, i, vp, vp, vp, vp, i, vp, vp, vp, vp, i]),
+        "rh_bfv_create": (i, [C.POINTER(vp), vp, vp, C.c_uint64]), "rh_bfv_destroy": (None, [vp]), "rh_bfv_level_qmul": (i, [vp, i]),
+        "rh_bfv_reserve": (i, [vp, i]), "rh_bfv_set_tuning": (i, [vp, C.c_char_p, C.c_long]), "rh_bfv_quantize_path": (i, [vp, i]),
+        "rh_bfv_tensor_lazy": (i, [vp, i] + [vp] * 14 + [i, i]), "rh_bfv_quantize": (i, [vp, i, vp, vp, vp, i]),
+        "rh_bfv_mul_scale_invariant": (i, [vp, i, vp, vp, vp, vp, vp, vp, vp, i]),
         "rh_kshard_create": (i, [C.POINTER(vp), vp, vp, U64P, i, U64P, i, C.POINTER(i), i, C.POINTER(i), i]),
         "rh_kshard_destroy": (None, [vp]), "rh_kshard_num_digits": (i, [vp]),
         "rh_kshard_digit_range": (i, [vp, i, C.POINTER(i), C.POINTER(i)]),

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Secondary measurements (not the headline metric): inverse NTT, element-wise kernels, basis extension and the 3N
-transform at the BASELINE config sizes, each against its algorithmic bytes.  Prints one JSON object."""
+transform at the BASELINE config sizes, each against its algorithmic bytes.  Prints one JSON object.
+`bench_ops.py bfv [OUT.json]` runs the BFV group alone (quantize composed vs fused, the whole scale-invariant multiply) and writes
+profiles/bfv_ops.json (or OUT.json)."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -36,6 +38,89 @@ def rand_block(B, mods, N):
 def entry(name, ms, alg_bytes, units, unit_name):
     gbs = alg_bytes / (ms * 1e-3) / 1e9
     return {"op": name, "ms": round(ms, 4), unit_name + "_per_s": units / (ms * 1e-3), "algorithmic_GBps": round(gbs, 1), "frac_of_8TBps": round(gbs / PEAK, 3)}
+
+
+def bfv_group(out_path):
+    """N = 2^15, 8 limbs of Q (GenModuli [55] + [45]*7: 7 limbs of QMul, the register variant of the fused quantize), batch 64.
+    (a) quantize through the three existing entry points, (b) rh_bfv_quantize (fused kernel), (c) the whole multiply.  (a) uses only entry
+    points the library had before the BFV ones and is timed HERE, in the same process as (b) and alternating with it, not in a run of an older
+    build: the two then see the same machine state (the extension kernels it launches compute what they did before); every figure is the median of `rounds` windows of `reps` calls, with the windows' min and max as the spread."""
+    import statistics
+    from oracle import primes
+    logN, B, rounds, reps = 15, 64, 7, 20
+    N = 1 << logN
+    Q, M = primes.gen_moduli(logN + 1, [55] + [45] * 7, [61] * 8)
+    ring_bits = 1
+    for q in Q:
+        ring_bits *= q
+    M = M[:-(-(ring_bits.bit_length() + logN) // 61)]
+    LQ, LM, T = len(Q), len(M), 65537
+    rq, rm = rh.Ring(N, Q), rh.Ring(N, M); rq.set_stream(stream.cuda_stream); rm.set_stream(stream.cuda_stream)
+    ev = rh.bgv.Evaluator(rq, rm, T); ev.reserve(B)
+    be = rh.BasisExtender(rq, rm)
+    assert ev.QuantizePath(LQ - 1) == "composed" and ev.levelQMul[LQ - 1] == LM - 1      # the default; "fused_quantize" = 1 selects the kernel
+    xq, xm = rand_block(B, Q, N), rand_block(B, M, N)
+    pq, pm = rh.DevicePoly.from_torch(rq, xq), rh.DevicePoly.from_torch(rm, xm)
+    tq, tm, oq = (rh.DevicePoly.from_torch(rq, torch.empty_like(xq)), rh.DevicePoly.from_torch(rm, torch.empty_like(xm)),
+                  rh.DevicePoly.from_torch(rq, torch.empty_like(xq)))
+
+    def composed():                                   # quantize (schemes/bgv/evaluator.go:1104-1124) call by call, public API of the parent commit
+        rq.INTTLazy(pq, tq); rm.INTTLazy(pm, tm)
+        be.ModDownQPtoP(LQ - 1, LM - 1, tq, tm, tm)
+        be.ModUpPtoQ(LM - 1, LQ - 1, tm, tq)
+        rq.MulScalar(tq, T, tq)
+        rq.NTT(tq, oq)
+
+    def fused():
+        ev.Quantize(LQ - 1, pq, pm, oq)
+    composed(); ref = oq.numpy().copy(); fused()
+    assert np.array_equal(ref, oq.numpy()), "composed path inside rh_bfv_quantize differs from the call-by-call sequence"
+    ev.set_tuning("fused_quantize", 1); fused()
+    assert ev.QuantizePath(LQ - 1) == "fused" and np.array_equal(ref, oq.numpy()), "fused quantize differs from the composed sequence"
+    ta, tb, tinner = [], [], []
+    for _ in range(rounds):
+        ta.append(timed(composed, reps=reps)); tb.append(timed(fused, reps=reps))
+        ev.set_tuning("fused_quantize", 0); tinner.append(timed(fused, reps=reps)); ev.set_tuning("fused_quantize", 1)
+    ev.set_tuning("fused_quantize", 0)
+    mk = lambda: rh.DevicePoly.from_torch(rq, rand_block(B, Q, N))
+    ct0, ct1 = rh.Ciphertext([mk(), mk()], is_ntt=True), rh.Ciphertext([mk(), mk()], is_ntt=True)
+    out = rh.Ciphertext([mk(), mk(), mk()], is_ntt=True)
+    tc, tcf = [], []
+    for _ in range(rounds):
+        tc.append(timed(lambda: ev.MulScaleInvariant(ct0, ct1, out), reps=5, warm=2))
+        ev.set_tuning("fused_quantize", 1); tcf.append(timed(lambda: ev.MulScaleInvariant(ct0, ct1, out), reps=5, warm=2)); ev.set_tuning("fused_quantize", 0)
+    stat = lambda v: {"ms_median": round(statistics.median(v), 4), "ms_min": round(min(v), 4), "ms_max": round(max(v), 4)}
+    q_tr = 16.0 * (2 * LQ + LM)                        # the three transforms of a quantize, bytes per coefficient
+    bytes_a, bytes_b = q_tr + 8.0 * (4 * LQ + 3 * LM), q_tr + 8.0 * (2 * LQ + LM)     # ModDownQPtoP LQ + 2 LM, ModUpPtoQ LM + LQ, MulScalar 2 LQ; fused: LQ + LM in, LQ out
+    mul_bytes = 296.0 * LQ + 224.0 * LM               # DESIGN.md: 10 LQ + 7 LM limb transforms, ModUp, tensor, fused quantize middle
+    mul_bytes_composed = mul_bytes + 3 * 8.0 * (2 * LQ + 2 * LM)     # the composed middle moves 8 (2 LQ + 2 LM) more per quantize
+    a, b, c = stat(ta), stat(tb), stat(tc)
+    gbs = lambda byt, ms: round(byt * N * B / (ms * 1e-3) / 1e9, 1)
+    a.update(op="(a) quantize composed: INTTLazy x2, rh_bext_moddown_qp_to_p, rh_bext_modup_p_to_q, MulScalar, NTT", algorithmic_GBps=gbs(bytes_a, a["ms_median"]))
+    b.update(op="(b) rh_bfv_quantize, fused kernel (fused_quantize = 1)", algorithmic_GBps=gbs(bytes_b, b["ms_median"]))
+    inner = stat(tinner); inner.update(op="(a') rh_bfv_quantize as shipped (fused_quantize = 0: the composed sequence on the handle's scratch)")
+    cf = stat(tcf); cf.update(op="(c') the same with fused_quantize = 1", ctmul_per_s=round(B / (cf["ms_median"] * 1e-3), 1),
+                              algorithmic_bytes_per_coefficient=mul_bytes, algorithmic_GBps=gbs(mul_bytes, cf["ms_median"]),
+                              frac_of_8TBps=round(gbs(mul_bytes, cf["ms_median"]) / PEAK, 3))
+    c.update(op="(c) rh_bfv_mul_scale_invariant as shipped (no relinearisation)", ctmul_per_s=round(B / (c["ms_median"] * 1e-3), 1),
+             limb_transforms_per_ctmul=10 * LQ + 7 * LM, algorithmic_bytes_per_coefficient=mul_bytes_composed,
+             algorithmic_GBps=gbs(mul_bytes_composed, c["ms_median"]), frac_of_8TBps=round(gbs(mul_bytes_composed, c["ms_median"]) / PEAK, 3))
+    spread = max(a["ms_max"] - a["ms_min"], b["ms_max"] - b["ms_min"])
+    from bench import csrc_tree_hash                 # ties the numbers to the kernel sources they were taken on, as tools/make_traffic.py does
+    res = {"device": torch.cuda.get_device_name(0), "csrc_tree": csrc_tree_hash(), "shape": {"N": N, "limbs_Q": LQ, "limbs_QMul": LM, "batch": B, "t": T},
+           "method": "%d alternating windows of %d calls each (5 for the multiply), device events, 2 warm-up calls per window" % (rounds, reps),
+           "results": [a, inner, b, c, cf], "run_to_run_spread_ms": round(spread, 4),
+           "fused_beats_composed_by_more_than_spread": bool(a["ms_median"] - b["ms_median"] > spread)}
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res, indent=1))
+    ev.close(); be.close(); rq.close(); rm.close()
+
+
+if sys.argv[1:2] == ["bfv"]:
+    bfv_group(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "bfv_ops.json"))
+    sys.exit(0)
 
 
 res = []
