@@ -397,6 +397,28 @@ int rh_bfv_quantize(rh_bfv* b, int level, const uint64_t* cQ_dev, const uint64_t
 int rh_bfv_mul_scale_invariant(rh_bfv* b, int level, const uint64_t* a0_dev, const uint64_t* a1_dev, const uint64_t* b0_dev,
                                const uint64_t* b1_dev, uint64_t* c0_dev, uint64_t* c1_dev, uint64_t* c2_dev, int npoly);
 
+/* ---- BGV: standard tensoring and scale matching (schemes/bgv/evaluator.go) ------------------------------------------------------------
+ * Entry points on a STANDARD ring handle (RH_ERR_ARG for a 3N or conjugate-invariant ring, a null handle, a level out of range, a scalar
+ * that is not below its modulus).  Blocks are device-resident, dense (npoly, level+1, N), NTT domain, residues in [0, q_i) in and out;
+ * per-limb scalars are host arrays of level+1 words.  Asynchronous on the ring's stream.  Every thread reads all its operands before it
+ * writes: outputs may be any of the inputs (opOut is op0 / op1).
+ *   rh_bgv_tensor     tensorStandard, ct x ct (:665-734), and the ct x ct branch of mulRelinThenAdd (:1299-1367) in ONE launch:
+ *                     c0 (+)= a0 b0 K, c1 (+)= (a0 b1 + a1 b0) K, c2 (+)= a1 b1 K with K = T * r0.  k[i] = T * r0 * 2^128 mod q_i (r0 = 1:
+ *                     tMontgomery of :46-78, one Montgomery factor per MRed).  b0 = b1 = NULL (or b == a): the squaring case (:704-708).
+ *                     accumulate 0: outputs written; 1: c0, c1, c2 read and added to (no relinearisation: opOut has degree 2);
+ *                     2: c0, c1 read and added to, c2 written (the relin form :1353: c2 is scratch for the gadget product).
+ *                     r1 (NULL or MForm(r1) per limb): every accumulator is multiplied by r1 before the add (:1324-1326).
+ *   rh_bgv_mul_plain  the plaintext branches (:737-748, :1370-1400): out_j (+)= ct_j * pt * K for the 1, 2 or 3 components given
+ *                     (ct1 / ct2 NULL with out1 / out2: fewer components); k, r1, accumulate (0 / 1) as above.
+ *   rh_bgv_axpby      matchScaleThenEvaluateInPlace (:288-305): out = r0 a + r1 b (sub != 0: - r1 b) with r0[i] = MForm(r0), r1[i] = MForm(r1);
+ *                     b = r1 = NULL: out = r0 a; a = r0 = NULL: out = +- r1 b (a component the other operand does not have). */
+int rh_bgv_tensor(rh_ring* r, int level, const uint64_t* a0_dev, const uint64_t* a1_dev, const uint64_t* b0_dev, const uint64_t* b1_dev,
+                  uint64_t* c0_dev, uint64_t* c1_dev, uint64_t* c2_dev, int npoly, const uint64_t* k, const uint64_t* r1, int accumulate);
+int rh_bgv_mul_plain(rh_ring* r, int level, const uint64_t* ct0_dev, const uint64_t* ct1_dev, const uint64_t* ct2_dev, const uint64_t* pt_dev,
+                     uint64_t* out0_dev, uint64_t* out1_dev, uint64_t* out2_dev, int npoly, const uint64_t* k, const uint64_t* r1, int accumulate);
+int rh_bgv_axpby(rh_ring* r, int level, const uint64_t* a_dev, const uint64_t* b_dev, uint64_t* out_dev, int npoly, const uint64_t* r0,
+                 const uint64_t* r1, int sub);
+
 /* ---- limb-sharded hybrid key switch (BASELINE config 5): one process per GPU owns a subset of the limbs
  * of Q and P and the matching slice of the evaluation key.  Same arithmetic as rh_bext_gadget_product, cut where
  * reconstructRNS (ring/basis_extension.go:550-594) needs limbs of other owners; the exchange (an all-gather of the

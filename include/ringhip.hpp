@@ -180,6 +180,20 @@ class Ring {
   void TensorDegree1(const Poly& a0, const Poly& a1, const Poly& b0, const Poly& b1, Poly& c0, Poly& c1, Poly& c2, bool mformFirst = true) const {
     check(rh_ring_tensor_degree1(h_.get(), a0.data(), a1.data(), b0.data(), b1.data(), c0.data(), c1.data(), c2.data(), a0.npoly(), level_, mformFirst ? 1 : 0));
   }
+  // BGV (schemes/bgv/evaluator.go): tensorStandard / mulRelinThenAdd ct x ct as one kernel, k[i] = T r0 2^128 mod q_i; b0 / b1 null: squaring;
+  // accumulate 0 / 1 / 2 and r1 (null or MForm(r1) per limb) as rh_bgv_tensor takes them.  BgvAxpby: out = r0 a +- r1 b (an operand and its scalar may be null)
+  void BgvTensor(const Poly& a0, const Poly& a1, const Poly* b0, const Poly* b1, Poly& c0, Poly& c1, Poly& c2, const uint64_t* k, const uint64_t* r1 = nullptr,
+                 int accumulate = 0) const {
+    check(rh_bgv_tensor(h_.get(), level_, a0.data(), a1.data(), b0 ? b0->data() : nullptr, b1 ? b1->data() : nullptr, c0.data(), c1.data(), c2.data(), a0.npoly(), k, r1, accumulate));
+  }
+  void BgvMulPlain(const Poly& ct0, const Poly* ct1, const Poly* ct2, const Poly& pt, Poly& out0, Poly* out1, Poly* out2, const uint64_t* k, const uint64_t* r1 = nullptr,
+                   int accumulate = 0) const {
+    check(rh_bgv_mul_plain(h_.get(), level_, ct0.data(), ct1 ? ct1->data() : nullptr, ct2 ? ct2->data() : nullptr, pt.data(), out0.data(), out1 ? out1->data() : nullptr,
+                           out2 ? out2->data() : nullptr, ct0.npoly(), k, r1, accumulate));
+  }
+  void BgvAxpby(const Poly* a, const Poly* b, Poly& out, const uint64_t* r0, const uint64_t* r1, bool sub = false) const {
+    check(rh_bgv_axpby(h_.get(), level_, a ? a->data() : nullptr, b ? b->data() : nullptr, out.data(), out.npoly(), r0, r1, sub ? 1 : 0));
+  }
   void AutomorphismNTT(const Poly& in, uint64_t gen, Poly& out) const { check(rh_ring_automorphism_ntt(h_.get(), level_, in.data(), gen, out.data(), in.npoly(), 0)); }
   void Automorphism(const Poly& in, uint64_t gen, Poly& out) const { check(rh_ring_automorphism(h_.get(), level_, in.data(), gen, out.data(), in.npoly())); }
   // AutomorphismNTTWithIndex / ...ThenAddLazy (ring/automorphism.go:50-117): `index` = a 1-poly, 1-limb device block holding the lookup table

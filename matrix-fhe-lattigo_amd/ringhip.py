@@ -134,6 +134,8 @@ def lib():
         "rh_bfv_reserve": (i, [vp, i]), "rh_bfv_set_tuning": (i, [vp, C.c_char_p, C.c_long]), "rh_bfv_quantize_path": (i, [vp, i]),
         "rh_bfv_tensor_lazy": (i, [vp, i] + [vp] * 14 + [i, i]), "rh_bfv_quantize": (i, [vp, i, vp, vp, vp, i]),
         "rh_bfv_mul_scale_invariant": (i, [vp, i, vp, vp, vp, vp, vp, vp, vp, i]),
+        "rh_bgv_tensor": (i, [vp, i] + [vp] * 7 + [i, U64P, U64P, i]), "rh_bgv_mul_plain": (i, [vp, i] + [vp] * 7 + [i, U64P, U64P, i]),
+        "rh_bgv_axpby": (i, [vp, i, vp, vp, vp, i, U64P, U64P, i]),
         "rh_kshard_create": (i, [C.POINTER(vp), vp, vp, U64P, i, U64P, i, C.POINTER(i), i, C.POINTER(i), i]),
         "rh_kshard_destroy": (None, [vp]), "rh_kshard_num_digits": (i, [vp]),
         "rh_kshard_digit_range": (i, [vp, i, C.POINTER(i), C.POINTER(i)]),

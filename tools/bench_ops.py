@@ -2,7 +2,8 @@
 """Secondary measurements (not the headline metric): inverse NTT, element-wise kernels, basis extension and the 3N
 transform at the BASELINE config sizes, each against its algorithmic bytes.  Prints one JSON object.
 `bench_ops.py bfv [OUT.json]` runs the BFV group alone (quantize composed vs fused, the whole scale-invariant multiply) and writes
-profiles/bfv_ops.json (or OUT.json)."""
+profiles/bfv_ops.json (or OUT.json); `bench_ops.py bgv [OUT.json]` the BGV group (standard tensoring and multiply-accumulate, one kernel each
+against the reference's sequence of ring calls) and writes profiles/bgv_ops.json."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -116,6 +117,79 @@ def bfv_group(out_path):
         f.write("\n")
     print(json.dumps(res, indent=1))
     ev.close(); be.close(); rq.close(); rm.close()
+
+
+def bgv_group(out_path):
+    """N = 2^15, 16 limbs of Qi60, 4 of Pi60, batch 32: one block is 128 MiB, an operand set 0.9 GiB, far beyond the Infinity Cache.
+    bgv.Evaluator with fused=True (rh_bgv_tensor) against fused=False, which issues the reference's own sequence of ring calls through entry
+    points the library had before (MulRNSScalarMontgomery, MulScalar, MulCoeffsMontgomery(ThenAdd)): the composed path is the baseline, timed
+    HERE, alternating with the fused one.  Medians of `rounds` windows of `reps` calls, the windows' min and max as the spread.  Algorithmic
+    bytes count whole-limb passes of the tensoring alone (7 vs 17; accumulate with r0, r1 != 1: 10 vs 30 into degree 2, 8 vs 25 with relin);
+    the relinearisation and the rescale are the same launches on both sides and are reported as times only."""
+    import statistics
+    N, LQ, LP, B, T, rounds, reps = 1 << 15, 16, 4, 32, 65537, 7, 10
+    Q, P = QI60[:LQ], PI60[:LP]
+    rq, rp = rh.Ring(N, Q), rh.Ring(N, P); rq.set_stream(stream.cuda_stream); rp.set_stream(stream.cuda_stream)
+    digits = (LQ + LP - 1) // LP
+    evkQ, evkP = rand_block(2 * digits, Q, N).cpu().numpy().astype(np.uint64), rand_block(2 * digits, P, N).cpu().numpy().astype(np.uint64)
+    rlk = rh.rlwe.GadgetCiphertext(rq, rp, evkQ.reshape(digits, 2, LQ, N), evkP.reshape(digits, 2, LP, N))
+    evs = {True: rh.bgv.Evaluator(rq, None, T, ringP=rp, rlk=rlk, fused=True), False: rh.bgv.Evaluator(rq, None, T, ringP=rp, rlk=rlk, fused=False)}
+    mk = lambda: rh.DevicePoly.from_torch(rq, rand_block(B, Q, N))
+    ct0, ct1 = rh.Ciphertext([mk(), mk()], is_ntt=True), rh.Ciphertext([mk(), mk()], is_ntt=True)
+    ct0.Scale, ct1.Scale = 3, 5
+    out2, out1, low = rh.Ciphertext([mk(), mk(), mk()], is_ntt=True), rh.Ciphertext([mk(), mk()], is_ntt=True), rh.Ciphertext([mk(), mk()], is_ntt=True)
+
+    def set7(ct):                                     # an accumulator whose scale differs from the product's: r0 != 1 and r1 != 1 on every call
+        ct.Scale = 7
+    cases = {
+        "Mul (tensorStandard, no relinearisation)": (lambda ev: ev.Mul(ct0, ct1, out2), 7, 17),
+        "MulThenAdd into degree 2, r0, r1 != 1": (lambda ev: (set7(out2), ev.MulThenAdd(ct0, ct1, out2)), 10, 30),
+        "MulRelin + Rescale": (lambda ev: (ev.MulRelin(ct0, ct1, out1), ev.Rescale(out1, low)), 7, 17),
+        "MulRelinThenAdd, r0, r1 != 1": (lambda ev: (set7(out1), ev.MulRelinThenAdd(ct0, ct1, out1)), 8, 25),
+    }
+    # same bits first, on the shapes that are timed (seeded inputs, both paths from the same accumulator)
+    for name, (fn, _, _) in cases.items():
+        acc = out2 if "degree 2" in name or "no relin" in name else out1
+        keep = [v.numpy().copy() for v in acc.Value]
+        res = []
+        for fused in (True, False):
+            for v, h in zip(acc.Value, keep):
+                _ = rh.DevicePoly.from_numpy(rq, h); rq.CopyLvl(_, v)
+            fn(evs[fused]); res.append([v.numpy() for v in (low.Value if "Rescale" in name else acc.Value)])
+        assert all(np.array_equal(x, y) for x, y in zip(*res)), "fused and composed differ: " + name
+    stat = lambda v: {"ms_median": round(statistics.median(v), 4), "ms_min": round(min(v), 4), "ms_max": round(max(v), 4)}
+    results = []
+    for name, (fn, pf, pc) in cases.items():
+        tf, tc = [], []
+        n = reps if "Relin" in name else 5 * reps      # the tensoring alone is a fraction of a millisecond: longer windows
+        for _ in range(rounds):
+            tf.append(timed(lambda: fn(evs[True]), reps=n)); tc.append(timed(lambda: fn(evs[False]), reps=n))
+        f, c = stat(tf), stat(tc)
+        limb_bytes = 8.0 * N * LQ * B
+        entry_ = {"op": name, "fused": f, "composed": c, "ratio_composed_over_fused": round(c["ms_median"] / f["ms_median"], 3),
+                  "tensor_passes_fused": pf, "tensor_passes_composed": pc}
+        if "Relin" not in name:                       # the tensoring alone: algorithmic bandwidth means something
+            f["algorithmic_GBps"] = round(pf * limb_bytes / (f["ms_median"] * 1e-3) / 1e9, 1)
+            c["algorithmic_GBps"] = round(pc * limb_bytes / (c["ms_median"] * 1e-3) / 1e9, 1)
+            f["frac_of_8TBps"] = round(f["algorithmic_GBps"] / PEAK, 3)
+        results.append(entry_)
+    from bench import csrc_tree_hash
+    res = {"device": torch.cuda.get_device_name(0), "csrc_tree": csrc_tree_hash(), "shape": {"N": N, "limbs_Q": LQ, "limbs_P": LP, "batch": B, "t": T},
+           "method": "%d alternating windows of %d calls each (%d for the two cases without relinearisation), device events, 2 warm-up calls per window; "
+                     "clocks left to the driver's default governor" % (rounds, reps, 5 * reps),
+           "results": results}
+    with open(out_path, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(res, indent=1))
+    for ev in evs.values():
+        ev.close()
+    rq.close(); rp.close()
+
+
+if sys.argv[1:2] == ["bgv"]:
+    bgv_group(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "bgv_ops.json"))
+    sys.exit(0)
 
 
 if sys.argv[1:2] == ["bfv"]:
