@@ -195,6 +195,11 @@ int rh_ring_ntt_phase(rh_ring* r, const uint64_t* in_dev, uint64_t* out_dev, int
  *   digit_pipeline  1: key switch transforms all digit blocks with one software-pipelined stream of launches (default; N = 2^14..2^16)
  *   fuse3n          1: 3N rings, split + radix-3 layer fused with the sub-transforms' column stages (default)
  *   perm_fwd_shape / perm_inv_shape  3N permutation tile as 10*A + B: block-order runs of 2^A words, rank-order runs of nb * 2^B words
+ *   nt_streams      cache policy of the data streams (a hint: every value gives the same bits).  1: non-temporal once a launch's working set
+ *                   passes its threshold (512 MiB; 256 MiB for the key switch's digit pipeline), and in the pipelined launches, which only exist for
+ *                   batches far beyond the Infinity Cache (default); 0: default policy everywhere (A/B runs: bench.py --tune nt_streams=0);
+ *                   2: non-temporal at every size (tests/test_gpu_cache_policy.py runs every variant at test sizes).  Other values: RH_ERR_ARG.
+ *                   3N rings hand the value on to their radix-2 sub-ring
  * One key changes a LAYOUT, not a value (3N rings, N = 3*2^k >= 24576, default 0):
  *   ntt3n_block_order  1: rh_ring_ntt / rh_ring_intt keep the NTT domain in "block order" (slot j of block c of the radix-2
  *                   sub-transforms at word c*N/6 + j) instead of the Go transformer's ascending-totative order

@@ -277,7 +277,7 @@ static int tensor_launch(rh_bfv* b, int level, int lq, const BfvTensorSide& sq, 
   const unsigned rows = (unsigned)npoly * (unsigned)(level + 1 + lq + 1), n = (unsigned)b->Q->N;
   if (rows == 0) return RH_OK;
   unsigned chunks = (n / 2 + 1023) / 1024; if (chunks < 1) chunks = 1; if (chunks > 64) chunks = 64;
-  const int nt = (b->Q->nt_streams && (size_t)rows * n * 8 >= ((size_t)512 << 20)) ? 1 : 0;     // as rh_streams_beyond_cache
+  const int nt = rh_nt_policy(b->Q->nt_streams, (size_t)rows * n * 8, (size_t)512 << 20) ? 1 : 0;     // as rh_streams_beyond_cache
   const dim3 grid(rows, chunks);
   hipStream_t st = rh_stream(b->Q);
   (void)hipGetLastError();

@@ -168,7 +168,7 @@ struct BgvGrid { dim3 grid; int nt; };
 static BgvGrid bgv_grid(const rh_ring* r, unsigned rows) {
   const unsigned n = (unsigned)r->N;
   unsigned chunks = (n / 2 + 1023) / 1024; if (chunks < 1) chunks = 1; if (chunks > 64) chunks = 64;
-  return {dim3(rows, chunks), (r->nt_streams && (size_t)rows * n * 8 >= ((size_t)512 << 20)) ? 1 : 0};     // as rh_streams_beyond_cache
+  return {dim3(rows, chunks), rh_nt_policy(r->nt_streams, (size_t)rows * n * 8, (size_t)512 << 20) ? 1 : 0};     // as rh_streams_beyond_cache
 }
 
 extern "C" int rh_bgv_tensor(rh_ring* r, int level, const uint64_t* a0, const uint64_t* a1, const uint64_t* b0, const uint64_t* b1,

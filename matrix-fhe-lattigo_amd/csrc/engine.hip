@@ -386,7 +386,7 @@ static int std_ntt_launch_span(rh_ring* r, const u64* in, u64* out, int npoly, i
   }
   const int S1 = logN - LT;
   const unsigned tiles = rows << S1;
-  const bool nt = r->nt_streams && (size_t)rows * (size_t)r->N * 8 >= ((size_t)512 << 20);   // non-temporal data streams beyond the Infinity Cache (see rh_streams_beyond_cache)
+  const bool nt = rh_nt_policy(r->nt_streams, (size_t)rows * (size_t)r->N * 8, (size_t)512 << 20);   // non-temporal data streams beyond the Infinity Cache (see rh_streams_beyond_cache)
   if (phase == 0 && !(lazy && !inverse) && one_pass_ok(r)) {          // (the forward lazy form keeps the reference's representatives: Montgomery bodies, two passes)
     const size_t lds = ((size_t)LDS_WORDS * 8) << S1;
     const dim3 wg(256u << S1);
@@ -460,10 +460,15 @@ static void launch_fused(rh_ring* r, const u64* in1, u64* out1, unsigned n1, u64
                          size_t toff, const LimbConsts* c, int Lrows) {
   const unsigned grid = n1 > n2 ? n1 : n2;
   hipStream_t st = rh_stream(r);
-  if (r->asm_tile && S1 >= 2 && S1 <= 4 && r->asm_cols)
-    if (r->nt_streams) ntt_fwd_fused_asm<S1, true, true><<<grid, 256, 0, st>>>(in1, out1, n1, data2, n2, npoly2, r->d_tw_fwd + toff, r->d_twk_fwd + toff, c, Lrows, r->logN);
-    else ntt_fwd_fused_asm<S1, true, false><<<grid, 256, 0, st>>>(in1, out1, n1, data2, n2, npoly2, r->d_tw_fwd + toff, r->d_twk_fwd + toff, c, Lrows, r->logN);
-  else if (r->asm_tile)
+  constexpr bool has_acols = S1 >= 2 && S1 <= 4;              // the hand-scheduled column stages exist for N = 2^14 .. 2^16 only: no instantiation elsewhere
+  if constexpr (has_acols) {
+    if (r->asm_tile && r->asm_cols) {
+      if (r->nt_streams) ntt_fwd_fused_asm<S1, true, true><<<grid, 256, 0, st>>>(in1, out1, n1, data2, n2, npoly2, r->d_tw_fwd + toff, r->d_twk_fwd + toff, c, Lrows, r->logN);
+      else ntt_fwd_fused_asm<S1, true, false><<<grid, 256, 0, st>>>(in1, out1, n1, data2, n2, npoly2, r->d_tw_fwd + toff, r->d_twk_fwd + toff, c, Lrows, r->logN);
+      return;
+    }
+  }
+  if (r->asm_tile)
     ntt_fwd_fused_asm<S1, false><<<grid, 256, 0, st>>>(in1, out1, n1, data2, n2, npoly2, r->d_tw_fwd + toff, r->d_twk_fwd + toff, c, Lrows, r->logN);
   else
     ntt_fwd_fused<ShoupPolicy, S1><<<grid, 256, 0, st>>>(in1, out1, n1, data2, n2, npoly2, r->d_tw_fwd + toff, r->d_twk_fwd + toff,
@@ -509,17 +514,22 @@ static void launch_inv_fused(rh_ring* r, const u64* in1, const u64* in1b, u64* o
                              size_t toff, int limb0, const LimbConsts* c, int Lrows) {
   const unsigned grid = n1 > n2 ? n1 : n2;
   hipStream_t st = rh_stream(r);
-  const bool acols = S1 >= 2 && S1 <= 4 && r->asm_cols;
+  constexpr bool has_acols = S1 >= 2 && S1 <= 4;              // (as launch_fused: no hand-scheduled column stages outside N = 2^14 .. 2^16)
+  const bool acols = has_acols && r->asm_cols;
   if (in1b) {                 // rh_ring_intt_mul: product on load, 2^64-scaled N^-1 constants (c = d_consts_r + limb0)
     const tw2* lw = r->d_lastw_r + limb0;
-    if (acols) ntt_inv_fused_asm<S1, true, true><<<grid, 256, 0, st>>>(in1, in1b, out1, n1, npoly1, data2, n2, r->d_twk_inv + toff, r->d_tw_inv + toff, lw, c, Lrows, r->logN);
-    else ntt_inv_fused_asm<S1, false, true><<<grid, 256, 0, st>>>(in1, in1b, out1, n1, npoly1, data2, n2, r->d_twk_inv + toff, r->d_tw_inv + toff, lw, c, Lrows, r->logN);
+    if constexpr (has_acols) {
+      if (acols) { ntt_inv_fused_asm<S1, true, true><<<grid, 256, 0, st>>>(in1, in1b, out1, n1, npoly1, data2, n2, r->d_twk_inv + toff, r->d_tw_inv + toff, lw, c, Lrows, r->logN); return; }
+    }
+    ntt_inv_fused_asm<S1, false, true><<<grid, 256, 0, st>>>(in1, in1b, out1, n1, npoly1, data2, n2, r->d_twk_inv + toff, r->d_tw_inv + toff, lw, c, Lrows, r->logN);
     return;
   }
   const tw2* lw = r->d_lastw + limb0;
-  if (acols && !r->nt_streams) ntt_inv_fused_asm<S1, true, false, false><<<grid, 256, 0, st>>>(in1, nullptr, out1, n1, npoly1, data2, n2, r->d_twk_inv + toff, r->d_tw_inv + toff, lw, c, Lrows, r->logN);
-  else if (acols) ntt_inv_fused_asm<S1, true, false><<<grid, 256, 0, st>>>(in1, nullptr, out1, n1, npoly1, data2, n2, r->d_twk_inv + toff, r->d_tw_inv + toff, lw, c, Lrows, r->logN);
-  else ntt_inv_fused_asm<S1, false, false><<<grid, 256, 0, st>>>(in1, nullptr, out1, n1, npoly1, data2, n2, r->d_twk_inv + toff, r->d_tw_inv + toff, lw, c, Lrows, r->logN);
+  if constexpr (has_acols) {
+    if (acols && !r->nt_streams) { ntt_inv_fused_asm<S1, true, false, false><<<grid, 256, 0, st>>>(in1, nullptr, out1, n1, npoly1, data2, n2, r->d_twk_inv + toff, r->d_tw_inv + toff, lw, c, Lrows, r->logN); return; }
+    if (acols) { ntt_inv_fused_asm<S1, true, false><<<grid, 256, 0, st>>>(in1, nullptr, out1, n1, npoly1, data2, n2, r->d_twk_inv + toff, r->d_tw_inv + toff, lw, c, Lrows, r->logN); return; }
+  }
+  ntt_inv_fused_asm<S1, false, false><<<grid, 256, 0, st>>>(in1, nullptr, out1, n1, npoly1, data2, n2, r->d_twk_inv + toff, r->d_tw_inv + toff, lw, c, Lrows, r->logN);
 }
 // Inverse transform of a large batch: launch j = tile stages of span j fused with column stages (+ N^-1) of span j-1.
 static int std_ntt_inv_pipelined(rh_ring* r, const u64* in, u64* out, int npoly, int Lrows, int limb0, int chunk, const u64* in_b = nullptr) {
@@ -636,7 +646,7 @@ int rh_std_ntt_fwd_blocks(rh_ring* r, u64* data, size_t block_stride, int npoly,
     // non-temporal data streams once a block is too large to be re-read from the Infinity Cache by the next launch's tile stages
 #define RH_GAP2(S, Z) do { if (nt) ntt_fwd_fused_gap_asm<S, Z, true><<<grid, 256, 0, st>>>(d1, n1, g1, d2, n2, npoly, g2, r->d_tw_fwd, r->d_twk_fwd, r->d_consts); \
                            else ntt_fwd_fused_gap_asm<S, Z, false><<<grid, 256, 0, st>>>(d1, n1, g1, d2, n2, npoly, g2, r->d_tw_fwd, r->d_twk_fwd, r->d_consts); } while (0)
-    const bool nt = r->nt_streams && (size_t)npoly * (size_t)Ls * (size_t)r->N * 8 >= ((size_t)256 << 20);
+    const bool nt = rh_nt_policy(r->nt_streams, (size_t)npoly * (size_t)Ls * (size_t)r->N * 8, (size_t)256 << 20);
     switch (S1) {
       case 2: if (lazy_out) RH_GAP2(2, true); else RH_GAP2(2, false); break;
       case 3: if (lazy_out) RH_GAP2(3, true); else RH_GAP2(3, false); break;
@@ -695,9 +705,9 @@ int rh_std_intt_rows(rh_ring* r, const u64* in, int in_rows, u64* out, int out_r
 }
 
 // ---- 3N transform (ntt3n.hip), b = 1: the hand-scheduled layer kernels live in this translation unit with the tile bodies they fuse with
-void rh_3n_launch_layer(bool inverse, int S1, unsigned nblocks, hipStream_t st, const u64* in, u64* out, const N3Layer& a, bool nt_streams) {
+void rh_3n_launch_layer(bool inverse, int S1, unsigned nblocks, hipStream_t st, const u64* in, u64* out, const N3Layer& a, int nt_streams) {
   // a unit moves 6 * 2^S1 coefficients per thread: nblocks * 256 * 6 * 2^S1 * 8 bytes per direction; non-temporal streams beyond 512 MiB
-  const bool nt = nt_streams && (size_t)nblocks * 256 * 6 * ((size_t)8 << S1) >= ((size_t)512 << 20);   // tuning nt_streams = 0: default policy everywhere
+  const bool nt = rh_nt_policy(nt_streams, (size_t)nblocks * 256 * 6 * ((size_t)8 << S1), (size_t)512 << 20);   // tuning nt_streams = 0: default policy everywhere, 2: non-temporal at every size
 #define RH_3NL2(S, I) do { if (nt) ntt3n_layer_asm<S, I, true><<<nblocks, 256, 0, st>>>(in, out, a); else ntt3n_layer_asm<S, I, false><<<nblocks, 256, 0, st>>>(in, out, a); } while (0)
 #define RH_3NL(S) do { if (inverse) RH_3NL2(S, true); else RH_3NL2(S, false); } while (0)
   if (S1 == 1) RH_3NL(1); else if (S1 == 2) RH_3NL(2); else RH_3NL(3);
@@ -709,7 +719,7 @@ bool rh_can_fuse_submul(const rh_ring* r) { return r->kind == RH_RING_STANDARD &
 // column stages as usual, then ntt_fwd_tile_submul.  y / out: (poly, limb) blocks with y_rows / out_rows limbs per poly.
 // Cache policy of a launch's data streams: non-temporal once the rows it moves exceed twice the 256 MiB Infinity Cache (the generated
 // bodies exist in both forms, tools/gen_tile_asm.py; smaller working sets are re-read from the caches and run 3-6 % slower with nt)
-static bool rh_streams_beyond_cache(const rh_ring* r, unsigned rows) { return r->nt_streams && (size_t)rows * (size_t)r->N * 8 >= ((size_t)512 << 20); }
+static bool rh_streams_beyond_cache(const rh_ring* r, unsigned rows) { return rh_nt_policy(r->nt_streams, (size_t)rows * (size_t)r->N * 8, (size_t)512 << 20); }
 
 // rescale: column stages of limbs 0..Lrows-1 fed by the re-expansion of the coefficient-domain last limb `tmp` (N >= 8192)
 int rh_std_ntt_expand_cols_launch(rh_ring* r, const u64* tmp, u64* buf, int npoly, int Lrows, const void* table_dev, int mode, u64 qL) {
@@ -844,7 +854,7 @@ static int ci_ntt_launch(rh_ring* r, const u64* in, u64* out, int npoly, int Lro
     if (chunk > 0 && npoly > chunk && r->inv_scale) {
       const int nspans = (npoly + chunk - 1) / chunk;
       const size_t stride = (size_t)Lrows * r->N;
-      const bool ntp = r->nt_streams;
+      const bool ntp = r->nt_streams != 0;
       auto span = [&](int j, int* n) { const int p0 = j * chunk; *n = (j < 0 || j >= nspans) ? 0 : (npoly - p0 < chunk ? npoly - p0 : chunk); return (size_t)(j < 0 ? 0 : p0) * stride; };
       for (int j = 0; j <= nspans; ++j) {
         int p1, p2;
@@ -1084,7 +1094,7 @@ extern "C" int rh_ring_polymul(rh_ring* r, uint64_t* a, uint64_t* b, uint64_t* o
     (void)hipGetLastError();
     const int nspans = (npoly + chunk - 1) / chunk;
     const size_t stride = (size_t)Lrows * r->N;
-    const bool nt = r->nt_streams;                         // a pipelined batch is always far beyond the Infinity Cache (three blocks of >= 2048 rows)
+    const bool nt = r->nt_streams != 0;                    // a pipelined batch is always far beyond the Infinity Cache (three blocks of >= 2048 rows)
     auto span = [&](int j, int* n) { const int p0 = j * chunk; *n = (j < 0 || j >= nspans) ? 0 : (npoly - p0 < chunk ? npoly - p0 : chunk); return (size_t)(j < 0 ? 0 : p0) * stride; };
     for (int j = 0; j < nspans + 2; ++j) {
       int p1, p2, p3;
@@ -1162,7 +1172,10 @@ extern "C" int rh_ring_set_tuning(rh_ring* r, const char* key, long value) {
   if (!strcmp(key, "ks_small_rows")) { if (value < 0) return rh_fail(RH_ERR_ARG, "ks_small_rows must be >= 0"); r->ks_small_rows = (int)value; return RH_OK; }
   if (!strcmp(key, "pair_submul")) { r->pair_submul = value != 0; return RH_OK; }
   if (!strcmp(key, "one_pass")) { r->one_pass = value != 0; return RH_OK; }
-  if (!strcmp(key, "nt_streams")) { r->nt_streams = value != 0; if (r->kind == RH_RING_3N) rh_ring3n_set_nt_streams(r, value != 0); return RH_OK; }     // 0: default cache policy everywhere (A/B runs: bench.py --tune nt_streams=0)
+  if (!strcmp(key, "nt_streams")) {     // 0: default cache policy everywhere (A/B runs: bench.py --tune nt_streams=0), 1: by working set, 2: non-temporal at every size
+    if (value < 0 || value > 2) return rh_fail(RH_ERR_ARG, "nt_streams must be 0, 1 or 2 (got %ld)", value);
+    r->nt_streams = (int)value; if (r->kind == RH_RING_3N) rh_ring3n_set_nt_streams(r, (int)value); return RH_OK;
+  }
   return rh_fail(RH_ERR_ARG, "set_tuning: unknown key %s", key);
 }
 
@@ -1413,7 +1426,7 @@ int rh_vec_launch(rh_ring* r, int opcode, const u64* p1, const u64* p2, u64* p3,
   if (chunks > 64) chunks = 64;
   const unsigned npairs = n >> 1;
   const RowStrides rs{rows1 ? rows1 : Lrows, rows2 ? rows2 : Lrows, rows3 ? rows3 : Lrows, half == 2 ? npairs / 2 : 0u, half == 1 ? npairs / 2 : npairs,
-                      (r->nt_streams && (size_t)rows * (size_t)r->N * 8 >= ((size_t)512 << 20)) ? 1 : 0};
+                      rh_nt_policy(r->nt_streams, (size_t)rows * (size_t)r->N * 8, (size_t)512 << 20) ? 1 : 0};
   hipLaunchKernelGGL(table[opcode], dim3(rows, chunks), dim3(256), 0, rh_stream(r), p1, p2, p3, n, a, b, r->d_consts + limb0, Lrows, rs);
   return check_launch("vec_op");
 }

@@ -12,6 +12,10 @@
 
 int rh_fail(int code, const char* fmt, ...);
 
+// The one cache-policy decision of every launch site (tuning nt_streams: 0 never, 1 by working set, 2 always): non-temporal data streams
+// once the bytes a launch moves reach the site's threshold.
+inline bool rh_nt_policy(int nt_streams, size_t bytes, size_t threshold) { return nt_streams == 2 || (nt_streams == 1 && bytes >= threshold); }
+
 struct rh_ring3n_state;   // ntt3n.hip
 struct CiFold { tw2 f, b; };   // conjugate-invariant fold twiddles roots_fwd[1], roots_bwd[1] (Shoup pairs)
 
@@ -62,7 +66,8 @@ struct rh_ring {
   bool pair_submul = true;        // ModDown of a ciphertext: both components' transform + subtract-multiply in ONE launch (false: one launch per component; A/B runs)
   bool one_pass = true;           // N = 2^13 / 2^14: whole limb row in one workgroup's LDS (ntt_fwd_onepass_asm / ntt_inv_onepass_asm); false: the two-pass launches
   bool one_pass_ready = false;    // ... their dynamic-LDS limit has been raised on this ring's device
-  bool nt_streams = true;         // non-temporal data streams for launches beyond the Infinity Cache (the generated _NT bodies); false: default policy everywhere
+  int nt_streams = 1;             // cache policy of the data streams: 1 non-temporal (the generated _NT bodies, the nt template arms) for launches beyond the
+                                  // Infinity Cache, by working set; 0 default policy everywhere; 2 non-temporal at every size (tests run every variant at small shapes)
   int chunk_polys = -1;           // -1 = auto (128-poly spans for batches >= 256), 0 = whole batch in two launches, >0 = polys per span
 };
 
@@ -112,11 +117,11 @@ int rh_upload_consts(rh_ring* r, const std::vector<LimbConsts>& hc);
 void rh_rescale_teardown(rh_ring* r);
 int rh_rescale_reserve(rh_ring* r, int npoly);
 int rh_ring3n_reserve(rh_ring* r, int npoly);
-void rh_3n_launch_layer(bool inverse, int S1, unsigned nblocks, hipStream_t st, const u64* in, u64* out, const N3Layer& a, bool nt_streams);
+void rh_3n_launch_layer(bool inverse, int S1, unsigned nblocks, hipStream_t st, const u64* in, u64* out, const N3Layer& a, int nt_streams);
 // 3N-cyclotomic transform (ntt3n.hip)
 int rh_ring3n_setup(rh_ring* r, std::vector<LimbConsts>& hc);
 void rh_ring3n_teardown(rh_ring* r);
-void rh_ring3n_set_nt_streams(rh_ring* r, bool on);
+void rh_ring3n_set_nt_streams(rh_ring* r, int policy);
 int rh_ring3n_ntt_launch(rh_ring* r, const u64* in, u64* out, int npoly, int Lrows, int limb0, bool inverse, bool block_order = false);
 int rh_ring3n_reorder_launch(rh_ring* r, const u64* in, u64* out, int npoly, int Lrows, bool to_reference);
 

@@ -666,6 +666,6 @@ int rh_ring3n_ntt_launch(rh_ring* r, const u64* in, u64* out, int npoly, int Lro
 }
 
 // tuning keys that must reach the radix-2 sub-ring as well (its tile stages choose their cache policy by size like any standard ring)
-void rh_ring3n_set_nt_streams(rh_ring* r, bool on) { if (r->s3n && r->s3n->sub) r->s3n->sub->nt_streams = on; }
+void rh_ring3n_set_nt_streams(rh_ring* r, int policy) { if (r->s3n && r->s3n->sub) r->s3n->sub->nt_streams = policy; }
 
 int rh_ring3n_reserve(rh_ring* r, int npoly) { return ensure_tmp(r->s3n, (size_t)npoly * r->L * r->N); }

@@ -52,6 +52,12 @@ def test_empty_batch_and_bad_arguments(rh):
     assert lib.rh_ring_vec_op(ring._h, 99, p.ptr, p.ptr, p.ptr, 1, 1, None, None) == -1
     assert lib.rh_ring_vec_op(ring._h, rh.OPS["ADD"], p.ptr, None, p.ptr, 1, 1, None, None) == -1     # missing operand
     assert lib.rh_ring_set_tuning(ring._h, b"no_such_knob", 1) == -1
+    for v in (0, 2, 1):                                                     # cache policy: default everywhere, non-temporal everywhere, by working set
+        assert lib.rh_ring_set_tuning(ring._h, b"nt_streams", v) == 0
+    for v in (-1, 3):
+        assert lib.rh_ring_set_tuning(ring._h, b"nt_streams", v) == -1 and b"nt_streams" in lib.rh_last_error()
+        with pytest.raises(rh.RingHipError, match="nt_streams"):
+            ring.set_tuning("nt_streams", v)
     ring.close()
 
 
