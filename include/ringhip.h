@@ -424,6 +424,37 @@ int rh_bgv_mul_plain(rh_ring* r, int level, const uint64_t* ct0_dev, const uint6
 int rh_bgv_axpby(rh_ring* r, int level, const uint64_t* a_dev, const uint64_t* b_dev, uint64_t* out_dev, int npoly, const uint64_t* r0,
                  const uint64_t* r1, int sub);
 
+/* ---- CKKS: the evaluator's element-wise sequences, one launch each (schemes/ckks/evaluator.go) -----------------------------------------
+ * Entry points on a STANDARD or conjugate-invariant power-of-two ring handle (RH_ERR_ARG for a 3N ring, a null handle, a level out of
+ * range, a scalar that is not below its modulus).  Blocks are device-resident, dense (npoly, level+1, N), NTT domain, residues in [0, q_i)
+ * in and out; per-limb scalars are host arrays of level+1 words.  Asynchronous on the ring's stream.  Every thread reads all its operands
+ * before it writes: any output may be any input.  x' = MForm(x) below.
+ *   rh_ckks_tensor          the ct x ct branch of mulRelin (:821-835) and of mulRelinThenAdd (:1135-1162) in ONE launch.
+ *                           accumulate 0: c0 = MRed(a0', b0), c2 = MRed(a1', b1), c1 = CRed(MRed(a0', b1) + MRed(a1', b0)) -- the bits of
+ *                           rh_ring_tensor_degree1; square != 0 (accumulate 0 only; b NULL or b == a): c1 = CRed(2 MRed(a0', a1)) (:825-828);
+ *                           1: c0 = CRed(c0 + MRed(a0', b0)), c1 = CRed(CRed(c1 + MRed(a0', b1)) + MRed(a1', b0)), c2 = CRed(c2 + MRed(a1', b1))
+ *                           (:1138-1140, :1161); 2: c0, c1 as for 1, c2 WRITTEN (the relin form :1150: c2 is scratch for the gadget product).
+ *   rh_ckks_mul_plain       the plaintext branches (:856-878, :1165-1175): out_j (+)= MRed(pt', ct_j) for the 1, 2 or 3 components given
+ *                           (trailing NULLs: fewer components); accumulate 0 / 1.
+ *   rh_ckks_scalar          evaluateWithScalar (:433-447) on every component given: Ring.AddDoubleRNSScalar / Sub... / Mul... / Mul...ThenAdd
+ *                           (ring/operations.go:167-184, :250-266) with the RNS scalar s0 on coefficients [0, N/2) and s1 on [N/2, N), the
+ *                           scalars as those calls take them (not in Montgomery form).
+ *   rh_ckks_scale_then_add  the scale-matching Add / Sub of evaluateInPlace (:246-431): the operand with the smaller scale (b if scaled_is_b,
+ *                           else a) times ratio[i] = ratioInt mod q_i as Mul(ct, ratioInt, tmp) does it (ratio NULL: equal scales, nothing is
+ *                           scaled), Add (sub != 0: Sub) on the components both operands have, the components only one has copied (:422-430)
+ *                           and, for b's under Sub, negated with ring.Neg (:173-177: q_i - x, so 0 gives q_i as in the reference).  out has
+ *                           the components of the larger operand. */
+enum rh_ckks_scalar_op { RH_CKKS_ADD_SCALAR = 0, RH_CKKS_SUB_SCALAR = 1, RH_CKKS_MUL_SCALAR = 2, RH_CKKS_MUL_SCALAR_THEN_ADD = 3 };
+int rh_ckks_tensor(rh_ring* r, int level, const uint64_t* a0_dev, const uint64_t* a1_dev, const uint64_t* b0_dev, const uint64_t* b1_dev,
+                   uint64_t* c0_dev, uint64_t* c1_dev, uint64_t* c2_dev, int npoly, int accumulate, int square);
+int rh_ckks_mul_plain(rh_ring* r, int level, const uint64_t* ct0_dev, const uint64_t* ct1_dev, const uint64_t* ct2_dev, const uint64_t* pt_dev,
+                      uint64_t* out0_dev, uint64_t* out1_dev, uint64_t* out2_dev, int npoly, int accumulate);
+int rh_ckks_scalar(rh_ring* r, int level, int op, const uint64_t* in0_dev, const uint64_t* in1_dev, const uint64_t* in2_dev,
+                   uint64_t* out0_dev, uint64_t* out1_dev, uint64_t* out2_dev, int npoly, const uint64_t* s0, const uint64_t* s1);
+int rh_ckks_scale_then_add(rh_ring* r, int level, const uint64_t* a0_dev, const uint64_t* a1_dev, const uint64_t* a2_dev, const uint64_t* b0_dev,
+                           const uint64_t* b1_dev, const uint64_t* b2_dev, uint64_t* out0_dev, uint64_t* out1_dev, uint64_t* out2_dev, int npoly,
+                           const uint64_t* ratio, int sub, int scaled_is_b);
+
 /* ---- limb-sharded hybrid key switch (BASELINE config 5): one process per GPU owns a subset of the limbs
  * of Q and P and the matching slice of the evaluation key.  Same arithmetic as rh_bext_gadget_product, cut where
  * reconstructRNS (ring/basis_extension.go:550-594) needs limbs of other owners; the exchange (an all-gather of the

@@ -1,24 +1,146 @@
-"""Host-side mirror of the CKKS evaluator methods that traverse the ring hot path: the ct x ct multiply
-with relinearisation and the rescale that follows it, on device-resident batches in the NTT domain.  Call sequences
-only -- the arithmetic is the HIP library's; scales, encoders and key generation stay with the reference.
+"""Host-side mirror of ckks.Evaluator, schemes/ckks/evaluator.go, on device-resident batches in the NTT domain: call sequences and the scale
+bookkeeping only -- the arithmetic is the HIP library's (csrc/ckks.hip and the ring entry points); encoders and key generation stay with
+the reference, so slice operands ([]complex128 / []float64 ...) are refused by name.
 
-  mulRelin   schemes/ckks/evaluator.go:786-881      Rescale   schemes/ckks/evaluator.go:500-535
+  Add(New) / Sub(New)   :59-244      evaluateInPlace   :246-431     evaluateWithScalar  :433-447     ScaleUp / SetScale  :449-478
+  DropLevel(New)        :480-492     Rescale           :500-535     RescaleTo           :543-602     Mul(New)            :604-728
+  MulRelin(New)         :730-784     mulRelin          :786-881     MulThenAdd          :918-1046    MulRelinThenAdd     :1065-1093
+  mulRelinThenAdd       :1095-1178   Rotate / Conjugate / RotateHoisted (New)  :1195-1255            bigComplexToRNSScalar  scaling.go:10-43
 
-A batch of B ciphertexts is one Ciphertext whose polys have npoly = B.  All operands of one call sit at the same level
-(every poly block has level+1 limbs): the device layout is (poly, limb, N) contiguous, so a poly cannot be read at a
-lower level than it was allocated for -- drop limbs first (DropLevel = re-upload / view of fewer limbs)."""
-from .ringhip import DevicePoly, RingHipError
-from .schemes import Ciphertext
+A batch of B ciphertexts is one Ciphertext whose polys have npoly = B.  All operands of one call sit at the same level (every poly block has
+level+1 limbs): the device layout is (poly, limb, N) contiguous, so a poly cannot be read at a lower level than it was allocated for --
+DropLevel copies the leading limbs into blocks of the lower level.  A degree-0 Ciphertext plays the role of a plaintext.  Scales are `Scale`
+objects in the attribute Scale; MulRelin and Rescale still serve ciphertexts that carry none, every other method raises on one."""
+from fractions import Fraction
+
+import numpy as np
+
+from .ringhip import ConjugateInvariant, DevicePoly, RingHipError, _check, _p, _u64, lib
+from .schemes import Ciphertext, MatrixCKKSEvaluator
 from . import rlwe
+
+ScalePrecision = 128            # core/rlwe/scale.go:12-15
+GaloisGen = 5                   # ring/ring.go
+_round = MatrixCKKSEvaluator._round_to_prec
+
+ADD_SCALAR, SUB_SCALAR, MUL_SCALAR, MUL_SCALAR_THEN_ADD = range(4)      # enum rh_ckks_scalar_op
+
+
+class Scale:
+    """rlwe.Scale without a modulus (core/rlwe/scale.go): a big.Float of ScalePrecision = 128 bits.  The value is an exact rational that is
+    rounded to 128 significant bits, half to even, when it is set and after every Mul / Div -- Go's new(big.Float).Mul / Quo take the larger
+    operand precision (128 on both sides here) and round to nearest even."""
+    __slots__ = ("Value",)
+
+    def __init__(self, s):
+        if isinstance(s, Scale):
+            s = s.Value
+        v = Fraction(s)
+        if v < 0:
+            raise RingHipError("scale cannot be negative, but is %s" % (s,))
+        self.Value = _round(v, ScalePrecision)
+
+    def Mul(self, s1):
+        return Scale(self.Value * Scale(s1).Value)
+
+    def Div(self, s1):
+        return Scale(self.Value / Scale(s1).Value)
+
+    def Cmp(self, s1):
+        a, b = self.Value, Scale(s1).Value
+        return (a > b) - (a < b)
+
+    def Max(self, s1):
+        s1 = Scale(s1)
+        return s1 if self.Cmp(s1) < 0 else self
+
+    def Min(self, s1):
+        s1 = Scale(s1)
+        return s1 if self.Cmp(s1) > 0 else self
+
+    def Equal(self, s1):
+        return self.Cmp(s1) == 0
+
+    def Float64(self):
+        return float(self.Value)          # int / int true division rounds to nearest even, as big.Float.Float64 does
+
+    def Uint64(self):
+        return min(int(self.Value), (1 << 64) - 1)
+
+    def BigInt(self):
+        return int(_round(self.Value + Fraction(1, 2), ScalePrecision))
+
+    def __eq__(self, other):
+        return isinstance(other, (Scale, int, float, Fraction)) and self.Cmp(other) == 0
+
+    def __hash__(self):
+        return hash(self.Value)
+
+    def __repr__(self):
+        return "Scale(%s)" % (self.Value,)
+
+
+def GaloisElement(N, k, NthRoot=None):
+    """rlwe.Parameters.GaloisElement (core/rlwe/params.go:671-675): GaloisGen^k mod NthRoot (2N; 4N on a conjugate-invariant ring); a negative k
+    is taken modulo NthRoot, a multiple of the order of GaloisGen"""
+    NthRoot = 2 * int(N) if NthRoot is None else int(NthRoot)
+    return pow(GaloisGen, int(k) % NthRoot, NthRoot)
+
+
+def GaloisElementOrderTwoOrthogonalSubgroup(N):
+    """:683-689: X -> X^-1, the conjugation, 2N - 1"""
+    return 2 * int(N) - 1
+
+
+def _is_slice(op):
+    return isinstance(op, (list, tuple, np.ndarray))
+
+
+def _is_scalar(op):
+    return isinstance(op, (int, float, complex, Fraction, np.integer, np.floating, np.complexfloating)) and not isinstance(op, bool)
+
+
+def to_complex(value, prec):
+    """bignum.ToComplex (utils/bignum/complex.go:22-55): both parts as big.Floats of `prec` bits -- ints and big.Floats (Fractions here) are
+    ROUNDED to prec bits like floats.  Returns two Fractions."""
+    if isinstance(value, (complex, np.complexfloating)):
+        re_, im_ = Fraction(float(value.real)), Fraction(float(value.imag))
+    elif isinstance(value, (float, np.floating)):
+        re_, im_ = Fraction(float(value)), Fraction(0)
+    else:
+        re_, im_ = Fraction(int(value) if isinstance(value, (int, np.integer)) else value), Fraction(0)
+    return _round(re_, prec), _round(im_, prec)
+
+
+def scaled_int(x, scale, prec):
+    """one part of bigComplexToRNSScalar (schemes/ckks/scaling.go:16-27): new(big.Float).Mul(x, scale) rounded to the larger operand precision,
+    plus / minus 0.5 by the sign of x rounded at that same precision, .Int truncating toward zero"""
+    prec = max(int(prec), ScalePrecision)
+    r = _round(x * scale, prec)
+    if x > 0:
+        r = _round(r + Fraction(1, 2), prec)
+    elif x < 0:
+        r = _round(r - Fraction(1, 2), prec)
+    return int(r)                         # Fraction -> int truncates toward zero
 
 
 class Evaluator:
-    def __init__(self, ringQ, ringP=None, rlk=None, levels_consumed_per_rescaling=1):
+    """ckks.Evaluator.  ringP / rlk / galois_keys: the key-switch ring, the relinearisation key and the Galois keys (a dict Galois element ->
+    rlwe.GadgetCiphertext).  fused: True the kernels of csrc/ckks.hip wherever there is one, False the reference's own sequence of Ring calls --
+    the same bits; None (default) what FUSED_DEFAULT says per kernel, the measured choice.  encoding_precision:
+    Parameters.EncodingPrecision(), max(53, floor(log2 DefaultScale)) (schemes/ckks/params.go:187-195)."""
+
+    FUSED_DEFAULT = {"tensor": True, "mul_plain": True, "scalar": False, "scale_then_add": True}   # profiles/ckks_ops.json: the scalar kernel is not faster than the four half-row launches
+
+    def __init__(self, ringQ, ringP=None, rlk=None, levels_consumed_per_rescaling=1, galois_keys=None, fused=None, encoding_precision=53):
         self.ringQ, self.ringP, self.rlk = ringQ, ringP, rlk
         self.nb_rescales = int(levels_consumed_per_rescaling)
-        self.fused_tensor = True          # regular ct x ct case: rh_ring_tensor_degree1 instead of six element-wise launches (same bits)
-        self.ks = rlwe.Evaluator(ringQ, ringP) if ringP is not None else None
+        self.fused = dict(self.FUSED_DEFAULT) if fused is None else {k: bool(fused) for k in self.FUSED_DEFAULT}
+        self.fused_tensor = fused is None or bool(fused)   # regular ct x ct case: rh_ring_tensor_degree1 instead of six element-wise launches (same bits)
+        self.encoding_precision = int(encoding_precision)
+        self.ks = rlwe.Evaluator(ringQ, ringP, galois_keys=galois_keys) if ringP is not None else None
         self._pool = {}
+        self._roots1 = None
 
     def close(self):
         self._pool.clear()
@@ -38,10 +160,333 @@ class Evaluator:
             raise RingHipError("operands must sit at the same level, got %s" % sorted(lv))
         return lv.pop()
 
+    # ---- operands, scales, host scalars ---------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _scale(ct, who):
+        s = getattr(ct, "Scale", None)
+        if s is None:
+            raise RingHipError("cannot %s: a ciphertext carries no Scale" % who)
+        return s if isinstance(s, Scale) else Scale(s)
+
+    def _operands(self, who, *cts):
+        for ct in cts:
+            if not ct.IsNTT:
+                raise RingHipError("cannot %s: operands must be in the NTT domain" % who)
+        lv = {ct.Level() for ct in cts}
+        if len(lv) != 1:
+            raise RingHipError("cannot %s: operands must sit at the same level, got %s" % (who, sorted(lv)))
+        level = lv.pop()
+        for ct in cts:
+            rlwe.Evaluator._rows(level, *ct.Value)
+        if len({p.npoly for ct in cts for p in ct.Value}) != 1:
+            raise RingHipError("cannot %s: every poly block of a call holds the same number of polys" % who)
+        return level
+
+    def _refuse(self, op1, who):
+        if _is_slice(op1):
+            raise RingHipError("cannot %s: op1 of type %s (a slice, []complex128 / []float64 ...) needs the CKKS encoder, which the device path does not build"
+                               % (who, type(op1).__name__))
+        if not (_is_scalar(op1) or isinstance(op1, Ciphertext)):
+            raise RingHipError("cannot %s: invalid op1.(type): must be a Ciphertext, int, float, complex or Fraction, but is %s" % (who, type(op1).__name__))
+
+    def _qs(self, level):
+        return [int(q) for q in self.ringQ.moduli[:level + 1]]
+
+    def _rescale_scale(self, level):
+        """the scale a non-integer constant is given: q_level ... over levels_consumed_per_rescaling moduli (:665-671, :962-966)"""
+        qs = self._qs(level)
+        if level - (self.nb_rescales - 1) < 0:
+            raise RingHipError("level %d is too low for a constant scaled by %d moduli" % (level, self.nb_rescales))
+        scale = Scale(qs[level])
+        for i in range(1, self.nb_rescales):
+            scale = scale.Mul(Scale(qs[level - i]))
+        return scale
+
+    def _rns_scalar(self, level, scale, cmplx):
+        """bigComplexToRNSScalar (scaling.go:10-43) followed by the scalar half of evaluateWithScalar (:439-442): the RNS scalars for
+        coefficients [0, N/2) and [N/2, N).  cmplx: the two Fractions of to_complex."""
+        qs = self._qs(level)
+        real = scaled_int(cmplx[0], Scale(scale).Value, self.encoding_precision)
+        imag = scaled_int(cmplx[1], Scale(scale).Value, self.encoding_precision)
+        s0, s1 = [], []
+        if imag != 0 and self._roots1 is None:
+            self._roots1 = [int(w) for w in self.ringQ.constants()["roots_fwd"][:, 1]]          # SubRing.RootsForward[1], Montgomery form
+        for i, q in enumerate(qs):
+            re_, im_ = real % q, imag % q                                                        # NewRNSScalarFromBigint: the non-negative residue
+            if im_:
+                im_ = im_ * self._roots1[i] * pow(1 << 64, -1, q) % q                            # MRed(RNSImag[i], RootsForward[1]) (:440)
+            s0.append((re_ + im_) % q)                                                           # (:441)
+            s1.append((re_ + q - im_) % q)
+        return s0, s1
+
+    def _use(self, kind):
+        return self.fused[kind]
+
+    @staticmethod
+    def _ptrs(polys, n=3):
+        return [p.ptr for p in polys] + [None] * (n - len(polys))
+
+    def _scalar_op(self, level, op, ins, outs, s0, s1):
+        """evaluateWithScalar's loop (:444-446) on the components given"""
+        rq = self.ringQ.AtLevel(level)
+        if self._use("scalar"):
+            a, b = _u64(s0), _u64(s1)
+            _check(lib().rh_ckks_scalar(self.ringQ._h, level, op, *self._ptrs(ins), *self._ptrs(outs), ins[0].npoly, _p(a), _p(b)))
+            return
+        f = (rq.AddDoubleRNSScalar, rq.SubDoubleRNSScalar, rq.MulDoubleRNSScalar, rq.MulDoubleRNSScalarThenAdd)[op]
+        for x, y in zip(ins, outs):
+            f(x, s0, s1, y)
+
+    def _new(self, degree, like):
+        level, npoly = like.Level(), like.Value[0].npoly
+        rq = self.ringQ.AtLevel(level)
+        return Ciphertext([rq.NewPoly(npoly) for _ in range(degree + 1)], is_ntt=True)
+
+    # ---- Add / Sub :59-244, evaluateInPlace :246-431 -------------------------------------------------------------------------------------
+    def _add_sub(self, op0, op1, opOut, sub):
+        who = "Sub" if sub else "Add"
+        self._refuse(op1, who)
+        if _is_scalar(op1):                                                        # (:82-101, :178-197)
+            level = self._operands(who, op0, opOut)
+            scale0 = self._scale(op0, who)
+            if opOut.Degree() != op0.Degree():
+                raise RingHipError("cannot %s: opOut must have degree %d" % (who, op0.Degree()))
+            s0, s1 = self._rns_scalar(level, scale0, to_complex(op1, self.encoding_precision))
+            self._scalar_op(level, SUB_SCALAR if sub else ADD_SCALAR, op0.Value[:1], opOut.Value[:1], s0, s1)
+            if op0 is not opOut:
+                rq = self.ringQ.AtLevel(level)
+                for i in range(1, op0.Degree() + 1):
+                    rq.CopyLvl(op0.Value[i], opOut.Value[i])
+            opOut.Scale, opOut.IsNTT = scale0, True
+            return
+        level = self._operands(who, op0, op1, opOut)
+        c0Scale, c1Scale = self._scale(op0, who), self._scale(op1, who)
+        d0, d1 = op0.Degree(), op1.Degree()
+        lo, hi = min(d0, d1), max(d0, d1)
+        if opOut.Degree() != hi:
+            raise RingHipError("cannot %s: opOut must have degree %d" % (who, hi))
+        rq = self.ringQ.AtLevel(level)
+        cmp = c0Scale.Cmp(c1Scale)
+        ratio = None
+        if cmp:
+            ratioInt = int((c0Scale.Div(c1Scale) if cmp == 1 else c1Scale.Div(c0Scale)).Value)      # ratioFlo.Int(nil)
+            # Mul(ct, ratioInt, tmp) (:282 ...): a *big.Int through bignum.ToComplex, a Gaussian integer, scale 1
+            ratio = self._rns_scalar(level, Scale(1), to_complex(ratioInt, self.encoding_precision))
+        if self._use("scale_then_add"):
+            a, b, o = self._ptrs(op0.Value), self._ptrs(op1.Value), self._ptrs(opOut.Value)
+            k = _u64(ratio[0]) if ratio is not None else None
+            _check(lib().rh_ckks_scale_then_add(self.ringQ._h, level, *a, *b, *o, op0.Value[0].npoly, _p(k), 1 if sub else 0, 1 if cmp == 1 else 0))
+        else:
+            npoly = op0.Value[0].npoly
+            tmp0, tmp1 = op0, op1
+            scaled = op1 if cmp == 1 else op0 if cmp == -1 else None
+            if scaled is not None:
+                if scaled is opOut:                                                # scaled in place (:295, :319)
+                    dst = opOut
+                else:                                                              # into eval.BuffCt (:273, :336, :366, :390)
+                    dst = Ciphertext([self._buffer("BuffCt%d" % i, rq, npoly, level + 1) for i in range(scaled.Degree() + 1)], is_ntt=True)
+                for x, y in zip(scaled.Value, dst.Value):
+                    rq.MulDoubleRNSScalar(x, ratio[0], ratio[1], y)
+                if cmp == 1:
+                    tmp1 = dst
+                else:
+                    tmp0 = dst
+            f = rq.Sub if sub else rq.Add
+            for i in range(lo + 1):
+                f(tmp0.Value[i], tmp1.Value[i], opOut.Value[i])                    # (:413-415)
+            if d0 > d1 and tmp0 is not opOut:
+                for i in range(lo + 1, hi + 1):
+                    rq.CopyLvl(tmp0.Value[i], opOut.Value[i])                      # (:422-425)
+            elif d1 > d0 and tmp1 is not opOut:
+                for i in range(lo + 1, hi + 1):
+                    rq.CopyLvl(tmp1.Value[i], opOut.Value[i])                      # (:426-430)
+            if sub and d0 < d1:
+                for i in range(d0 + 1, d1 + 1):
+                    rq.Neg(opOut.Value[i], opOut.Value[i])                         # (:173-177)
+        opOut.Scale, opOut.IsNTT = c0Scale.Max(c1Scale), True                      # (:417)
+
+    def Add(self, op0, op1, opOut):
+        """:66-135: op1 a Ciphertext (degrees up to 2; the operand with the smaller scale is first multiplied by the integer part of the
+        ratio of the scales) or a scalar (added to component 0 at op0's scale)"""
+        self._add_sub(op0, op1, opOut, False)
+
+    def Sub(self, op0, op1, opOut):
+        """:156-232"""
+        self._add_sub(op0, op1, opOut, True)
+
+    def _new_binary(self, op0, op1):
+        return self._new(max(op0.Degree(), op1.Degree()) if isinstance(op1, Ciphertext) else op0.Degree(), op0)
+
+    def AddNew(self, op0, op1):
+        """:144-147 (the reference's Resize lets opOut grow to the larger degree: it is allocated with it here)"""
+        self._refuse(op1, "Add")
+        opOut = self._new_binary(op0, op1)
+        self.Add(op0, op1, opOut)
+        return opOut
+
+    def SubNew(self, op0, op1):
+        """:241-244"""
+        self._refuse(op1, "Sub")
+        opOut = self._new_binary(op0, op1)
+        self.Sub(op0, op1, opOut)
+        return opOut
+
+    # ---- ScaleUp, SetScale, DropLevel :449-492 --------------------------------------------------------------------------------------------
+    def ScaleUp(self, op0, scale, opOut):
+        """:456-465: op0 times scale.Uint64(), the scale multiplied by `scale`"""
+        scale = Scale(scale)
+        scale0 = self._scale(op0, "ScaleUp")
+        self._mul_scalar(op0, scale.Uint64(), opOut, "ScaleUp")
+        opOut.Scale = scale0.Mul(scale)
+
+    def ScaleUpNew(self, op0, scale):
+        opOut = self._new(op0.Degree(), op0)
+        self.ScaleUp(op0, scale, opOut)
+        return opOut
+
+    def SetScale(self, ct, scale):
+        """:468-478: ct times scale / ct.Scale (a *big.Float: not an integer, so it is scaled by the moduli one rescaling consumes), RescaleTo
+        the target, and the scale set to it"""
+        scale = Scale(scale)
+        ratioFlo = scale.Div(self._scale(ct, "SetScale")).Value
+        self._mul_scalar(ct, ratioFlo, ct, "SetScale")
+        self.RescaleTo(ct, scale, ct)
+        ct.Scale = scale
+
+    def _resize(self, ct, level):
+        """rlwe.Element.Resize to a lower level: device blocks are dense, so the leading limbs are copied into blocks of that level"""
+        rq = self.ringQ.AtLevel(level)
+        for i, p in enumerate(ct.Value):
+            if p.limbs != level + 1:
+                q = rq.NewPoly(p.npoly)
+                rq.CopyLvl(p, q)
+                ct.Value[i] = q
+
+    def DropLevel(self, op0, levels):
+        """:490-492: no rescaling"""
+        if not 0 <= int(levels) <= op0.Level():
+            raise RingHipError("cannot DropLevel: %d levels from level %d" % (levels, op0.Level()))
+        self._resize(op0, op0.Level() - int(levels))
+
+    def DropLevelNew(self, op0, levels):
+        """:482-486"""
+        opOut = Ciphertext(list(op0.Value), is_ntt=op0.IsNTT)
+        if hasattr(op0, "Scale"):
+            opOut.Scale = op0.Scale
+        if int(levels) == 0:
+            rq = self.ringQ.AtLevel(op0.Level())
+            opOut.Value = [rq.NewPoly(p.npoly) for p in op0.Value]
+            for p, q in zip(op0.Value, opOut.Value):
+                rq.CopyLvl(p, q)
+            return opOut
+        self.DropLevel(opOut, levels)
+        return opOut
+
+    # ---- Rescale :500-535, RescaleTo :543-602 ---------------------------------------------------------------------------------------------
+    def Rescale(self, op0, opOut):
+        """Rescale (:500-535): DivRoundByLastModulusManyNTT(nbRescales) on every component.  opOut's polys keep op0's limb count; limbs
+        0 .. level-nbRescales hold the result (ring/scaling.go:130-156).  With a Scale on op0 the scale is divided by the consumed moduli."""
+        nb = self.nb_rescales
+        if op0.Level() <= nb - 1:
+            raise RingHipError("cannot Rescale: input Ciphertext level is too low")
+        if opOut.Degree() != op0.Degree():
+            raise RingHipError("Rescale: degrees differ")
+        rq = self.ringQ.AtLevel(op0.Level())
+        if getattr(op0, "Scale", None) is not None:
+            scale = self._scale(op0, "Rescale")
+            for i in range(nb):
+                scale = scale.Div(Scale(int(self.ringQ.moduli[op0.Level() - i])))          # (:522-524)
+            opOut.Scale = scale
+        for a, b in zip(op0.Value, opOut.Value):
+            rq.DivRoundByLastModulusManyNTT(nb, a, b)
+        opOut.IsNTT = op0.IsNTT
+
+    def RescaleTo(self, op0, minScale, opOut):
+        """:543-602: divides by the last moduli, one level each, as long as the scale stays at or above minScale / 2.  opOut's blocks are
+        replaced by blocks of the new level (the reference's Resize); with nothing to divide op0 is copied."""
+        minScale = Scale(minScale)
+        if minScale.Cmp(Scale(0)) != 1:
+            raise RingHipError("cannot RescaleTo: minScale is <0")
+        minScale = minScale.Div(Scale(2))
+        scale = self._scale(op0, "RescaleTo")
+        if scale.Cmp(Scale(0)) != 1:
+            raise RingHipError("cannot RescaleTo: ciphertext scale is <0")
+        level = op0.Level()
+        if level == 0:
+            raise RingHipError("cannot RescaleTo: input Ciphertext already at level 0")
+        if opOut.Degree() != op0.Degree() or not op0.IsNTT:
+            raise RingHipError("cannot RescaleTo: opOut must have op0's degree and op0 must be in the NTT domain")
+        rlwe.Evaluator._rows(level, *op0.Value)
+        newLevel, nbRescales = level, 0
+        while newLevel >= 0:                                                       # (:572-584)
+            s = scale.Div(Scale(int(self.ringQ.moduli[newLevel])))
+            if s.Cmp(minScale) == -1:
+                break
+            scale = s
+            nbRescales += 1
+            newLevel -= 1
+        if newLevel < 0:
+            raise RingHipError("cannot RescaleTo: the scale allows %d divisions, more than the %d levels above level 0" % (nbRescales, level))
+        rq = self.ringQ.AtLevel(level)
+        if nbRescales > 0:
+            outs = [self.ringQ.AtLevel(newLevel).NewPoly(p.npoly) for p in op0.Value]
+            for a, b in zip(op0.Value, outs):
+                rq.DivRoundByLastModulusManyNTT(nbRescales, a, b)                  # (:590-593)
+            opOut.Value = outs
+        elif op0 is not opOut:
+            for i, p in enumerate(op0.Value):                                      # opOut.Copy(op0) (:596-598)
+                if opOut.Value[i].limbs != level + 1 or opOut.Value[i].npoly != p.npoly:
+                    opOut.Value[i] = rq.NewPoly(p.npoly)
+                rq.CopyLvl(p, opOut.Value[i])
+        opOut.Scale, opOut.IsNTT = scale, True
+
+    # ---- Mul / MulRelin :604-881 ----------------------------------------------------------------------------------------------------------
+    def _mul_scalar(self, op0, op1, opOut, who):
+        """the scalar branch of Mul (:646-683): a Gaussian integer multiplies as it is; any other constant is scaled by the moduli one
+        rescaling consumes and the scale grows by that factor"""
+        level = self._operands(who, op0, opOut)
+        scale0 = self._scale(op0, who)
+        if opOut.Degree() != op0.Degree():
+            raise RingHipError("cannot %s: opOut must have degree %d" % (who, op0.Degree()))
+        cmplx = to_complex(op1, self.encoding_precision)
+        scale = Scale(1) if cmplx[0].denominator == 1 and cmplx[1].denominator == 1 else self._rescale_scale(level)
+        s0, s1 = self._rns_scalar(level, scale, cmplx)
+        self._scalar_op(level, MUL_SCALAR, op0.Value, opOut.Value, s0, s1)
+        opOut.Scale, opOut.IsNTT = scale0.Mul(scale), True                        # (:681)
+
+    def Mul(self, op0, op1, opOut):
+        """:630-728: without relinearisation; op1 a Ciphertext (opOut of degree op0.Degree() + op1.Degree()) or a scalar"""
+        self._refuse(op1, "Mul")
+        if _is_scalar(op1):
+            return self._mul_scalar(op0, op1, opOut, "Mul")
+        self._scale(op0, "Mul"), self._scale(op1, "Mul")
+        self.MulRelin(op0, op1, opOut, relin=False)
+
+    def MulNew(self, op0, op1):
+        """:613-616 (opOut allocated with the product's degree)"""
+        self._refuse(op1, "Mul")
+        opOut = self._new(op0.Degree() + op1.Degree() if isinstance(op1, Ciphertext) else op0.Degree(), op0)
+        self.Mul(op0, op1, opOut)
+        return opOut
+
+    def MulRelinNew(self, op0, op1):
+        """:741-750"""
+        self._refuse(op1, "MulRelin")
+        ct = isinstance(op1, Ciphertext)
+        opOut = self._new((1 if op0.Degree() == 1 and op1.Degree() == 1 else max(op0.Degree(), op1.Degree())) if ct else op0.Degree(), op0)
+        if ct:
+            self._scale(op0, "MulRelin"), self._scale(op1, "MulRelin")
+        self.MulRelin(op0, op1, opOut)
+        return opOut
+
     def MulRelin(self, op0, op1, opOut, relin=True):
         """mulRelin (:786-881).  Degree-1 x degree-1: tensoring (:821-834, squaring case :825-829 when op1 is op0), then
         with relin the gadget product of c2 with the relinearisation key and two Adds (:836-852); opOut has degree 1 with
-        relin, 2 without.  Degree-0 x degree-1 (plaintext x ciphertext): MForm + MulCoeffsMontgomery per component (:855-878)."""
+        relin, 2 without.  Degree-0 x degree-1 (plaintext x ciphertext): MForm + MulCoeffsMontgomery per component (:855-878).
+        A scalar op1 goes to Mul (:778-781).  Operands that carry scales give opOut their product (:790)."""
+        if not isinstance(op1, Ciphertext):
+            self._refuse(op1, "MulRelin")
+            return self._mul_scalar(op0, op1, opOut, "MulRelin")
         if not (op0.IsNTT and op1.IsNTT):
             raise RingHipError("MulRelin: operands must be in the NTT domain")
         level = self._same_level(op0, op1, opOut)
@@ -57,50 +502,201 @@ class Evaluator:
             need = 1 if relin else 2
             if opOut.Degree() != need:
                 raise RingHipError("MulRelin: opOut must have degree %d" % need)
+            if relin and (self.rlk is None or self.ks is None):
+                raise RingHipError("cannot MulRelin: Relinearize: relinearization key is missing")
             c00, c01 = new(), new()
             c0, c1 = opOut.Value[0], opOut.Value[1]
             c2 = new() if relin else opOut.Value[2]
             tmp0, tmp1 = (op1, op0) if op1 is opOut else (op0, op1)        # avoid overwriting when the second input is the output
-            if op0 is op1 or not self.fused_tensor:
-                rq.MForm(tmp0.Value[0], c00)
-                rq.MForm(tmp0.Value[1], c01)
-            if op0 is op1:                                                  # squaring
-                rq.MulCoeffsMontgomery(c00, tmp1.Value[0], c0)
-                rq.MulCoeffsMontgomery(c01, tmp1.Value[1], c2)
-                rq.MulCoeffsMontgomery(c00, tmp1.Value[1], c1)
-                rq.Add(c1, c1, c1)
-            elif self.fused_tensor:                                         # the same six ring calls as one kernel
+            if self._use("tensor") and (op0 is op1 or op1 is opOut):        # squaring, or the swapped operands: one launch
+                rlwe.Evaluator._rows(level, *tmp0.Value, *tmp1.Value, c0, c1, c2)
+                sq = op0 is op1
+                _check(lib().rh_ckks_tensor(self.ringQ._h, level, tmp0.Value[0].ptr, tmp0.Value[1].ptr, None if sq else tmp1.Value[0].ptr,
+                                            None if sq else tmp1.Value[1].ptr, c0.ptr, c1.ptr, c2.ptr, npoly, 0, 1 if sq else 0))
+            elif self.fused_tensor and op0 is not op1:                      # the same six ring calls as one kernel
                 rq.TensorDegree1(tmp0.Value[0], tmp0.Value[1], tmp1.Value[0], tmp1.Value[1], c0, c1, c2)
             else:
+                rq.MForm(tmp0.Value[0], c00)
+                rq.MForm(tmp0.Value[1], c01)
                 rq.MulCoeffsMontgomery(c00, tmp1.Value[0], c0)
                 rq.MulCoeffsMontgomery(c01, tmp1.Value[1], c2)
                 rq.MulCoeffsMontgomery(c00, tmp1.Value[1], c1)
-                rq.MulCoeffsMontgomeryThenAdd(c01, tmp1.Value[0], c1)
+                if op0 is op1:                                              # squaring
+                    rq.Add(c1, c1, c1)
+                else:
+                    rq.MulCoeffsMontgomeryThenAdd(c01, tmp1.Value[0], c1)
             if relin:
-                if self.rlk is None or self.ks is None:
-                    raise RingHipError("cannot MulRelin: Relinearize: relinearization key is missing")
                 self.ks.GadgetProductThenAdd(level, c2, self.rlk, c0, c1, opOut)      # GadgetProduct + the two Adds (:850-852)
-        elif d0 + d1 == 1 or (d0 == 0 and d1 == 0):
+        elif (d0 == 0 or d1 == 0) and d0 + d1 <= 2:
             pt, ct = (op0, op1) if d0 == 0 else (op1, op0)
             if opOut.Degree() != max(d0, d1):
                 raise RingHipError("MulRelin: opOut must have degree %d" % max(d0, d1))
-            c0 = new()
-            rq.MForm(pt.Value[0], c0)
-            for i, v in enumerate(ct.Value):
-                rq.MulCoeffsMontgomery(c0, v, opOut.Value[i])
+            if self._use("mul_plain"):
+                rlwe.Evaluator._rows(level, *pt.Value, *ct.Value, *opOut.Value)
+                _check(lib().rh_ckks_mul_plain(self.ringQ._h, level, *self._ptrs(ct.Value), pt.Value[0].ptr, *self._ptrs(opOut.Value), npoly, 0))
+            else:
+                c0 = new()
+                rq.MForm(pt.Value[0], c0)
+                for i, v in enumerate(ct.Value):
+                    rq.MulCoeffsMontgomery(c0, v, opOut.Value[i])
         else:
             raise RingHipError("MulRelin: unsupported degrees %d, %d" % (d0, d1))
+        if getattr(op0, "Scale", None) is not None and getattr(op1, "Scale", None) is not None:
+            opOut.Scale = self._scale(op0, "MulRelin").Mul(self._scale(op1, "MulRelin"))   # (:790)
         opOut.IsNTT = True
 
-    def Rescale(self, op0, opOut):
-        """Rescale (:500-535): DivRoundByLastModulusManyNTT(nbRescales) on every component.  opOut's polys keep op0's limb
-        count; limbs 0 .. level-nbRescales hold the result (ring/scaling.go:130-156)."""
-        nb = self.nb_rescales
-        if op0.Level() <= nb - 1:
-            raise RingHipError("cannot Rescale: input Ciphertext level is too low")
+    # ---- MulThenAdd / MulRelinThenAdd :918-1178 -------------------------------------------------------------------------------------------
+    def MulThenAdd(self, op0, op1, opOut):
+        """:918-1046: opOut += op0 x op1 without relinearisation.  A scalar op1: opOut and op0 of equal scale and a constant that is not a
+        Gaussian integer have opOut multiplied by the moduli one rescaling consumes first; opOut.Scale > op0.Scale scales the constant by
+        the quotient; op0.Scale > opOut.Scale is refused."""
+        self._refuse(op1, "MulThenAdd")
+        if isinstance(op1, Ciphertext):
+            if op0 is opOut or op1 is opOut:
+                raise RingHipError("cannot MulThenAdd: opOut must be different from op0 and op1")     # (:927-929)
+            return self.mulRelinThenAdd(op0, op1, False, opOut)
+        who = "MulThenAdd"
+        level = self._operands(who, op0, opOut)
+        scale0, scaleOut = self._scale(op0, who), self._scale(opOut, who)
         if opOut.Degree() != op0.Degree():
-            raise RingHipError("Rescale: degrees differ")
-        rq = self.ringQ.AtLevel(op0.Level())
-        for a, b in zip(op0.Value, opOut.Value):
-            rq.DivRoundByLastModulusManyNTT(nb, a, b)
-        opOut.IsNTT = op0.IsNTT
+            raise RingHipError("cannot MulThenAdd: opOut must have degree %d" % op0.Degree())
+        cmplx = to_complex(op1, self.encoding_precision)
+        cmp = scale0.Cmp(scaleOut)
+        if cmp == 0:                                                               # (:957-974)
+            if cmplx[0].denominator == 1 and cmplx[1].denominator == 1:
+                scaleRLWE = Scale(1)
+            else:
+                scaleRLWE = self._rescale_scale(level)
+                self._mul_scalar(opOut, int(scaleRLWE.Value), opOut, who)          # eval.Mul(opOut, scaleInt, opOut)
+                opOut.Scale = scaleOut.Mul(scaleRLWE)
+        elif cmp == -1:
+            scaleRLWE = scaleOut.Div(scale0)                                       # (:976-977)
+        else:
+            raise RingHipError("cannot MulThenAdd: op0.Scale > opOut.Scale is not supported")
+        s0, s1 = self._rns_scalar(level, scaleRLWE, cmplx)                         # (:982)
+        self._scalar_op(level, MUL_SCALAR_THEN_ADD, op0.Value, opOut.Value, s0, s1)
+        opOut.IsNTT = True
+
+    def MulRelinThenAdd(self, op0, op1, opOut):
+        """:1065-1093: the same with the degree-2 term relinearised before it is added (opOut of degree 1 or 2)"""
+        if isinstance(op1, Ciphertext) and op1.Degree() != 0:
+            if op0 is opOut or op1 is opOut:
+                raise RingHipError("cannot MulThenAdd: opOut must be different from op0 and op1")     # (:1078-1080)
+            return self.mulRelinThenAdd(op0, op1, True, opOut)
+        self.MulThenAdd(op0, op1, opOut)
+
+    def mulRelinThenAdd(self, op0, op1, relin, opOut):
+        """:1095-1178"""
+        who = "MulRelinThenAdd" if relin else "MulThenAdd"
+        level = self._operands(who, op0, op1, opOut)
+        d0, d1 = op0.Degree(), op1.Degree()
+        if d0 + d1 > 2 or d1 > 1 or d0 > 2:
+            raise RingHipError("cannot %s: degrees %d and %d: the sum of the degrees is at most 2" % (who, d0, d1))
+        ct = d0 == 1 and d1 == 1
+        if not ct and d1 != 0:
+            raise RingHipError("cannot %s: a degree-0 op0 with a degree-1 op1: give the plaintext as op1" % who)
+        if ct and (opOut.Degree() != 2 if not relin else opOut.Degree() not in (1, 2)):
+            raise RingHipError("cannot %s: opOut must have degree %s" % (who, "1 or 2" if relin else "2"))
+        if not ct and opOut.Degree() < d0:
+            raise RingHipError("cannot %s: opOut must have at least degree %d" % (who, d0))
+        if ct and relin and (self.rlk is None or self.ks is None):
+            raise RingHipError("cannot %s: cannot relinearize: relinearization key is missing" % who)
+        resScale = self._scale(op0, who).Mul(self._scale(op1, who))               # (:1099)
+        scaleOut = self._scale(opOut, who)
+        if scaleOut.Cmp(resScale) == -1:
+            ratio = resScale.Div(scaleOut)
+            if ratio.Float64() >= 2.0:                                             # only scales up if int(ratio) >= 2 (:1103-1109)
+                self._mul_scalar(opOut, ratio.Value, opOut, who)                   # eval.Mul(opOut, &ratio.Value, opOut): a *big.Float
+                opOut.Scale = resScale
+        rq = self.ringQ.AtLevel(level)
+        npoly = op0.Value[0].npoly
+        if ct:
+            c0, c1 = opOut.Value[0], opOut.Value[1]
+            c2 = self._buffer("buffQ3", rq, npoly, level + 1) if relin else opOut.Value[2]
+            if self._use("tensor"):
+                _check(lib().rh_ckks_tensor(self.ringQ._h, level, op0.Value[0].ptr, op0.Value[1].ptr, op1.Value[0].ptr, op1.Value[1].ptr,
+                                            c0.ptr, c1.ptr, c2.ptr, npoly, 2 if relin else 1, 0))
+            else:
+                c00, c01 = self._buffer("buffQ1", rq, npoly, level + 1), self._buffer("buffQ2", rq, npoly, level + 1)
+                rq.MForm(op0.Value[0], c00)                                        # (:1135-1136)
+                rq.MForm(op0.Value[1], c01)
+                rq.MulCoeffsMontgomeryThenAdd(c00, op1.Value[0], c0)               # (:1138-1140)
+                rq.MulCoeffsMontgomeryThenAdd(c00, op1.Value[1], c1)
+                rq.MulCoeffsMontgomeryThenAdd(c01, op1.Value[0], c1)
+                if relin:
+                    rq.MulCoeffsMontgomery(c01, op1.Value[1], c2)                  # (:1150)
+                else:
+                    rq.MulCoeffsMontgomeryThenAdd(c01, op1.Value[1], c2)           # (:1161)
+            if relin:
+                self.ks.GadgetProductThenAdd(level, c2, self.rlk, c0, c1, opOut)   # GadgetProduct + the two Adds (:1157-1159)
+        else:                                                                      # plaintext x ciphertext (:1165-1175)
+            if self._use("mul_plain"):
+                _check(lib().rh_ckks_mul_plain(self.ringQ._h, level, *self._ptrs(op0.Value), op1.Value[0].ptr,
+                                               *self._ptrs(opOut.Value[:d0 + 1]), npoly, 1))
+            else:
+                c00 = self._buffer("buffQ1", rq, npoly, level + 1)
+                rq.MForm(op1.Value[0], c00)
+                for i in range(d0 + 1):
+                    rq.MulCoeffsMontgomeryThenAdd(op0.Value[i], c00, opOut.Value[i])
+        opOut.IsNTT = True
+
+    # ---- Rotate / Conjugate / RotateHoisted :1195-1255 ------------------------------------------------------------------------------------
+    def _nth_root(self):
+        return (4 if self.ringQ.kind == ConjugateInvariant else 2) * self.ringQ.N
+
+    def GaloisElement(self, k):
+        return GaloisElement(self.ringQ.N, k, self._nth_root())
+
+    def _automorphism(self, op0, galEl, opOut, who):
+        if self.ks is None:
+            raise RingHipError("cannot %s: the evaluator was built without ringP, which the key switch needs" % who)
+        scale = self._scale(op0, who)
+        try:
+            self.ks.Automorphism(op0, galEl, opOut)
+        except RingHipError as e:
+            raise RingHipError("cannot %s: %s" % (who, e)) from None
+        opOut.Scale = scale
+
+    def Rotate(self, op0, k, opOut):
+        """:1202-1207: the slots rotated by k positions to the left"""
+        self._automorphism(op0, self.GaloisElement(k), opOut, "Rotate")
+
+    def RotateNew(self, op0, k):
+        opOut = self._new(op0.Degree(), op0)
+        self.Rotate(op0, k, opOut)
+        return opOut
+
+    def Conjugate(self, op0, opOut):
+        """:1218-1229"""
+        if self.ringQ.kind == ConjugateInvariant:
+            raise RingHipError("cannot Conjugate: method is not supported when parameters.RingType() == ring.ConjugateInvariant")
+        self._automorphism(op0, GaloisElementOrderTwoOrthogonalSubgroup(self.ringQ.N), opOut, "Conjugate")
+
+    def ConjugateNew(self, op0):
+        opOut = self._new(op0.Degree(), op0)
+        self.Conjugate(op0, opOut)
+        return opOut
+
+    def RotateHoisted(self, ctIn, rotations, opOut):
+        """:1245-1255: opOut, a dict rotation -> Ciphertext, filled with the rotations of ctIn, its decomposition shared"""
+        if self.ks is None:
+            raise RingHipError("cannot RotateHoisted: the evaluator was built without ringP, which the key switch needs")
+        scale = self._scale(ctIn, "RotateHoisted")
+        levelQ, levelP = ctIn.Level(), self.ringP.L - 1
+        beta = self.ks.BaseRNSDecompositionVectorSize(levelQ, levelP)
+        npoly = ctIn.Value[1].npoly
+        buff = (self.ks.buffer("BuffDecompQ", self.ringQ.AtLevel(levelQ), beta * npoly, levelQ + 1),
+                self.ks.buffer("BuffDecompP", self.ringP.AtLevel(levelP), beta * npoly, levelP + 1))
+        self.ks.DecomposeNTT(levelQ, levelP, ctIn.Value[1], ctIn.IsNTT, buff)
+        for i in rotations:
+            try:
+                self.ks.AutomorphismHoisted(levelQ, ctIn, buff, self.GaloisElement(i), opOut[i])
+            except RingHipError as e:
+                raise RingHipError("cannot RotateHoisted: %s" % e) from None
+            opOut[i].Scale = scale
+
+    def RotateHoistedNew(self, ctIn, rotations):
+        """:1233-1240"""
+        opOut = {i: self._new(1, ctIn) for i in rotations}
+        self.RotateHoisted(ctIn, rotations, opOut)
+        return opOut

@@ -136,6 +136,8 @@ def lib():
         "rh_bfv_mul_scale_invariant": (i, [vp, i, vp, vp, vp, vp, vp, vp, vp, i]),
         "rh_bgv_tensor": (i, [vp, i] + [vp] * 7 + [i, U64P, U64P, i]), "rh_bgv_mul_plain": (i, [vp, i] + [vp] * 7 + [i, U64P, U64P, i]),
         "rh_bgv_axpby": (i, [vp, i, vp, vp, vp, i, U64P, U64P, i]),
+        "rh_ckks_tensor": (i, [vp, i] + [vp] * 7 + [i, i, i]), "rh_ckks_mul_plain": (i, [vp, i] + [vp] * 7 + [i, i]),
+        "rh_ckks_scalar": (i, [vp, i, i] + [vp] * 6 + [i, U64P, U64P]), "rh_ckks_scale_then_add": (i, [vp, i] + [vp] * 9 + [i, U64P, i, i]),
         "rh_kshard_create": (i, [C.POINTER(vp), vp, vp, U64P, i, U64P, i, C.POINTER(i), i, C.POINTER(i), i]),
         "rh_kshard_destroy": (None, [vp]), "rh_kshard_num_digits": (i, [vp]),
         "rh_kshard_digit_range": (i, [vp, i, C.POINTER(i), C.POINTER(i)]),

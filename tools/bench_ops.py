@@ -3,7 +3,8 @@
 transform at the BASELINE config sizes, each against its algorithmic bytes.  Prints one JSON object.
 `bench_ops.py bfv [OUT.json]` runs the BFV group alone (quantize composed vs fused, the whole scale-invariant multiply) and writes
 profiles/bfv_ops.json (or OUT.json); `bench_ops.py bgv [OUT.json]` the BGV group (standard tensoring and multiply-accumulate, one kernel each
-against the reference's sequence of ring calls) and writes profiles/bgv_ops.json."""
+against the reference's sequence of ring calls) and writes profiles/bgv_ops.json; `bench_ops.py ckks [OUT.json]` the CKKS group
+(MulThenAdd, MulRelinThenAdd, scale-matched Add and scalar Mul at the config 5 ring, fused against composed) and writes profiles/ckks_ops.json."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -185,6 +186,82 @@ def bgv_group(out_path):
     for ev in evs.values():
         ev.close()
     rq.close(); rp.close()
+
+
+def ckks_group(out_path):
+    """The config 5 ring: N = 2^16, 24 limbs of Qi60, 6 of Pi60, batch 64 (one block is 768 MiB, far beyond the Infinity Cache).
+    ckks.Evaluator with fused=True (csrc/ckks.hip) against fused=False, which issues the reference's own sequence of ring calls through entry
+    points the library had before: the composed path is the baseline, timed HERE, alternating with the fused one.  Medians of `rounds` windows
+    of `reps` calls; the spread is the composed windows' max - min, and `fused_default` says whether the fused median is within that spread of
+    the composed one or below it -- the rule the evaluator's FUSED_DEFAULT table follows.  Whole-limb passes of the element-wise part: MulThenAdd
+    10 vs 20, scale-matched Add 6 vs 10, scalar Mul 4 vs 4 (one launch vs four); the relinearisation is the same launches on both sides."""
+    import statistics
+    N, LQ, LP, B, rounds, reps = 1 << 16, 24, 6, 64, 7, 10
+    Q, P = QI60[:LQ], PI60[:LP]
+    rq, rp = rh.Ring(N, Q), rh.Ring(N, P); rq.set_stream(stream.cuda_stream); rp.set_stream(stream.cuda_stream)
+    digits = (LQ + LP - 1) // LP
+    evq, evp = rand_block(2 * digits, Q, N), rand_block(2 * digits, P, N)
+    rlk = rh.rlwe.GadgetCiphertext.__new__(rh.rlwe.GadgetCiphertext)
+    rlk.digits, rlk.levelQ, rlk.levelP, rlk.BaseTwoDecomposition, rlk.digits_per_limb = digits, LQ - 1, LP - 1, 0, None
+    rlk.Q, rlk.P = rh.DevicePoly.from_torch(rq, evq), rh.DevicePoly.from_torch(rp, evp)
+    evs = {f: rh.ckks.Evaluator(rq, rp, rlk=rlk, fused=f) for f in (True, False)}
+    mk = lambda: rh.DevicePoly.from_torch(rq, rand_block(B, Q, N))
+    Sc = rh.ckks.Scale
+    ct0, ct1, ct6 = (rh.Ciphertext([mk(), mk()], is_ntt=True) for _ in range(3))
+    ct0.Scale, ct1.Scale, ct6.Scale = Sc(2 ** 40), Sc(2 ** 40), Sc(6 * 2 ** 40)
+    out2, out1 = rh.Ciphertext([mk(), mk(), mk()], is_ntt=True), rh.Ciphertext([mk(), mk()], is_ntt=True)
+
+    def matched(ct):                                  # an accumulator at the product's scale: nothing but the multiply-accumulate on every call
+        ct.Scale = Sc(2 ** 80)
+    cases = {
+        "MulThenAdd ct x ct into degree 2": (lambda ev: (matched(out2), ev.MulThenAdd(ct0, ct1, out2)), out2, 10, 20),
+        "MulRelinThenAdd": (lambda ev: (matched(out1), ev.MulRelinThenAdd(ct0, ct1, out1)), out1, 9, 19),
+        "Add, scales 1 : 6": (lambda ev: ev.Add(ct0, ct6, out1), out1, 6, 10),
+        "Mul by 0.5 on a degree-1 ciphertext": (lambda ev: ev.Mul(ct0, 0.5, out1), out1, 4, 4),
+    }
+    for name, (fn, acc, _, _) in cases.items():       # same bits first, on the shapes that are timed, both paths from the same accumulator
+        keep = [rh.DevicePoly.from_torch(rq, rand_block(B, Q, N)) for _ in acc.Value]
+        res = []
+        for fused in (True, False):
+            for v, h in zip(acc.Value, keep):
+                rq.CopyLvl(h, v)
+            fn(evs[fused]); res.append([v.numpy() for v in acc.Value])
+        assert all(np.array_equal(x, y) for x, y in zip(*res)), "fused and composed differ: " + name
+        del keep, res
+    stat = lambda v: {"ms_median": round(statistics.median(v), 4), "ms_min": round(min(v), 4), "ms_max": round(max(v), 4)}
+    results = []
+    for name, (fn, _, pf, pc) in cases.items():
+        tf, tc = [], []
+        for _ in range(rounds):
+            tf.append(timed(lambda: fn(evs[True]), reps=reps)); tc.append(timed(lambda: fn(evs[False]), reps=reps))
+        f, c = stat(tf), stat(tc)
+        spread = round(c["ms_max"] - c["ms_min"], 4)
+        limb_bytes = 8.0 * N * LQ * B
+        entry_ = {"op": name, "fused": f, "composed": c, "ratio_composed_over_fused": round(c["ms_median"] / f["ms_median"], 3),
+                  "composed_run_to_run_spread_ms": spread, "fused_default": bool(f["ms_median"] <= c["ms_median"] + spread),
+                  "passes_fused": pf, "passes_composed": pc}
+        if "Relin" not in name:                       # the element-wise part alone: algorithmic bandwidth means something
+            f["algorithmic_GBps"] = round(pf * limb_bytes / (f["ms_median"] * 1e-3) / 1e9, 1)
+            c["algorithmic_GBps"] = round(pc * limb_bytes / (c["ms_median"] * 1e-3) / 1e9, 1)
+            f["frac_of_8TBps"] = round(f["algorithmic_GBps"] / PEAK, 3)
+        results.append(entry_)
+    from bench import csrc_tree_hash
+    res = {"device": torch.cuda.get_device_name(0), "csrc_tree": csrc_tree_hash(), "shape": {"N": N, "limbs_Q": LQ, "limbs_P": LP, "batch": B},
+           "method": "%d alternating windows of %d calls each, device events, 2 warm-up calls per window; clocks left to the driver's default governor"
+                     % (rounds, reps),
+           "results": results}
+    with open(out_path, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(res, indent=1))
+    for ev in evs.values():
+        ev.close()
+    rq.close(); rp.close()
+
+
+if sys.argv[1:2] == ["ckks"]:
+    ckks_group(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "ckks_ops.json"))
+    sys.exit(0)
 
 
 if sys.argv[1:2] == ["bgv"]:
