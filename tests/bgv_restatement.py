@@ -180,7 +180,7 @@ def rescale(N, mods, t, op0, s0):
     return [div_round_by_last_modulus_ntt(x, N, mods) for x in op0], s0 * pow(mods[-1] % t, -1, t) % t    # :1436-1443
 
 
-# ---- big-integer ground truth: a toy key generator, encryption and decryption --------------------------------------------------------
+# ---- big-integer ground truth: encryption and decryption (real keys: tests/rlwe_restatement.py) --------------------------------------------------------
 def encrypt(rnd, N, mods, t, m, s, scale=1):
     """a degree-1 ciphertext of the given scale: phase c0 + c1 s = (m scale) T^-1 + e (mod Q), |e| <= 3, i.e. T * phase = m scale + T e, the
     BGV encryption c0 = -a s + m + T e up to the factor T^-1 this evaluator carries (tensorStandard multiplies it back in)"""
@@ -202,27 +202,3 @@ def decrypt(N, mods, t, c, s):
     for ck in reversed(c):                                           # Horner in s
         acc = [x + y for x, y in zip(negacyclic_mul_small(acc, s), crt(intt(ck, sr), mods))]
     return [x % t for x in centered([t * x for x in acc], Qb)]
-
-
-def relin_key(rnd, N, Q, Pk, s):
-    """a real relinearisation key for a gadget with one P modulus (one digit per q_i): row i = (b_i, a_i) over Q and P with
-    b_i + a_i s = e_i + P s^2 [limb q_i only], NTT domain, Montgomery form -- the layout oracle.compose.gadget_product_single_p reads.
-    Returns (evkQ (len(Q), 2, len(Q), N), evkP (len(Q), 2, len(Pk), N))."""
-    Pb = prod(Pk)
-    allm = list(Q) + list(Pk)
-    sr = subrings(N, tuple(allm))
-    s_ntt = ntt(rns(s, allm), sr)
-    rows = []
-    for i in range(len(Q)):
-        e_ntt = ntt(rns([rnd.randrange(-3, 4) for _ in range(N)], allm), sr)
-        b, a = [], []
-        for u, q in enumerate(allm):
-            au = [rnd.randrange(q) for _ in range(N)]
-            bu = [(int(ev) - x * int(sv)) % q for ev, x, sv in zip(e_ntt[u], au, s_ntt[u])]
-            if u == i:
-                bu = [(x + Pb * int(sv) * int(sv)) % q for x, sv in zip(bu, s_ntt[u])]
-            a.append(np.array([(x << 64) % q for x in au], dtype=np.uint64))
-            b.append(np.array([(x << 64) % q for x in bu], dtype=np.uint64))
-        rows.append(np.stack([np.stack(b), np.stack(a)]))
-    key = np.stack(rows)                                             # (digit, component, limb of Q then P, N)
-    return key[:, :, :len(Q)].copy(), key[:, :, len(Q):].copy()

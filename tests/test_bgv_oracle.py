@@ -10,6 +10,7 @@ import pytest
 
 import bfv_restatement as br
 import bgv_restatement as gr
+import rlwe_restatement as rr
 from oracle import primes
 
 T = 65537
@@ -120,7 +121,8 @@ def world():
     Q, Pk = primes.gen_moduli(6, [61, 61], [61])
     rnd = random.Random(2025)
     s = [rnd.randrange(-1, 2) for _ in range(N)]
-    evkQ, evkP = gr.relin_key(rnd, N, Q, Pk, s)
+    rlk = rr.relin_key(rnd, rr.Secret(N, s), Q, Pk, len(Q) - 1, 0)     # the one key generator (tests/rlwe_restatement.py), one P modulus
+    evkQ, evkP = rlk.Q, rlk.P
     return N, Q, Pk, s, evkQ, evkP, rnd
 
 

@@ -1,6 +1,7 @@
 """GPU: the CKKS multiply -> relinearise -> rescale chain (schemes/ckks/evaluator.go:786-881, 500-535) on device batches
-against the same sequence on the CPU oracle.  Keys are uniformly random; scheme-level decryption
-correctness is the reference's business and is not claimed here."""
+against the same sequence on the CPU oracle.  Keys are uniformly random here: arithmetic parity only.  Decryption
+under a real relinearisation key and real Galois keys (MulRelin -> Rescale, Rotate, Conjugate, RotateHoisted) is pinned by
+tests/test_rlwe_oracle.py on the CPU composition and by tests/test_gpu_rlwe_decrypt.py on the device path."""
 import numpy as np
 import pytest
 

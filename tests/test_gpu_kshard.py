@@ -1,5 +1,5 @@
 """GPU: limb-sharded hybrid key switch against the unsharded rh_bext_gadget_product, which
-tests/test_gpu_keyswitch.py pins to the oracle composition.  Multi-rank cases run as separate processes that share
+tests/test_gpu_keyswitch.py pins to the oracle composition; the multi-rank case also compares every rank's owned limbs with that composition itself.  Multi-rank cases run as separate processes that share
 the box's one GPU and exchange limbs over gloo (host-staged); on a multi-GPU node the same class uses RCCL."""
 import os
 import socket
@@ -95,9 +95,14 @@ def _worker(rank, world, port, q, N, nq, np_):
     Q, P, beta, cx, evkQ, evkP = _case(N, nq, np_, 5, 99)              # same case on every rank; each keeps its limbs (5 polys: chunks of 2, 2, 1)
     g0, g1, ownQ, ownP, _ = _run_shard(rh, sharding, N, Q, P, cx, evkQ, evkP, rank, world, dist)
     ok = None
+    from oracle import compose
+    own = [compose.gadget_product(N, Q, P, nq - 1, np_ - 1, cx[k], evkQ, evkP) for k in range(cx.shape[0])]
+    direct = all(np.array_equal(g[k], o[c][ownQ]) for k, o in enumerate(own) for c, g in ((0, g0), (1, g1)))    # every owned limb of every poly
     if rank == 0:
         e0, e1 = _unsharded(rh, N, Q, P, beta, cx, evkQ, evkP)
         ok = (e0, e1)
+    directs = [None] * world
+    dist.all_gather_object(directs, bool(direct))
     parts = sharding.gather_shards((g0, g1, ownQ, ownP), dist)          # the final gather
     if rank == 0:
         full0, full1 = np.zeros_like(ok[0]), np.zeros_like(ok[1])
@@ -105,7 +110,7 @@ def _worker(rank, world, port, q, N, nq, np_):
         for p0, p1, oq, _op in parts:
             full0[:, oq] = p0; full1[:, oq] = p1; seen += oq
         q.put((sorted(seen) == list(range(nq)), bool(np.array_equal(full0, ok[0])), bool(np.array_equal(full1, ok[1])),
-               [len(p[3]) for p in parts]))
+               [len(p[3]) for p in parts], directs))
     dist.barrier()
     dist.destroy_process_group()
 
@@ -133,11 +138,12 @@ def test_multi_rank_limb_shard_gloo(world, N, nq, np_):
             if p.is_alive():
                 p.terminate()
         raise AssertionError("a rank failed: exit codes %s" % [p.exitcode for p in ps])
-    covered, ok0, ok1, pcounts = res
+    covered, ok0, ok1, pcounts, directs = res
     for p in ps:
         p.join(timeout=120)
         assert p.exitcode == 0
     assert covered and ok0 and ok1
+    assert directs == [True] * world                                    # every rank's owned limbs against oracle/compose.py directly, not only the unsharded device product
     if world == 4:
         assert 0 in pcounts                                             # a rank that owns no P limb took part
 

@@ -1,7 +1,8 @@
 """GPU: rgsw.Evaluator.ExternalProduct (core/rgsw/evaluator.go:42-80, 188-257, LevelP >= 1) against the reference's loop restated over
 the oracle pieces (oracle/compose.py: one pair of lazy accumulators through both components and all digits, running Reduce counter,
-closing Reduce, ModDownQPtoQNTT).  Uniformly random RGSW values: arithmetic parity needs no encryption (the reference pins the external
-product only through decryption noise, core/rgsw/rgsw_test.go:60-129: that end-to-end statement stays parity unpinned)."""
+closing Reduce, ModDownQPtoQNTT).  Uniformly random RGSW values here: arithmetic parity needs no encryption.  The reference's own statement (core/rgsw/rgsw_test.go:61-113:
+RGSW(X^k0) x RLWE(q0 X^k1) decrypts to the monomial) is pinned with real RGSW encryptions by tests/test_rlwe_oracle.py (the oracle's loop) and
+tests/test_gpu_rlwe_decrypt.py (the device path, multi-P and single-P with a power-of-two decomposition)."""
 import numpy as np
 import pytest
 
