@@ -67,17 +67,15 @@ static int common(rh_ring* r, int level, const void* in, const void* out, int np
   (void)hipGetLastError();
   return 0;
 }
-static int done(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return rh_fail(RH_ERR_DEVICE, "%s launch failed: %s", what, hipGetErrorString(e));
-  return RH_OK;
-}
+// These kernels move single words to permuted places, so a thread's unit is the coefficient: chunks of 1024 words, not rh_stream_grid's
+// 1024 pairs.
+static unsigned word_chunks(unsigned words) { unsigned c = (words + 1023) / 1024; return c > 64 ? 64 : (c ? c : 1); }
 
 extern "C" int rh_ring_automorphism_ntt(rh_ring* r, int level, const uint64_t* in, uint64_t gen, uint64_t* out, int npoly, int add_lazy) {
   if (int rc = common(r, level, in, out, npoly)) return rc;
   const unsigned rows = (unsigned)npoly * (level + 1);
   if (!rows) return RH_OK;
-  unsigned chunks = ((unsigned)r->N + 1023) / 1024; if (chunks > 64) chunks = 64;
+  const unsigned chunks = word_chunks((unsigned)r->N);
   const int lg = r->kind == RH_RING_CI ? r->logN + 1 : r->logN;          // log2(NthRoot) - 1 with NthRoot = 4N / 2N (ring/ring.go:178-183)
   const u64 nthroot = (u64)2 << lg;
   if ((gen & 1) == 0) return rh_fail(RH_ERR_ARG, "automorphism: the Galois element must be odd");
@@ -85,17 +83,17 @@ extern "C" int rh_ring_automorphism_ntt(rh_ring* r, int level, const uint64_t* i
   // ring does not hold and the reference's table look-up runs past the N coefficients (index out of range panic)
   if (r->kind == RH_RING_CI && (gen & 3) != 1) return rh_fail(RH_ERR_ARG, "automorphism: on a conjugate-invariant ring the Galois element must be 1 mod 4");
   automorphism_ntt_kernel<<<dim3(rows, chunks), 256, 0, rh_stream(r)>>>(in, out, r->logN, lg, (u32)(gen & (nthroot - 1)), add_lazy ? 1 : 0);
-  return done("automorphism_ntt_kernel");
+  return rh_launch_ok("automorphism_ntt_kernel");
 }
 extern "C" int rh_ring_automorphism(rh_ring* r, int level, const uint64_t* in, uint64_t gen, uint64_t* out, int npoly) {
   if (int rc = common(r, level, in, out, npoly)) return rc;
   const unsigned rows = (unsigned)npoly * (level + 1);
   if (!rows) return RH_OK;
-  unsigned chunks = ((unsigned)r->N + 1023) / 1024; if (chunks > 64) chunks = 64;
+  const unsigned chunks = word_chunks((unsigned)r->N);
   if ((gen & 1) == 0) return rh_fail(RH_ERR_ARG, "automorphism: the Galois element must be odd");
   if (r->kind == RH_RING_CI) automorphism_coeff_ci_kernel<<<dim3(rows, chunks), 256, 0, rh_stream(r)>>>(in, out, r->logN, gen, r->d_consts, level + 1);
   else automorphism_coeff_kernel<<<dim3(rows, chunks), 256, 0, rh_stream(r)>>>(in, out, r->logN, gen, r->d_consts, level + 1);
-  return done("automorphism_coeff_kernel");
+  return rh_launch_ok("automorphism_coeff_kernel");
 }
 
 // ---- ring.Shift and ring.MultByMonomial (ring/operations.go:278-282, 306-363): index maps over every limb of a block, out of place ----
@@ -138,9 +136,9 @@ extern "C" int rh_ring_shift(rh_ring* r, int level, const uint64_t* in, uint64_t
   if (!rows) return RH_OK;
   const int N = r->N;
   int kk = k % N; if (kk < 0) kk += N;
-  unsigned chunks = ((unsigned)N + 1023) / 1024; if (chunks > 64) chunks = 64;
+  const unsigned chunks = word_chunks((unsigned)N);
   shift_kernel<<<dim3(rows, chunks), 256, 0, rh_stream(r)>>>(in, out, (unsigned)N, (unsigned)kk);
-  return done("shift_kernel");
+  return rh_launch_ok("shift_kernel");
 }
 extern "C" int rh_ring_mult_by_monomial(rh_ring* r, int level, const uint64_t* in, uint64_t* out, int k, int npoly) {
   if (int rc = index_map_common(r, level, in, out, npoly, "mult_by_monomial")) return rc;
@@ -152,9 +150,9 @@ extern "C" int rh_ring_mult_by_monomial(rh_ring* r, int level, const uint64_t* i
     if (hipMemcpyAsync(out, in, (size_t)rows * N * 8, hipMemcpyDeviceToDevice, rh_stream(r)) != hipSuccess) return rh_fail(RH_ERR_DEVICE, "mult_by_monomial: copy failed");
     return RH_OK;
   }
-  unsigned chunks = ((unsigned)N + 1023) / 1024; if (chunks > 64) chunks = 64;
+  const unsigned chunks = word_chunks((unsigned)N);
   monomial_kernel<<<dim3(rows, chunks), 256, 0, rh_stream(r)>>>(in, out, (unsigned)N, (unsigned)sh, r->d_consts, level + 1);
-  return done("monomial_kernel");
+  return rh_launch_ok("monomial_kernel");
 }
 
 // ---- AutomorphismNTTWithIndex / ...ThenAddLazy (:50-117): the caller's lookup table (N words on the device), any permutation
@@ -172,9 +170,9 @@ extern "C" int rh_ring_automorphism_ntt_index(rh_ring* r, int level, const uint6
   if (int rc = index_map_common(r, level, in, out, npoly, "automorphism (with index)")) return rc;
   const unsigned rows = (unsigned)npoly * (unsigned)(level + 1);
   if (!rows) return RH_OK;
-  unsigned chunks = ((unsigned)r->N + 1023) / 1024; if (chunks > 64) chunks = 64;
+  const unsigned chunks = word_chunks((unsigned)r->N);
   automorphism_index_kernel<<<dim3(rows, chunks), 256, 0, rh_stream(r)>>>(in, out, index, (unsigned)r->N, add_lazy);
-  return done("automorphism_index_kernel");
+  return rh_launch_ok("automorphism_index_kernel");
 }
 
 // ---- standard <-> conjugate-invariant bridges (ring/conjugate_invariant.go) ----------------------------------------------------------
@@ -212,28 +210,27 @@ ci_pad_kernel(const u64* std_, u64* ci, unsigned n, int is_ntt, const LimbConsts
     ci[bo + k] = v;
   }
 }
-static unsigned bridge_chunks(unsigned words) { unsigned c = (words + 1023) / 1024; return c > 64 ? 64 : (c ? c : 1); }
 extern "C" int rh_ring_unfold_ci_to_standard(rh_ring* r, int level, const uint64_t* ci, uint64_t* std_, int npoly) {
   if (int rc = index_map_common(r, level, ci, std_, npoly, "unfold_ci_to_standard")) return rc;
   if (r->kind != RH_RING_STANDARD || r->N < 2) return rh_fail(RH_ERR_ARG, "unfold_ci_to_standard: the receiver is the standard ring of degree 2n");
   const unsigned rows = (unsigned)npoly * (unsigned)(level + 1), n = (unsigned)r->N / 2;
   if (!rows) return RH_OK;
-  ci_unfold_kernel<<<dim3(rows, bridge_chunks(2 * n)), 256, 0, rh_stream(r)>>>(ci, std_, n);
-  return done("ci_unfold_kernel");
+  ci_unfold_kernel<<<dim3(rows, word_chunks(2 * n)), 256, 0, rh_stream(r)>>>(ci, std_, n);
+  return rh_launch_ok("ci_unfold_kernel");
 }
 extern "C" int rh_ring_fold_standard_to_ci(rh_ring* r, int level, const uint64_t* std_, const uint64_t* index, uint64_t* ci, int npoly) {
   if (!index) return rh_fail(RH_ERR_ARG, "fold_standard_to_ci: null index table");
   if (int rc = index_map_common(r, level, std_, ci, npoly, "fold_standard_to_ci")) return rc;
   const unsigned rows = (unsigned)npoly * (unsigned)(level + 1), n = (unsigned)r->N;
   if (!rows) return RH_OK;
-  ci_fold_std_kernel<<<dim3(rows, bridge_chunks(n)), 256, 0, rh_stream(r)>>>(std_, index, ci, n, r->d_consts, level + 1);
-  return done("ci_fold_std_kernel");
+  ci_fold_std_kernel<<<dim3(rows, word_chunks(n)), 256, 0, rh_stream(r)>>>(std_, index, ci, n, r->d_consts, level + 1);
+  return rh_launch_ok("ci_fold_std_kernel");
 }
 extern "C" int rh_ring_pad_default_to_ci(rh_ring* r, int level, const uint64_t* std_, int is_ntt, uint64_t* ci, int npoly) {
   if (int rc = index_map_common(r, level, std_, ci, npoly, "pad_default_to_ci")) return rc;
   if (r->N < 2) return rh_fail(RH_ERR_ARG, "pad_default_to_ci: degree < 2");
   const unsigned rows = (unsigned)npoly * (unsigned)(level + 1), n = (unsigned)r->N;
   if (!rows) return RH_OK;
-  ci_pad_kernel<<<dim3(rows, bridge_chunks(n)), 256, 0, rh_stream(r)>>>(std_, ci, n, is_ntt ? 1 : 0, r->d_consts, level + 1);
-  return done("ci_pad_kernel");
+  ci_pad_kernel<<<dim3(rows, word_chunks(n)), 256, 0, rh_stream(r)>>>(std_, ci, n, is_ntt ? 1 : 0, r->d_consts, level + 1);
+  return rh_launch_ok("ci_pad_kernel");
 }

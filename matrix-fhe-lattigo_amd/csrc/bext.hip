@@ -302,9 +302,7 @@ static int launch_plan(rh_bext* be, const BextPlan& p, const u64* in, int in_row
   dim3 grid((N + 255) / 256, npoly);
   (void)hipGetLastError();
   bext_dispatch(grid, rh_stream(R), p, in, in_rows, src_limb0, out0, out0_rows, out1, out1_rows, other, other_rows, N, add_mode);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return rh_fail(RH_ERR_DEVICE, "bext_kernel launch failed: %s", hipGetErrorString(e));
-  return RH_OK;
+  return rh_launch_ok("bext_kernel");
 }
 
 static int check_levels(rh_bext* be, int levelQ, int levelP, bool needP) {
@@ -465,9 +463,7 @@ extern "C" int rh_bext_decompose_and_split(rh_bext* be, int levelQ, int levelP, 
     dim3 grid((N + 255) / 256, npoly);
     (void)hipGetLastError();
     bext_sign_copy_kernel<<<grid, 256, 0, rh_stream(RQ)>>>(p0Q, levelQ + 1, st, p.qd, p.ntgt, p.d_sign, p1Q, levelQ + 1, p1P, nP, N);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return rh_fail(RH_ERR_DEVICE, "bext_sign_copy_kernel launch failed: %s", hipGetErrorString(e));
-    return RH_OK;
+    return rh_launch_ok("bext_sign_copy_kernel");
   }
   return launch_plan(be, p, p0Q, levelQ + 1, st, p1Q, levelQ + 1, p1P, nP, nullptr, 0, npoly, BEXT_ADD_RAW);
 }
@@ -508,9 +504,7 @@ int rh_bext_decompose_and_split_all(rh_bext* be, int levelQ, int levelP, int nbP
     default: RH_BM(8, false); break;
   }
 #undef RH_BM
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return rh_fail(RH_ERR_DEVICE, "bext_multi_kernel launch failed: %s", hipGetErrorString(e));
-  return RH_OK;
+  return rh_launch_ok("bext_multi_kernel");
 }
 
 // ---- internals shared with kshard.hip (bext_internal.hpp) ----
@@ -550,9 +544,7 @@ int rh_bext_launch_raw(hipStream_t st, int N, const BextPlan& p, const u64* in, 
   dim3 grid((N + 255) / 256, npoly);
   (void)hipGetLastError();
   bext_dispatch(grid, st, p, in, in_rows, src_limb0, out0, out0_rows, out1, out1_rows, other, other_rows, N, add_mode);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return rh_fail(RH_ERR_DEVICE, "bext_kernel launch failed: %s", hipGetErrorString(e));
-  return RH_OK;
+  return rh_launch_ok("bext_kernel");
 }
 int rh_bext_launch_sign(hipStream_t st, int N, const BextPlan& p, const u64* in, int in_rows, int src_limb, u64* out0, int out0_rows,
                         u64* out1, int out1_rows, int npoly) {
@@ -560,7 +552,5 @@ int rh_bext_launch_sign(hipStream_t st, int N, const BextPlan& p, const u64* in,
   dim3 grid((N + 255) / 256, npoly);
   (void)hipGetLastError();
   bext_sign_copy_kernel<<<grid, 256, 0, st>>>(in, in_rows, src_limb, p.qd, p.ntgt, p.d_sign, out0, out0_rows, out1, out1_rows, N);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return rh_fail(RH_ERR_DEVICE, "bext_sign_copy_kernel launch failed: %s", hipGetErrorString(e));
-  return RH_OK;
+  return rh_launch_ok("bext_sign_copy_kernel");
 }

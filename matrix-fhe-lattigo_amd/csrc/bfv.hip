@@ -29,6 +29,7 @@
 #include "engine_internal.hpp"
 #include "bext_internal.hpp"
 #include "bext_kernels.hip.hpp"
+#include "stream_kernels.hip.hpp"
 #include "hostmath.hpp"
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -41,21 +42,12 @@ struct BfvTensorSide {
   int rows;                        // limbs per poly of this ring's blocks
 };
 
-// grid: (npoly * (rowsQ + rowsM), chunks); row u of a poly is limb u of Q (u < rowsQ) or limb u - rowsQ of QMul.
+// grid: (npoly * (rowsQ + rowsM), chunks); row u of a poly is limb u of Q (u < rowsQ) or limb u - rowsQ of QMul: a row mapping of its own,
+// so of the scaffold (stream_kernels.hip.hpp) it takes the pair loop and the load / store pair, not StreamRow.
 // Outputs may alias inputs element-wise.
 template <bool SQUARE>
 __global__ void __launch_bounds__(256)
 bfv_tensor_kernel(BfvTensorSide sq, BfvTensorSide sm, unsigned n, int nt) {
-  typedef u64 u64x2_t __attribute__((ext_vector_type(2)));
-  auto ld = [&](const u64* p) {
-    if (!nt) return *reinterpret_cast<const ulonglong2*>(p);
-    const u64x2_t v = __builtin_nontemporal_load(reinterpret_cast<const u64x2_t*>(p));
-    return make_ulonglong2(v.x, v.y);
-  };
-  auto st = [&](u64* p, const ulonglong2& w) {
-    if (nt) { u64x2_t v; v.x = w.x; v.y = w.y; __builtin_nontemporal_store(v, reinterpret_cast<u64x2_t*>(p)); }
-    else *reinterpret_cast<ulonglong2*>(p) = w;
-  };
   const u32 per = (u32)(sq.rows + sm.rows);
   const u32 poly = blockIdx.x / per, u = blockIdx.x % per;
   const bool inQ = u < (u32)sq.rows;
@@ -74,15 +66,15 @@ bfv_tensor_kernel(BfvTensorSide sq, BfvTensorSide sm, unsigned n, int nt) {
       r1 = mred(m0, y1, c.q, c.qinv) + mred(m1, y0, c.q, c.qinv);
     }
   };
-  for (unsigned i = blockIdx.y * blockDim.x + threadIdx.x; i < (n >> 1); i += gridDim.y * blockDim.x) {
+  RH_FOR_EACH_PAIR(i, 0, n >> 1) {
     const size_t o = ro + 2 * (size_t)i;
-    const ulonglong2 x0 = ld(s.a0 + o), x1 = ld(s.a1 + o);
+    const ulonglong2 x0 = rh_ld2(s.a0 + o, nt), x1 = rh_ld2(s.a1 + o, nt);
     ulonglong2 y0 = make_ulonglong2(0, 0), y1 = y0;
-    if (!SQUARE) { y0 = ld(s.b0 + o); y1 = ld(s.b1 + o); }
+    if (!SQUARE) { y0 = rh_ld2(s.b0 + o, nt); y1 = rh_ld2(s.b1 + o, nt); }
     u64 lo0, lo1, lo2, hi0, hi1, hi2;
     one(x0.x, x1.x, y0.x, y1.x, lo0, lo1, lo2);
     one(x0.y, x1.y, y0.y, y1.y, hi0, hi1, hi2);
-    st(s.c0 + o, make_ulonglong2(lo0, hi0)); st(s.c1 + o, make_ulonglong2(lo1, hi1)); st(s.c2 + o, make_ulonglong2(lo2, hi2));
+    rh_st2(s.c0 + o, make_ulonglong2(lo0, hi0), nt); rh_st2(s.c1 + o, make_ulonglong2(lo1, hi1), nt); rh_st2(s.c2 + o, make_ulonglong2(lo2, hi2), nt);
   }
 }
 
@@ -169,12 +161,6 @@ struct rh_bfv {
   int fused_quantize = 0;                             // see the header: composed by default, the fused kernel on request
   std::recursive_mutex mu;
 };
-
-static int bfv_launch_ok(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return rh_fail(RH_ERR_DEVICE, "%s launch failed: %s", what, hipGetErrorString(e));
-  return RH_OK;
-}
 
 // bit length of q_0 * ... * q_i for every i
 static std::vector<int> product_bitlens(const std::vector<u64>& mods) {
@@ -276,14 +262,12 @@ static int bfv_levels(rh_bfv* b, int level, int npoly, int* lq, const char* who)
 static int tensor_launch(rh_bfv* b, int level, int lq, const BfvTensorSide& sq, const BfvTensorSide& sm, int npoly, bool square) {
   const unsigned rows = (unsigned)npoly * (unsigned)(level + 1 + lq + 1), n = (unsigned)b->Q->N;
   if (rows == 0) return RH_OK;
-  unsigned chunks = (n / 2 + 1023) / 1024; if (chunks < 1) chunks = 1; if (chunks > 64) chunks = 64;
-  const int nt = rh_nt_policy(b->Q->nt_streams, (size_t)rows * n * 8, (size_t)512 << 20) ? 1 : 0;     // as rh_streams_beyond_cache
-  const dim3 grid(rows, chunks);
+  const RhStreamGrid g = rh_stream_grid(b->Q, rows);                 // both rings have Q's N; the rows of both count towards the working set
   hipStream_t st = rh_stream(b->Q);
   (void)hipGetLastError();
-  if (square) bfv_tensor_kernel<true><<<grid, 256, 0, st>>>(sq, sm, n, nt);
-  else bfv_tensor_kernel<false><<<grid, 256, 0, st>>>(sq, sm, n, nt);
-  return bfv_launch_ok("bfv_tensor_kernel");
+  if (square) bfv_tensor_kernel<true><<<g.grid, 256, 0, st>>>(sq, sm, n, g.nt);
+  else bfv_tensor_kernel<false><<<g.grid, 256, 0, st>>>(sq, sm, n, g.nt);
+  return rh_launch_ok("bfv_tensor_kernel");
 }
 
 extern "C" int rh_bfv_tensor_lazy(rh_bfv* b, int level, const uint64_t* a0Q, const uint64_t* a1Q, const uint64_t* b0Q, const uint64_t* b1Q,
@@ -317,7 +301,7 @@ static int quantize_core(rh_bfv* b, int level, int lq, u64* bq, u64* bm, int npo
   const size_t lds = (size_t)(NM * (NQ + 1) + NQ * (NM + 1)) * 8;                                  // at most 2 * 72 words
   (void)hipGetLastError();
   hipLaunchKernelGGL(table[(NQ - 1) * 8 + (NM - 1)], dim3((N + 255) / 256, npoly), dim3(256), lds, rh_stream(b->Q), bq, bm, bq, a, N);
-  return bfv_launch_ok("bfv_quantize_kernel");
+  return rh_launch_ok("bfv_quantize_kernel");
 }
 
 extern "C" int rh_bfv_quantize(rh_bfv* b, int level, const uint64_t* cQ, const uint64_t* cM, uint64_t* outQ, int npoly) {

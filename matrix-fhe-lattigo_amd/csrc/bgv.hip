@@ -16,34 +16,23 @@
 //   bgv_axpby_kernel      matchScaleThenEvaluateInPlace (:288-305): out = r0 * a +- r1 * b, out = r0 * a, out = +- r1 * b.
 //
 // Each thread reads all of its operands before it writes, so outputs may alias inputs element-wise (opOut is op0 / op1).  Bandwidth-bound,
-// no LDS; 16-byte loads and stores, non-temporal beyond the Infinity Cache, as tensor_degree1_kernel (engine.hip).
+// no LDS; 16-byte loads and stores, non-temporal beyond the Infinity Cache: the scaffold of stream_kernels.hip.hpp.
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include "engine_internal.hpp"
+#include "stream_kernels.hip.hpp"
 
-struct BgvScalars { u64 k[RH_MAX_LIMBS]; u64 r1[RH_MAX_LIMBS]; };      // per-limb constants by value (1 KiB of kernel arguments)
-
-typedef u64 bgv_u64x2_t __attribute__((ext_vector_type(2)));
-RH_DEV ulonglong2 bgv_ld(const u64* p, int nt) {
-  if (!nt) return *reinterpret_cast<const ulonglong2*>(p);
-  const bgv_u64x2_t v = __builtin_nontemporal_load(reinterpret_cast<const bgv_u64x2_t*>(p));
-  return make_ulonglong2(v.x, v.y);
-}
-RH_DEV void bgv_st(u64* p, const ulonglong2& w, int nt) {
-  if (nt) { bgv_u64x2_t v; v.x = w.x; v.y = w.y; __builtin_nontemporal_store(v, reinterpret_cast<bgv_u64x2_t*>(p)); }
-  else *reinterpret_cast<ulonglong2*>(p) = w;
-}
+// The per-limb constants travel by value as RhScalars: a = k (tensor, mul_plain) or MForm(r0) (axpby), b = r1.
 
 // ACC 0: c0, c1, c2 written; 1: all three read and added to; 2: c0, c1 read and added to, c2 written (the relin form :1353).
 // grid: (npoly * L, chunks); L = level + 1 rows per poly.
 template <bool SQUARE, int ACC>
 __global__ void __launch_bounds__(256)
 bgv_tensor_kernel(const u64* a0, const u64* a1, const u64* b0, const u64* b1, u64* c0, u64* c1, u64* c2, unsigned n,
-                  const LimbConsts* __restrict__ consts, int L, BgvScalars s, int has_r1, int nt) {
-  const u32 row = blockIdx.x, limb = row % (u32)L;
-  const LimbConsts c = consts[limb];
-  const u64 k = s.k[limb], r1 = s.r1[limb];
-  const size_t ro = (size_t)row * n;
+                  const LimbConsts* __restrict__ consts, int L, RhScalars s, int has_r1, int nt) {
+  const StreamRow row(consts, L, n);
+  const LimbConsts& c = row.c;
+  const u64 k = s.a[row.limb], r1 = s.b[row.limb];
   auto one = [&](u64 x0, u64 x1, u64 y0, u64 y1, u64 z0, u64 z1, u64 z2, u64& o0, u64& o1, u64& o2) {
     const u64 m0 = mred(x0, k, c.q, c.qinv), m1 = mred(x1, k, c.q, c.qinv);          // x * T * r0 * 2^64
     u64 p0, p1, p2;
@@ -64,17 +53,17 @@ bgv_tensor_kernel(const u64* a0, const u64* a1, const u64* b0, const u64* b1, u6
       o0 = p0; o1 = cred(p1, c.q); o2 = p2;
     }
   };
-  for (unsigned i = blockIdx.y * blockDim.x + threadIdx.x; i < (n >> 1); i += gridDim.y * blockDim.x) {
-    const size_t o = ro + 2 * (size_t)i;
-    const ulonglong2 x0 = bgv_ld(a0 + o, nt), x1 = bgv_ld(a1 + o, nt);
+  RH_FOR_EACH_PAIR(i, 0, n >> 1) {
+    const size_t o = row.ro + 2 * (size_t)i;
+    const ulonglong2 x0 = rh_ld2(a0 + o, nt), x1 = rh_ld2(a1 + o, nt);
     ulonglong2 y0 = make_ulonglong2(0, 0), y1 = y0, z0 = y0, z1 = y0, z2 = y0;
-    if (!SQUARE) { y0 = bgv_ld(b0 + o, nt); y1 = bgv_ld(b1 + o, nt); }
-    if (ACC) { z0 = bgv_ld(c0 + o, nt); z1 = bgv_ld(c1 + o, nt); }
-    if (ACC == 1) z2 = bgv_ld(c2 + o, nt);
+    if (!SQUARE) { y0 = rh_ld2(b0 + o, nt); y1 = rh_ld2(b1 + o, nt); }
+    if (ACC) { z0 = rh_ld2(c0 + o, nt); z1 = rh_ld2(c1 + o, nt); }
+    if (ACC == 1) z2 = rh_ld2(c2 + o, nt);
     u64 lo0, lo1, lo2, hi0, hi1, hi2;
     one(x0.x, x1.x, y0.x, y1.x, z0.x, z1.x, z2.x, lo0, lo1, lo2);
     one(x0.y, x1.y, y0.y, y1.y, z0.y, z1.y, z2.y, hi0, hi1, hi2);
-    bgv_st(c0 + o, make_ulonglong2(lo0, hi0), nt); bgv_st(c1 + o, make_ulonglong2(lo1, hi1), nt); bgv_st(c2 + o, make_ulonglong2(lo2, hi2), nt);
+    rh_st2(c0 + o, make_ulonglong2(lo0, hi0), nt); rh_st2(c1 + o, make_ulonglong2(lo1, hi1), nt); rh_st2(c2 + o, make_ulonglong2(lo2, hi2), nt);
   }
 }
 
@@ -83,19 +72,18 @@ struct BgvComps { const u64* in[3]; u64* out[3]; };
 // out[j] (+)= ct[j] * pt * T * r0 for j < NC; pt: one block (npoly, L, N) shared by the components
 template <int NC, bool ACC>
 __global__ void __launch_bounds__(256)
-bgv_mul_plain_kernel(BgvComps p, const u64* pt, unsigned n, const LimbConsts* __restrict__ consts, int L, BgvScalars s, int has_r1, int nt) {
-  const u32 row = blockIdx.x, limb = row % (u32)L;
-  const LimbConsts c = consts[limb];
-  const u64 k = s.k[limb], r1 = s.r1[limb];
-  const size_t ro = (size_t)row * n;
-  for (unsigned i = blockIdx.y * blockDim.x + threadIdx.x; i < (n >> 1); i += gridDim.y * blockDim.x) {
-    const size_t o = ro + 2 * (size_t)i;
-    const ulonglong2 w = bgv_ld(pt + o, nt);
+bgv_mul_plain_kernel(BgvComps p, const u64* pt, unsigned n, const LimbConsts* __restrict__ consts, int L, RhScalars s, int has_r1, int nt) {
+  const StreamRow row(consts, L, n);
+  const LimbConsts& c = row.c;
+  const u64 k = s.a[row.limb], r1 = s.b[row.limb];
+  RH_FOR_EACH_PAIR(i, 0, n >> 1) {
+    const size_t o = row.ro + 2 * (size_t)i;
+    const ulonglong2 w = rh_ld2(pt + o, nt);
     ulonglong2 x[NC], z[NC];
 #pragma unroll
     for (int j = 0; j < NC; ++j) {
-      x[j] = bgv_ld(p.in[j] + o, nt);
-      if (ACC) z[j] = bgv_ld(p.out[j] + o, nt);
+      x[j] = rh_ld2(p.in[j] + o, nt);
+      if (ACC) z[j] = rh_ld2(p.out[j] + o, nt);
     }
     const u64 mx = mred(w.x, k, c.q, c.qinv), my = mred(w.y, k, c.q, c.qinv);         // pt * T * r0 * 2^64
 #pragma unroll
@@ -105,86 +93,50 @@ bgv_mul_plain_kernel(BgvComps p, const u64* pt, unsigned n, const LimbConsts* __
         if (has_r1) { z[j].x = mred(z[j].x, r1, c.q, c.qinv); z[j].y = mred(z[j].y, r1, c.q, c.qinv); }
         r.x = cred(z[j].x + r.x, c.q); r.y = cred(z[j].y + r.y, c.q);
       }
-      bgv_st(p.out[j] + o, r, nt);
+      rh_st2(p.out[j] + o, r, nt);
     }
   }
 }
 
-// MODE 0: out = r0 a + r1 b; 1: out = r0 a - r1 b; 2: out = r0 a; 3: out = r1 b; 4: out = -r1 b.  s.k = MForm(r0), s.r1 = MForm(r1).
+// MODE 0: out = r0 a + r1 b; 1: out = r0 a - r1 b; 2: out = r0 a; 3: out = r1 b; 4: out = -r1 b.  s.a = MForm(r0), s.b = MForm(r1).
 template <int MODE>
 __global__ void __launch_bounds__(256)
-bgv_axpby_kernel(const u64* a, const u64* b, u64* out, unsigned n, const LimbConsts* __restrict__ consts, int L, BgvScalars s, int nt) {
-  const u32 row = blockIdx.x, limb = row % (u32)L;
-  const LimbConsts c = consts[limb];
-  const u64 r0 = s.k[limb], r1 = s.r1[limb];
-  const size_t ro = (size_t)row * n;
+bgv_axpby_kernel(const u64* a, const u64* b, u64* out, unsigned n, const LimbConsts* __restrict__ consts, int L, RhScalars s, int nt) {
+  const StreamRow row(consts, L, n);
+  const LimbConsts& c = row.c;
+  const u64 r0 = s.a[row.limb], r1 = s.b[row.limb];
   auto one = [&](u64 x, u64 y) -> u64 {
     const u64 u = MODE <= 2 ? mred(x, r0, c.q, c.qinv) : 0;
     if (MODE == 2) return u;
     const u64 v = mred(y, r1, c.q, c.qinv);
     return (MODE == 0 || MODE == 3) ? cred(u + v, c.q) : cred(u + c.q - v, c.q);
   };
-  for (unsigned i = blockIdx.y * blockDim.x + threadIdx.x; i < (n >> 1); i += gridDim.y * blockDim.x) {
-    const size_t o = ro + 2 * (size_t)i;
+  RH_FOR_EACH_PAIR(i, 0, n >> 1) {
+    const size_t o = row.ro + 2 * (size_t)i;
     ulonglong2 x = make_ulonglong2(0, 0), y = x;
-    if (MODE <= 2) x = bgv_ld(a + o, nt);
-    if (MODE != 2) y = bgv_ld(b + o, nt);
-    bgv_st(out + o, make_ulonglong2(one(x.x, y.x), one(x.y, y.y)), nt);
+    if (MODE <= 2) x = rh_ld2(a + o, nt);
+    if (MODE != 2) y = rh_ld2(b + o, nt);
+    rh_st2(out + o, make_ulonglong2(one(x.x, y.x), one(x.y, y.y)), nt);
   }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
-static int bgv_launch_ok(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return rh_fail(RH_ERR_DEVICE, "%s launch failed: %s", what, hipGetErrorString(e));
-  return RH_OK;
-}
-
-// argument checks shared by the entry points
-static int bgv_args(rh_ring* r, int level, int npoly, const char* who) {
-  if (!r) return rh_fail(RH_ERR_ARG, "%s: null ring handle", who);
-  if (r->kind != RH_RING_STANDARD) return rh_fail(RH_ERR_ARG, "%s: BGV tensoring needs a standard ring (3N and conjugate-invariant rings are not supported)", who);
-  if (level < 0 || level >= r->L) return rh_fail(RH_ERR_ARG, "%s: level %d out of range [0,%d)", who, level, r->L);
-  if (level + 1 > RH_MAX_LIMBS) return rh_fail(RH_ERR_ARG, "%s: at most %d limbs", who, RH_MAX_LIMBS);
-  if (npoly < 0) return rh_fail(RH_ERR_ARG, "%s: npoly < 0", who);
-  if (r->N < 2 || (r->N & 1)) return rh_fail(RH_ERR_ARG, "%s: N must be even", who);
-  return 0;
-}
-
-// per-limb host scalars -> the by-value pack; every scalar must be a residue of its limb
-static int bgv_pack(const rh_ring* r, int level, const uint64_t* k, const uint64_t* r1, BgvScalars* s, const char* who) {
-  memset(s, 0, sizeof(*s));
-  for (int i = 0; i <= level; ++i) {
-    if ((k && k[i] >= r->moduli[i]) || (r1 && r1[i] >= r->moduli[i])) return rh_fail(RH_ERR_ARG, "%s: scalar of limb %d is not below its modulus", who, i);
-    if (k) s->k[i] = k[i];
-    if (r1) s->r1[i] = r1[i];
-  }
-  return 0;
-}
-
-struct BgvGrid { dim3 grid; int nt; };
-static BgvGrid bgv_grid(const rh_ring* r, unsigned rows) {
-  const unsigned n = (unsigned)r->N;
-  unsigned chunks = (n / 2 + 1023) / 1024; if (chunks < 1) chunks = 1; if (chunks > 64) chunks = 64;
-  return {dim3(rows, chunks), rh_nt_policy(r->nt_streams, (size_t)rows * n * 8, (size_t)512 << 20) ? 1 : 0};     // as rh_streams_beyond_cache
-}
+static const unsigned BGV_RINGS = 1u << RH_RING_STANDARD;
 
 extern "C" int rh_bgv_tensor(rh_ring* r, int level, const uint64_t* a0, const uint64_t* a1, const uint64_t* b0, const uint64_t* b1,
                              uint64_t* c0, uint64_t* c1, uint64_t* c2, int npoly, const uint64_t* k, const uint64_t* r1, int accumulate) {
-  if (int rc = bgv_args(r, level, npoly, "rh_bgv_tensor")) return rc;
+  if (int rc = rh_scheme_args(r, level, npoly, BGV_RINGS, 2, "rh_bgv_tensor")) return rc;
   if (!a0 || !a1 || !c0 || !c1 || !c2 || !k || ((b0 == nullptr) != (b1 == nullptr))) return rh_fail(RH_ERR_ARG, "rh_bgv_tensor: null argument");
   if (accumulate < 0 || accumulate > 2) return rh_fail(RH_ERR_ARG, "rh_bgv_tensor: accumulate must be 0 (overwrite), 1 (c0, c1, c2) or 2 (c0, c1; c2 overwritten)");
   if (r1 && !accumulate) return rh_fail(RH_ERR_ARG, "rh_bgv_tensor: an accumulator scalar without accumulate");
-  BgvScalars s;
-  if (int rc = bgv_pack(r, level, k, r1, &s, "rh_bgv_tensor")) return rc;
+  RhScalars s;
+  if (int rc = rh_pack_scalars(r, level, k, r1, false, &s, "rh_bgv_tensor")) return rc;
   const unsigned rows = (unsigned)npoly * (unsigned)(level + 1), n = (unsigned)r->N;
   if (rows == 0) return RH_OK;
-  (void)hipSetDevice(r->device);
-  (void)hipGetLastError();
   const bool square = !b0 || (b0 == a0 && b1 == a1);                 // op0 == op1 (:704): the same values with two operands less to read
-  const BgvGrid g = bgv_grid(r, rows);
+  const RhStreamGrid g = rh_stream_begin(r, rows);
   hipStream_t st = rh_stream(r);
   const LimbConsts* lc = r->d_consts;
   const int L = level + 1, h = r1 ? 1 : 0;
@@ -192,24 +144,21 @@ extern "C" int rh_bgv_tensor(rh_ring* r, int level, const uint64_t* a0, const ui
   if (square) { if (accumulate == 0) BGV_T(true, 0); else if (accumulate == 1) BGV_T(true, 1); else BGV_T(true, 2); }
   else { if (accumulate == 0) BGV_T(false, 0); else if (accumulate == 1) BGV_T(false, 1); else BGV_T(false, 2); }
 #undef BGV_T
-  return bgv_launch_ok("bgv_tensor_kernel");
+  return rh_launch_ok("bgv_tensor_kernel");
 }
 
 extern "C" int rh_bgv_mul_plain(rh_ring* r, int level, const uint64_t* ct0, const uint64_t* ct1, const uint64_t* ct2, const uint64_t* pt,
                                 uint64_t* out0, uint64_t* out1, uint64_t* out2, int npoly, const uint64_t* k, const uint64_t* r1, int accumulate) {
-  if (int rc = bgv_args(r, level, npoly, "rh_bgv_mul_plain")) return rc;
-  if (!ct0 || !pt || !out0 || !k) return rh_fail(RH_ERR_ARG, "rh_bgv_mul_plain: null argument");
-  if ((ct2 && !ct1) || (ct1 != nullptr) != (out1 != nullptr) || (ct2 != nullptr) != (out2 != nullptr))
-    return rh_fail(RH_ERR_ARG, "rh_bgv_mul_plain: components 1 and 2 need an input and an output each, and component 2 needs component 1");
+  if (int rc = rh_scheme_args(r, level, npoly, BGV_RINGS, 2, "rh_bgv_mul_plain")) return rc;
+  if (!pt || !k) return rh_fail(RH_ERR_ARG, "rh_bgv_mul_plain: null argument");
+  if (int rc = rh_comps3(ct0, ct1, ct2, out0, out1, out2, "rh_bgv_mul_plain")) return rc;
   if (accumulate < 0 || accumulate > 1) return rh_fail(RH_ERR_ARG, "rh_bgv_mul_plain: accumulate must be 0 or 1");
   if (r1 && !accumulate) return rh_fail(RH_ERR_ARG, "rh_bgv_mul_plain: an accumulator scalar without accumulate");
-  BgvScalars s;
-  if (int rc = bgv_pack(r, level, k, r1, &s, "rh_bgv_mul_plain")) return rc;
+  RhScalars s;
+  if (int rc = rh_pack_scalars(r, level, k, r1, false, &s, "rh_bgv_mul_plain")) return rc;
   const unsigned rows = (unsigned)npoly * (unsigned)(level + 1), n = (unsigned)r->N;
   if (rows == 0) return RH_OK;
-  (void)hipSetDevice(r->device);
-  (void)hipGetLastError();
-  const BgvGrid g = bgv_grid(r, rows);
+  const RhStreamGrid g = rh_stream_begin(r, rows);
   hipStream_t st = rh_stream(r);
   const BgvComps p{{ct0, ct1, ct2}, {out0, out1, out2}};
   const int nc = ct2 ? 3 : ct1 ? 2 : 1, L = level + 1, h = r1 ? 1 : 0;
@@ -217,21 +166,19 @@ extern "C" int rh_bgv_mul_plain(rh_ring* r, int level, const uint64_t* ct0, cons
   if (accumulate) { if (nc == 1) BGV_P(1, true); else if (nc == 2) BGV_P(2, true); else BGV_P(3, true); }
   else { if (nc == 1) BGV_P(1, false); else if (nc == 2) BGV_P(2, false); else BGV_P(3, false); }
 #undef BGV_P
-  return bgv_launch_ok("bgv_mul_plain_kernel");
+  return rh_launch_ok("bgv_mul_plain_kernel");
 }
 
 extern "C" int rh_bgv_axpby(rh_ring* r, int level, const uint64_t* a, const uint64_t* b, uint64_t* out, int npoly, const uint64_t* r0,
                             const uint64_t* r1, int sub) {
-  if (int rc = bgv_args(r, level, npoly, "rh_bgv_axpby")) return rc;
+  if (int rc = rh_scheme_args(r, level, npoly, BGV_RINGS, 2, "rh_bgv_axpby")) return rc;
   if (!out || (!a && !b)) return rh_fail(RH_ERR_ARG, "rh_bgv_axpby: null argument");
   if ((a != nullptr) != (r0 != nullptr) || (b != nullptr) != (r1 != nullptr)) return rh_fail(RH_ERR_ARG, "rh_bgv_axpby: every operand comes with its scalar and every scalar with its operand");
-  BgvScalars s;
-  if (int rc = bgv_pack(r, level, r0, r1, &s, "rh_bgv_axpby")) return rc;
+  RhScalars s;
+  if (int rc = rh_pack_scalars(r, level, r0, r1, false, &s, "rh_bgv_axpby")) return rc;
   const unsigned rows = (unsigned)npoly * (unsigned)(level + 1), n = (unsigned)r->N;
   if (rows == 0) return RH_OK;
-  (void)hipSetDevice(r->device);
-  (void)hipGetLastError();
-  const BgvGrid g = bgv_grid(r, rows);
+  const RhStreamGrid g = rh_stream_begin(r, rows);
   hipStream_t st = rh_stream(r);
   const int L = level + 1;
 #define BGV_A(MODE) bgv_axpby_kernel<MODE><<<g.grid, 256, 0, st>>>(a, b, out, n, r->d_consts, L, s, g.nt)
@@ -240,5 +187,5 @@ extern "C" int rh_bgv_axpby(rh_ring* r, int level, const uint64_t* a, const uint
   else if (sub) BGV_A(4);
   else BGV_A(3);
 #undef BGV_A
-  return bgv_launch_ok("bgv_axpby_kernel");
+  return rh_launch_ok("bgv_axpby_kernel");
 }

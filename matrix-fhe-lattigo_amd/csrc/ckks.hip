@@ -14,37 +14,26 @@
 //                               scale, Add / Sub on the shared components, the rest copied (:422-430) and negated under Sub (:173-177).
 //
 // Each thread reads all of its operands before it writes, so any output may be any input.  Bandwidth-bound, no LDS; 16-byte loads and
-// stores, rows (one limb of one poly) on blockIdx.x so the per-limb constants are wave-uniform, non-temporal beyond the Infinity Cache, as
-// tensor_degree1_kernel (engine.hip) and the BGV kernels (bgv.hip).
+// stores, rows (one limb of one poly) on blockIdx.x so the per-limb constants are wave-uniform, non-temporal beyond the Infinity Cache: the
+// scaffold of stream_kernels.hip.hpp, as the BGV kernels (bgv.hip).
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include "engine_internal.hpp"
+#include "stream_kernels.hip.hpp"
 
-struct CkksScalars { u64 a[RH_MAX_LIMBS]; u64 b[RH_MAX_LIMBS]; };      // per-limb constants by value (1 KiB of kernel arguments)
 struct CkksComps { const u64* in[3]; const u64* in2[3]; u64* out[3]; };
 
-typedef u64 ckks_u64x2_t __attribute__((ext_vector_type(2)));
-RH_DEV ulonglong2 ckks_ld(const u64* p, int nt) {
-  if (!nt) return *reinterpret_cast<const ulonglong2*>(p);
-  const ckks_u64x2_t v = __builtin_nontemporal_load(reinterpret_cast<const ckks_u64x2_t*>(p));
-  return make_ulonglong2(v.x, v.y);
-}
-RH_DEV void ckks_st(u64* p, const ulonglong2& w, int nt) {
-  if (nt) { ckks_u64x2_t v; v.x = w.x; v.y = w.y; __builtin_nontemporal_store(v, reinterpret_cast<ckks_u64x2_t*>(p)); }
-  else *reinterpret_cast<ulonglong2*>(p) = w;
-}
-
 // ACC 0: c0, c1, c2 written; 1: all three read and added to; 2: c0, c1 read and added to, c2 written (the relin form :1150).
+// MFORM false: op0 comes in Montgomery form already (matrix_ckks.Evaluator.Mul, evaluator.go:166-173).
 // grid: (npoly * L, chunks); L = level + 1 rows per poly.
-template <bool SQUARE, int ACC>
+template <bool SQUARE, int ACC, bool MFORM>
 __global__ void __launch_bounds__(256)
 ckks_tensor_kernel(const u64* a0, const u64* a1, const u64* b0, const u64* b1, u64* c0, u64* c1, u64* c2, unsigned n,
                    const LimbConsts* __restrict__ consts, int L, int nt) {
-  const u32 row = blockIdx.x, limb = row % (u32)L;
-  const LimbConsts c = consts[limb];
-  const size_t ro = (size_t)row * n;
+  const StreamRow row(consts, L, n);
+  const LimbConsts& c = row.c;
   auto one = [&](u64 x0, u64 x1, u64 y0, u64 y1, u64 z0, u64 z1, u64 z2, u64& o0, u64& o1, u64& o2) {
-    const u64 m0 = mform(x0, c.q, c.bred0, c.bred1), m1 = mform(x1, c.q, c.bred0, c.bred1);   // (:821-822 / :1135-1136)
+    const u64 m0 = MFORM ? mform(x0, c.q, c.bred0, c.bred1) : x0, m1 = MFORM ? mform(x1, c.q, c.bred0, c.bred1) : x1;   // (:821-822 / :1135-1136)
     if (SQUARE) { y0 = x0; y1 = x1; }
     const u64 p0 = mred(m0, y0, c.q, c.qinv), p2 = mred(m1, y1, c.q, c.qinv), p01 = mred(m0, y1, c.q, c.qinv);
     if (ACC) {
@@ -56,17 +45,17 @@ ckks_tensor_kernel(const u64* a0, const u64* a1, const u64* b0, const u64* b1, u
       o1 = SQUARE ? cred(p01 + p01, c.q) : cred(p01 + mred(m1, y0, c.q, c.qinv), c.q);         // (:827-828 / :833-834)
     }
   };
-  for (unsigned i = blockIdx.y * blockDim.x + threadIdx.x; i < (n >> 1); i += gridDim.y * blockDim.x) {
-    const size_t o = ro + 2 * (size_t)i;
-    const ulonglong2 x0 = ckks_ld(a0 + o, nt), x1 = ckks_ld(a1 + o, nt);
+  RH_FOR_EACH_PAIR(i, 0, n >> 1) {
+    const size_t o = row.ro + 2 * (size_t)i;
+    const ulonglong2 x0 = rh_ld2(a0 + o, nt), x1 = rh_ld2(a1 + o, nt);
     ulonglong2 y0 = make_ulonglong2(0, 0), y1 = y0, z0 = y0, z1 = y0, z2 = y0;
-    if (!SQUARE) { y0 = ckks_ld(b0 + o, nt); y1 = ckks_ld(b1 + o, nt); }
-    if (ACC) { z0 = ckks_ld(c0 + o, nt); z1 = ckks_ld(c1 + o, nt); }
-    if (ACC == 1) z2 = ckks_ld(c2 + o, nt);
+    if (!SQUARE) { y0 = rh_ld2(b0 + o, nt); y1 = rh_ld2(b1 + o, nt); }
+    if (ACC) { z0 = rh_ld2(c0 + o, nt); z1 = rh_ld2(c1 + o, nt); }
+    if (ACC == 1) z2 = rh_ld2(c2 + o, nt);
     u64 lo0, lo1, lo2, hi0, hi1, hi2;
     one(x0.x, x1.x, y0.x, y1.x, z0.x, z1.x, z2.x, lo0, lo1, lo2);
     one(x0.y, x1.y, y0.y, y1.y, z0.y, z1.y, z2.y, hi0, hi1, hi2);
-    ckks_st(c0 + o, make_ulonglong2(lo0, hi0), nt); ckks_st(c1 + o, make_ulonglong2(lo1, hi1), nt); ckks_st(c2 + o, make_ulonglong2(lo2, hi2), nt);
+    rh_st2(c0 + o, make_ulonglong2(lo0, hi0), nt); rh_st2(c1 + o, make_ulonglong2(lo1, hi1), nt); rh_st2(c2 + o, make_ulonglong2(lo2, hi2), nt);
   }
 }
 
@@ -74,24 +63,23 @@ ckks_tensor_kernel(const u64* a0, const u64* a1, const u64* b0, const u64* b1, u
 template <int NC, bool ACC>
 __global__ void __launch_bounds__(256)
 ckks_mul_plain_kernel(CkksComps p, const u64* pt, unsigned n, const LimbConsts* __restrict__ consts, int L, int nt) {
-  const u32 row = blockIdx.x, limb = row % (u32)L;
-  const LimbConsts c = consts[limb];
-  const size_t ro = (size_t)row * n;
-  for (unsigned i = blockIdx.y * blockDim.x + threadIdx.x; i < (n >> 1); i += gridDim.y * blockDim.x) {
-    const size_t o = ro + 2 * (size_t)i;
-    const ulonglong2 w = ckks_ld(pt + o, nt);
+  const StreamRow row(consts, L, n);
+  const LimbConsts& c = row.c;
+  RH_FOR_EACH_PAIR(i, 0, n >> 1) {
+    const size_t o = row.ro + 2 * (size_t)i;
+    const ulonglong2 w = rh_ld2(pt + o, nt);
     ulonglong2 x[NC], z[NC];
 #pragma unroll
     for (int j = 0; j < NC; ++j) {
-      x[j] = ckks_ld(p.in[j] + o, nt);
-      if (ACC) z[j] = ckks_ld(p.out[j] + o, nt);
+      x[j] = rh_ld2(p.in[j] + o, nt);
+      if (ACC) z[j] = rh_ld2(p.out[j] + o, nt);
     }
     const u64 mx = mform(w.x, c.q, c.bred0, c.bred1), my = mform(w.y, c.q, c.bred0, c.bred1);   // (:864 / :869 / :1171)
 #pragma unroll
     for (int j = 0; j < NC; ++j) {
       ulonglong2 r = make_ulonglong2(mred(x[j].x, mx, c.q, c.qinv), mred(x[j].y, my, c.q, c.qinv));
       if (ACC) { r.x = cred(z[j].x + r.x, c.q); r.y = cred(z[j].y + r.y, c.q); }
-      ckks_st(p.out[j] + o, r, nt);
+      rh_st2(p.out[j] + o, r, nt);
     }
   }
 }
@@ -100,11 +88,10 @@ ckks_mul_plain_kernel(CkksComps p, const u64* pt, unsigned n, const LimbConsts* 
 // below `half` (coefficients [0, N/2)) and s.b[limb] above; for OP >= 2 the host has put the scalars in Montgomery form.
 template <int OP, int NC>
 __global__ void __launch_bounds__(256)
-ckks_scalar_kernel(CkksComps p, unsigned n, const LimbConsts* __restrict__ consts, int L, CkksScalars s, int nt) {
-  const u32 row = blockIdx.x, limb = row % (u32)L;
-  const LimbConsts c = consts[limb];
-  const u64 sa = s.a[limb], sb = s.b[limb];
-  const size_t ro = (size_t)row * n;
+ckks_scalar_kernel(CkksComps p, unsigned n, const LimbConsts* __restrict__ consts, int L, RhScalars s, int nt) {
+  const StreamRow row(consts, L, n);
+  const LimbConsts& c = row.c;
+  const u64 sa = s.a[row.limb], sb = s.b[row.limb];
   const unsigned half = n >> 2;
   auto one = [&](u64 x, u64 z, u64 sc) -> u64 {
     if (OP == 0) return cred(x + sc, c.q);
@@ -112,17 +99,17 @@ ckks_scalar_kernel(CkksComps p, unsigned n, const LimbConsts* __restrict__ const
     const u64 m = mred(x, sc, c.q, c.qinv);
     return OP == 2 ? m : cred(z + m, c.q);
   };
-  for (unsigned i = blockIdx.y * blockDim.x + threadIdx.x; i < (n >> 1); i += gridDim.y * blockDim.x) {
-    const size_t o = ro + 2 * (size_t)i;
+  RH_FOR_EACH_PAIR(i, 0, n >> 1) {
+    const size_t o = row.ro + 2 * (size_t)i;
     const u64 sc = i < half ? sa : sb;
     ulonglong2 x[NC], z[NC];
 #pragma unroll
     for (int j = 0; j < NC; ++j) {
-      x[j] = ckks_ld(p.in[j] + o, nt);
-      z[j] = OP == 3 ? ckks_ld(p.out[j] + o, nt) : make_ulonglong2(0, 0);
+      x[j] = rh_ld2(p.in[j] + o, nt);
+      z[j] = OP == 3 ? rh_ld2(p.out[j] + o, nt) : make_ulonglong2(0, 0);
     }
 #pragma unroll
-    for (int j = 0; j < NC; ++j) ckks_st(p.out[j] + o, make_ulonglong2(one(x[j].x, z[j].x, sc), one(x[j].y, z[j].y, sc)), nt);
+    for (int j = 0; j < NC; ++j) rh_st2(p.out[j] + o, make_ulonglong2(one(x[j].x, z[j].x, sc), one(x[j].y, z[j].y, sc)), nt);
   }
 }
 
@@ -130,12 +117,11 @@ ckks_scalar_kernel(CkksComps p, unsigned n, const LimbConsts* __restrict__ const
 // MForm(ratio) (has_ratio 0: none is).  With a alone: out = a'.  With b alone: out = b', and q - b' under Sub -- ring.Neg, which like the
 // reference's maps 0 to q_i (ring/vec_ops.go:103).
 __global__ void __launch_bounds__(256)
-ckks_scale_then_add_kernel(CkksComps p, unsigned n, const LimbConsts* __restrict__ consts, int L, CkksScalars s, int has_ratio, int sub,
+ckks_scale_then_add_kernel(CkksComps p, unsigned n, const LimbConsts* __restrict__ consts, int L, RhScalars s, int has_ratio, int sub,
                            int scaled_b, int nt) {
-  const u32 row = blockIdx.x, limb = row % (u32)L;
-  const LimbConsts c = consts[limb];
-  const u64 k = s.a[limb];
-  const size_t ro = (size_t)row * n;
+  const StreamRow row(consts, L, n);
+  const LimbConsts& c = row.c;
+  const u64 k = s.a[row.limb];
   const bool sa = has_ratio && !scaled_b, sb = has_ratio && scaled_b;
   auto one = [&](u64 x, u64 y, bool ha, bool hb) -> u64 {
     if (ha && sa) x = mred(x, k, c.q, c.qinv);
@@ -144,19 +130,19 @@ ckks_scale_then_add_kernel(CkksComps p, unsigned n, const LimbConsts* __restrict
     if (ha) return x;
     return sub ? c.q - y : y;
   };
-  for (unsigned i = blockIdx.y * blockDim.x + threadIdx.x; i < (n >> 1); i += gridDim.y * blockDim.x) {
-    const size_t o = ro + 2 * (size_t)i;
+  RH_FOR_EACH_PAIR(i, 0, n >> 1) {
+    const size_t o = row.ro + 2 * (size_t)i;
     ulonglong2 x[3], y[3];
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-      x[j] = p.in[j] ? ckks_ld(p.in[j] + o, nt) : make_ulonglong2(0, 0);
-      y[j] = p.in2[j] ? ckks_ld(p.in2[j] + o, nt) : make_ulonglong2(0, 0);
+      x[j] = p.in[j] ? rh_ld2(p.in[j] + o, nt) : make_ulonglong2(0, 0);
+      y[j] = p.in2[j] ? rh_ld2(p.in2[j] + o, nt) : make_ulonglong2(0, 0);
     }
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
       if (!p.out[j]) continue;
       const bool ha = p.in[j] != nullptr, hb = p.in2[j] != nullptr;
-      ckks_st(p.out[j] + o, make_ulonglong2(one(x[j].x, y[j].x, ha, hb), one(x[j].y, y[j].y, ha, hb)), nt);
+      rh_st2(p.out[j] + o, make_ulonglong2(one(x[j].x, y[j].x, ha, hb), one(x[j].y, y[j].y, ha, hb)), nt);
     }
   }
 }
@@ -164,75 +150,55 @@ ckks_scale_then_add_kernel(CkksComps p, unsigned n, const LimbConsts* __restrict
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
-static int ckks_launch_ok(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return rh_fail(RH_ERR_DEVICE, "%s launch failed: %s", what, hipGetErrorString(e));
-  return RH_OK;
-}
+static const unsigned CKKS_RINGS = 1u << RH_RING_STANDARD | 1u << RH_RING_CI;    // the CKKS evaluator's rings; N a multiple of 4 (two scalar halves of pairs)
 
-// argument checks shared by the entry points
-static int ckks_args(rh_ring* r, int level, int npoly, const char* who) {
-  if (!r) return rh_fail(RH_ERR_ARG, "%s: null ring handle", who);
-  if (r->kind != RH_RING_STANDARD && r->kind != RH_RING_CI)
-    return rh_fail(RH_ERR_ARG, "%s: the CKKS evaluator needs a standard or conjugate-invariant power-of-two ring (3N rings are not supported)", who);
-  if (level < 0 || level >= r->L) return rh_fail(RH_ERR_ARG, "%s: level %d out of range [0,%d)", who, level, r->L);
-  if (level + 1 > RH_MAX_LIMBS) return rh_fail(RH_ERR_ARG, "%s: at most %d limbs", who, RH_MAX_LIMBS);
-  if (npoly < 0) return rh_fail(RH_ERR_ARG, "%s: npoly < 0", who);
-  if (r->N < 4 || (r->N & 3)) return rh_fail(RH_ERR_ARG, "%s: N must be a multiple of 4", who);
-  return 0;
-}
-
-// 1, 2 or 3 components, each with an input and an output; trailing NULLs mean fewer
-static int ckks_comps(const uint64_t* in0, const uint64_t* in1, const uint64_t* in2, uint64_t* out0, uint64_t* out1, uint64_t* out2, const char* who) {
-  if (!in0 || !out0) return rh_fail(RH_ERR_ARG, "%s: null argument", who);
-  if ((in2 && !in1) || (in1 != nullptr) != (out1 != nullptr) || (in2 != nullptr) != (out2 != nullptr))
-    return rh_fail(RH_ERR_ARG, "%s: components 1 and 2 need an input and an output each, and component 2 needs component 1", who);
-  return 0;
-}
-
-struct CkksGrid { dim3 grid; int nt; };
-static CkksGrid ckks_grid(const rh_ring* r, unsigned rows) {
-  const unsigned n = (unsigned)r->N;
-  unsigned chunks = (n / 2 + 1023) / 1024; if (chunks < 1) chunks = 1; if (chunks > 64) chunks = 64;
-  return {dim3(rows, chunks), rh_nt_policy(r->nt_streams, (size_t)rows * n * 8, (size_t)512 << 20) ? 1 : 0};     // as rh_streams_beyond_cache
+static int tensor_launch(rh_ring* r, int level, const u64* a0, const u64* a1, const u64* b0, const u64* b1, u64* c0, u64* c1, u64* c2, int npoly,
+                         int accumulate, bool square, bool mform_first, const char* what = "ckks_tensor_kernel") {
+  const unsigned rows = (unsigned)npoly * (unsigned)(level + 1), n = (unsigned)r->N;
+  if (rows == 0) return RH_OK;
+  const RhStreamGrid g = rh_stream_begin(r, rows);
+  hipStream_t st = rh_stream(r);
+  const LimbConsts* lc = r->d_consts;
+  const int L = level + 1;
+#define CKKS_T(SQ, ACC, MF) ckks_tensor_kernel<SQ, ACC, MF><<<g.grid, 256, 0, st>>>(a0, a1, b0, b1, c0, c1, c2, n, lc, L, g.nt)
+  if (!mform_first) CKKS_T(false, 0, false);
+  else if (square) CKKS_T(true, 0, true);
+  else if (accumulate == 0) CKKS_T(false, 0, true);
+  else if (accumulate == 1) CKKS_T(false, 1, true);
+  else CKKS_T(false, 2, true);
+#undef CKKS_T
+  return rh_launch_ok(what);
 }
 
 extern "C" int rh_ckks_tensor(rh_ring* r, int level, const uint64_t* a0, const uint64_t* a1, const uint64_t* b0, const uint64_t* b1,
                               uint64_t* c0, uint64_t* c1, uint64_t* c2, int npoly, int accumulate, int square) {
-  if (int rc = ckks_args(r, level, npoly, "rh_ckks_tensor")) return rc;
+  if (int rc = rh_scheme_args(r, level, npoly, CKKS_RINGS, 4, "rh_ckks_tensor")) return rc;
   if (!a0 || !a1 || !c0 || !c1 || !c2 || ((b0 == nullptr) != (b1 == nullptr))) return rh_fail(RH_ERR_ARG, "rh_ckks_tensor: null argument");
   if (accumulate < 0 || accumulate > 2) return rh_fail(RH_ERR_ARG, "rh_ckks_tensor: accumulate must be 0 (overwrite), 1 (c0, c1, c2) or 2 (c0, c1; c2 overwritten)");
   if (square && accumulate) return rh_fail(RH_ERR_ARG, "rh_ckks_tensor: the squaring case comes without accumulate");
   if (square && b0 && (b0 != a0 || b1 != a1)) return rh_fail(RH_ERR_ARG, "rh_ckks_tensor: the squaring case takes b = NULL or b == a");
   if (!square && !b0) return rh_fail(RH_ERR_ARG, "rh_ckks_tensor: null argument");
-  const unsigned rows = (unsigned)npoly * (unsigned)(level + 1), n = (unsigned)r->N;
-  if (rows == 0) return RH_OK;
-  (void)hipSetDevice(r->device);
-  (void)hipGetLastError();
-  const CkksGrid g = ckks_grid(r, rows);
-  hipStream_t st = rh_stream(r);
-  const LimbConsts* lc = r->d_consts;
-  const int L = level + 1;
-#define CKKS_T(SQ, ACC) ckks_tensor_kernel<SQ, ACC><<<g.grid, 256, 0, st>>>(a0, a1, b0, b1, c0, c1, c2, n, lc, L, g.nt)
-  if (square) CKKS_T(true, 0);
-  else if (accumulate == 0) CKKS_T(false, 0);
-  else if (accumulate == 1) CKKS_T(false, 1);
-  else CKKS_T(false, 2);
-#undef CKKS_T
-  return ckks_launch_ok("ckks_tensor_kernel");
+  return tensor_launch(r, level, a0, a1, b0, b1, c0, c1, c2, npoly, accumulate, square != 0, true);
+}
+
+// The degree-1 x degree-1 tensoring alone (ringhip.h), on any ring kind: the 3N ring of matrix_ckks.Evaluator.Mul calls it with
+// mform_first = 0.  With mform_first = 1 it is rh_ckks_tensor(accumulate 0, square 0).
+extern "C" int rh_ring_tensor_degree1(rh_ring* r, const uint64_t* a0, const uint64_t* a1, const uint64_t* b0, const uint64_t* b1,
+                                      uint64_t* c0, uint64_t* c1, uint64_t* c2, int npoly, int level, int mform_first) {
+  if (!r || !a0 || !a1 || !b0 || !b1 || !c0 || !c1 || !c2) return rh_fail(RH_ERR_ARG, "tensor_degree1: null argument");
+  if (int rc = rh_scheme_args(r, level, npoly, ~0u, 2, "tensor_degree1")) return rc;
+  return tensor_launch(r, level, a0, a1, b0, b1, c0, c1, c2, npoly, 0, false, mform_first != 0, "tensor_degree1");
 }
 
 extern "C" int rh_ckks_mul_plain(rh_ring* r, int level, const uint64_t* ct0, const uint64_t* ct1, const uint64_t* ct2, const uint64_t* pt,
                                  uint64_t* out0, uint64_t* out1, uint64_t* out2, int npoly, int accumulate) {
-  if (int rc = ckks_args(r, level, npoly, "rh_ckks_mul_plain")) return rc;
+  if (int rc = rh_scheme_args(r, level, npoly, CKKS_RINGS, 4, "rh_ckks_mul_plain")) return rc;
   if (!pt) return rh_fail(RH_ERR_ARG, "rh_ckks_mul_plain: null argument");
-  if (int rc = ckks_comps(ct0, ct1, ct2, out0, out1, out2, "rh_ckks_mul_plain")) return rc;
+  if (int rc = rh_comps3(ct0, ct1, ct2, out0, out1, out2, "rh_ckks_mul_plain")) return rc;
   if (accumulate < 0 || accumulate > 1) return rh_fail(RH_ERR_ARG, "rh_ckks_mul_plain: accumulate must be 0 or 1");
   const unsigned rows = (unsigned)npoly * (unsigned)(level + 1), n = (unsigned)r->N;
   if (rows == 0) return RH_OK;
-  (void)hipSetDevice(r->device);
-  (void)hipGetLastError();
-  const CkksGrid g = ckks_grid(r, rows);
+  const RhStreamGrid g = rh_stream_begin(r, rows);
   hipStream_t st = rh_stream(r);
   const CkksComps p{{ct0, ct1, ct2}, {nullptr, nullptr, nullptr}, {out0, out1, out2}};
   const int nc = ct2 ? 3 : ct1 ? 2 : 1, L = level + 1;
@@ -240,29 +206,20 @@ extern "C" int rh_ckks_mul_plain(rh_ring* r, int level, const uint64_t* ct0, con
   if (accumulate) { if (nc == 1) CKKS_P(1, true); else if (nc == 2) CKKS_P(2, true); else CKKS_P(3, true); }
   else { if (nc == 1) CKKS_P(1, false); else if (nc == 2) CKKS_P(2, false); else CKKS_P(3, false); }
 #undef CKKS_P
-  return ckks_launch_ok("ckks_mul_plain_kernel");
+  return rh_launch_ok("ckks_mul_plain_kernel");
 }
 
 extern "C" int rh_ckks_scalar(rh_ring* r, int level, int op, const uint64_t* in0, const uint64_t* in1, const uint64_t* in2,
                               uint64_t* out0, uint64_t* out1, uint64_t* out2, int npoly, const uint64_t* s0, const uint64_t* s1) {
-  if (int rc = ckks_args(r, level, npoly, "rh_ckks_scalar")) return rc;
+  if (int rc = rh_scheme_args(r, level, npoly, CKKS_RINGS, 4, "rh_ckks_scalar")) return rc;
   if (!s0 || !s1) return rh_fail(RH_ERR_ARG, "rh_ckks_scalar: null argument");
-  if (int rc = ckks_comps(in0, in1, in2, out0, out1, out2, "rh_ckks_scalar")) return rc;
+  if (int rc = rh_comps3(in0, in1, in2, out0, out1, out2, "rh_ckks_scalar")) return rc;
   if (op < RH_CKKS_ADD_SCALAR || op > RH_CKKS_MUL_SCALAR_THEN_ADD) return rh_fail(RH_ERR_ARG, "rh_ckks_scalar: op must be 0 (add), 1 (sub), 2 (mul) or 3 (mul then add)");
-  CkksScalars s;
-  memset(&s, 0, sizeof(s));
-  for (int i = 0; i <= level; ++i) {
-    const uint64_t q = r->moduli[i];
-    if (s0[i] >= q || s1[i] >= q) return rh_fail(RH_ERR_ARG, "rh_ckks_scalar: scalar of limb %d is not below its modulus", i);
-    const bool mul = op >= RH_CKKS_MUL_SCALAR;                          // MulDoubleRNSScalar(ThenAdd): MForm(scalar) (ring/operations.go:250-266)
-    s.a[i] = mul ? (uint64_t)((((unsigned __int128)s0[i]) << 64) % q) : s0[i];
-    s.b[i] = mul ? (uint64_t)((((unsigned __int128)s1[i]) << 64) % q) : s1[i];
-  }
+  RhScalars s;                                                          // MulDoubleRNSScalar(ThenAdd): MForm(scalar) (ring/operations.go:250-266)
+  if (int rc = rh_pack_scalars(r, level, s0, s1, op >= RH_CKKS_MUL_SCALAR, &s, "rh_ckks_scalar")) return rc;
   const unsigned rows = (unsigned)npoly * (unsigned)(level + 1), n = (unsigned)r->N;
   if (rows == 0) return RH_OK;
-  (void)hipSetDevice(r->device);
-  (void)hipGetLastError();
-  const CkksGrid g = ckks_grid(r, rows);
+  const RhStreamGrid g = rh_stream_begin(r, rows);
   hipStream_t st = rh_stream(r);
   const CkksComps p{{in0, in1, in2}, {nullptr, nullptr, nullptr}, {out0, out1, out2}};
   const int nc = in2 ? 3 : in1 ? 2 : 1, L = level + 1;
@@ -274,30 +231,23 @@ extern "C" int rh_ckks_scalar(rh_ring* r, int level, int op, const uint64_t* in0
   else CKKS_SN(3);
 #undef CKKS_SN
 #undef CKKS_S
-  return ckks_launch_ok("ckks_scalar_kernel");
+  return rh_launch_ok("ckks_scalar_kernel");
 }
 
 extern "C" int rh_ckks_scale_then_add(rh_ring* r, int level, const uint64_t* a0, const uint64_t* a1, const uint64_t* a2, const uint64_t* b0,
                                       const uint64_t* b1, const uint64_t* b2, uint64_t* out0, uint64_t* out1, uint64_t* out2, int npoly,
                                       const uint64_t* ratio, int sub, int scaled_is_b) {
-  if (int rc = ckks_args(r, level, npoly, "rh_ckks_scale_then_add")) return rc;
+  if (int rc = rh_scheme_args(r, level, npoly, CKKS_RINGS, 4, "rh_ckks_scale_then_add")) return rc;
   if (!a0 || !b0 || !out0) return rh_fail(RH_ERR_ARG, "rh_ckks_scale_then_add: null argument");
   if ((a2 && !a1) || (b2 && !b1) || (out2 && !out1)) return rh_fail(RH_ERR_ARG, "rh_ckks_scale_then_add: component 2 needs component 1");
   if ((out1 != nullptr) != (a1 || b1) || (out2 != nullptr) != (a2 || b2))
     return rh_fail(RH_ERR_ARG, "rh_ckks_scale_then_add: the output has the components of the larger operand, no more and no fewer");
-  CkksScalars s;
-  memset(&s, 0, sizeof(s));
-  for (int i = 0; ratio && i <= level; ++i) {
-    const uint64_t q = r->moduli[i];
-    if (ratio[i] >= q) return rh_fail(RH_ERR_ARG, "rh_ckks_scale_then_add: ratio of limb %d is not below its modulus", i);
-    s.a[i] = (uint64_t)((((unsigned __int128)ratio[i]) << 64) % q);       // Mul(ct, ratioInt, tmp) -> MulDoubleRNSScalar: MForm(ratio mod q_i)
-  }
+  RhScalars s;                                                          // Mul(ct, ratioInt, tmp) -> MulDoubleRNSScalar: MForm(ratio mod q_i)
+  if (int rc = rh_pack_scalars(r, level, ratio, nullptr, true, &s, "rh_ckks_scale_then_add", "ratio")) return rc;
   const unsigned rows = (unsigned)npoly * (unsigned)(level + 1), n = (unsigned)r->N;
   if (rows == 0) return RH_OK;
-  (void)hipSetDevice(r->device);
-  (void)hipGetLastError();
-  const CkksGrid g = ckks_grid(r, rows);
+  const RhStreamGrid g = rh_stream_begin(r, rows);
   const CkksComps p{{a0, a1, a2}, {b0, b1, b2}, {out0, out1, out2}};
   ckks_scale_then_add_kernel<<<g.grid, 256, 0, rh_stream(r)>>>(p, n, r->d_consts, level + 1, s, ratio ? 1 : 0, sub ? 1 : 0, scaled_is_b ? 1 : 0, g.nt);
-  return ckks_launch_ok("ckks_scale_then_add_kernel");
+  return rh_launch_ok("ckks_scale_then_add_kernel");
 }

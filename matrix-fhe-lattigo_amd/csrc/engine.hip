@@ -13,6 +13,7 @@
 #include "hostmath.hpp"
 #include "ntt_kernels.hip.hpp"
 #include "vec_kernels.hip.hpp"
+#include "stream_kernels.hip.hpp"
 #include "ntt_kernels_asm.hip.hpp"
 #include "ntt3n_kernels_asm.hip.hpp"
 #include "engine_internal.hpp"
@@ -312,12 +313,48 @@ extern "C" int rh_dev_download(rh_ring* r, uint64_t* dst, const uint64_t* src, s
   return RH_OK;
 }
 
-// ------------------------------------------------------------------------------------------------ NTT launches
-static int check_launch(const char* what) {
+// ------------------------------------------------------------------------------------------------ launch plumbing (engine_internal.hpp)
+int rh_launch_ok(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return rh_fail(RH_ERR_DEVICE, "%s launch failed: %s", what, hipGetErrorString(e));
   return RH_OK;
 }
+unsigned rh_stream_chunks(const rh_ring* r) {
+  unsigned chunks = ((unsigned)r->N / 2 + 1023) / 1024; if (chunks < 1) chunks = 1; if (chunks > 64) chunks = 64;
+  return chunks;
+}
+RhStreamGrid rh_stream_grid(const rh_ring* r, unsigned rows) {
+  return {dim3(rows, rh_stream_chunks(r)), rh_nt_policy(r->nt_streams, (size_t)rows * (size_t)r->N * 8, (size_t)512 << 20) ? 1 : 0};
+}
+int rh_scheme_args(const rh_ring* r, int level, int npoly, unsigned kinds, int n_multiple, const char* who) {
+  if (!r) return rh_fail(RH_ERR_ARG, "%s: null ring handle", who);
+  if (!(kinds >> r->kind & 1))
+    return kinds >> RH_RING_CI & 1 ? rh_fail(RH_ERR_ARG, "%s: the CKKS evaluator needs a standard or conjugate-invariant power-of-two ring (3N rings are not supported)", who)
+                                   : rh_fail(RH_ERR_ARG, "%s: BGV tensoring needs a standard ring (3N and conjugate-invariant rings are not supported)", who);
+  if (level < 0 || level >= r->L) return rh_fail(RH_ERR_ARG, "%s: level %d out of range [0,%d)", who, level, r->L);
+  if (level + 1 > RH_MAX_LIMBS) return rh_fail(RH_ERR_ARG, "%s: at most %d limbs", who, RH_MAX_LIMBS);
+  if (npoly < 0) return rh_fail(RH_ERR_ARG, "%s: npoly < 0", who);
+  if (r->N < n_multiple || r->N % n_multiple) return rh_fail(RH_ERR_ARG, n_multiple == 2 ? "%s: N must be even" : "%s: N must be a multiple of %d", who, n_multiple);
+  return 0;
+}
+int rh_comps3(const void* in0, const void* in1, const void* in2, const void* out0, const void* out1, const void* out2, const char* who) {
+  if (!in0 || !out0) return rh_fail(RH_ERR_ARG, "%s: null argument", who);
+  if ((in2 && !in1) || (in1 != nullptr) != (out1 != nullptr) || (in2 != nullptr) != (out2 != nullptr))
+    return rh_fail(RH_ERR_ARG, "%s: components 1 and 2 need an input and an output each, and component 2 needs component 1", who);
+  return 0;
+}
+int rh_pack_scalars(const rh_ring* r, int level, const u64* a, const u64* b, bool mont, RhScalars* s, const char* who, const char* noun) {
+  memset(s, 0, sizeof(*s));
+  for (int i = 0; i <= level; ++i) {
+    const u64 q = r->moduli[i];
+    if ((a && a[i] >= q) || (b && b[i] >= q)) return rh_fail(RH_ERR_ARG, "%s: %s of limb %d is not below its modulus", who, noun, i);
+    if (a) s->a[i] = mont ? rh::mform(a[i], q) : a[i];
+    if (b) s->b[i] = mont ? rh::mform(b[i], q) : b[i];
+  }
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ NTT launches
 
 template <class P>
 static void launch_fwd_cols(int S1, dim3 grid, hipStream_t st, const u64* in, u64* out, const typename P::tw_t* tw,
@@ -382,11 +419,11 @@ static int std_ntt_launch_span(rh_ring* r, const u64* in, u64* out, int npoly, i
     } else {
       ntt_inv_small<<<rows, 256, 0, st>>>(in, out, r->d_tw_inv + toff, c, Lrows, logN, r->inv_scale ? 1 : 0, Ls, Lso);
     }
-    return check_launch("ntt_small");
+    return rh_launch_ok("ntt_small");
   }
   const int S1 = logN - LT;
   const unsigned tiles = rows << S1;
-  const bool nt = rh_nt_policy(r->nt_streams, (size_t)rows * (size_t)r->N * 8, (size_t)512 << 20);   // non-temporal data streams beyond the Infinity Cache (see rh_streams_beyond_cache)
+  const bool nt = rh_stream_grid(r, rows).nt;   // non-temporal data streams beyond the Infinity Cache
   if (phase == 0 && !(lazy && !inverse) && one_pass_ok(r)) {          // (the forward lazy form keeps the reference's representatives: Montgomery bodies, two passes)
     const size_t lds = ((size_t)LDS_WORDS * 8) << S1;
     const dim3 wg(256u << S1);
@@ -403,7 +440,7 @@ static int std_ntt_launch_span(rh_ring* r, const u64* in, u64* out, int npoly, i
       else if (nt) ntt_inv_onepass_asm<2, true><<<grid, wg, lds, st>>>(in, out, r->d_twk_inv + toff, r->d_tw_inv + toff, r->d_lastw + limb0, c, Lrows, Ls, Lso, sc);
       else ntt_inv_onepass_asm<2, false><<<grid, wg, lds, st>>>(in, out, r->d_twk_inv + toff, r->d_tw_inv + toff, r->d_lastw + limb0, c, Lrows, Ls, Lso, sc);
     }
-    return check_launch("ntt (one pass)");
+    return rh_launch_ok("ntt (one pass)");
   }
   if (!inverse) {
     const u64* src = in;
@@ -437,7 +474,7 @@ static int std_ntt_launch_span(rh_ring* r, const u64* in, u64* out, int npoly, i
       if (r->asm_tile && S1 == 0 && r->inv_scale && r->one_pass && phase == 0) {
         if (nt) ntt_inv_onepass_asm<0, true><<<rows, 256, (size_t)LDS_WORDS * 8, st>>>(in, out, r->d_twk_inv + toff, r->d_tw_inv + toff, r->d_lastw + limb0, c, Lrows, Ls, Lso, 1);
         else ntt_inv_onepass_asm<0, false><<<rows, 256, (size_t)LDS_WORDS * 8, st>>>(in, out, r->d_twk_inv + toff, r->d_tw_inv + toff, r->d_lastw + limb0, c, Lrows, Ls, Lso, 1);
-        return check_launch("ntt (N = 4096, inverse)");
+        return rh_launch_ok("ntt (N = 4096, inverse)");
       }
       if (r->asm_tile && (S1 > 0 || !r->inv_scale) && nt) ntt_inv_tile_asm<true><<<tiles, 256, 0, st>>>(in, out, r->d_twk_inv + toff, c, Lrows, logN, npoly, Ls, Lso);
       else if (r->asm_tile && (S1 > 0 || !r->inv_scale)) ntt_inv_tile_asm<false><<<tiles, 256, 0, st>>>(in, out, r->d_twk_inv + toff, c, Lrows, logN, npoly, Ls, Lso);
@@ -452,7 +489,7 @@ static int std_ntt_launch_span(rh_ring* r, const u64* in, u64* out, int npoly, i
     else if (S1 == 2 && acols) ntt_inv_cols_asm<2><<<dim3(rows * 16), 256, 0, st>>>(out, r->d_tw_inv + toff, r->d_lastw + limb0, c, Lrows, Lso);
     else if (S1 > 0 && phase != 2) launch_inv_cols(S1, dim3(rows * 16), st, out, r->d_tw_inv + toff, r->d_lastw + limb0, c, Lrows, logN, r->inv_scale ? 1 : 0, Lso);
   }
-  return check_launch("ntt");
+  return rh_launch_ok("ntt");
 }
 
 template <int S1>
@@ -502,7 +539,7 @@ static int std_ntt_fwd_pipelined_segs(rh_ring* r, const NttSeg* segs, int nseg, 
       case 5: launch_fused<5>(r, i1, o1, n1, d2, n2, n2p, toff, c, Lrows); break;
     }
   }
-  return check_launch("ntt_fwd_fused");
+  return rh_launch_ok("ntt_fwd_fused");
 }
 static int std_ntt_fwd_pipelined(rh_ring* r, const u64* in, u64* out, int npoly, int Lrows, int limb0, int chunk) {
   const NttSeg seg{in, out, npoly};
@@ -552,7 +589,7 @@ static int std_ntt_inv_pipelined(rh_ring* r, const u64* in, u64* out, int npoly,
       case 5: launch_inv_fused<5>(r, i1, ib, o1, n1, n1p, d2, n2, toff, limb0, c, Lrows); break;
     }
   }
-  return check_launch("ntt_inv_fused_asm");
+  return rh_launch_ok("ntt_inv_fused_asm");
 }
 
 int rh_std_ntt_launch(rh_ring* r, const u64* in, u64* out, int npoly, int Lrows, int limb0, bool inverse, bool lazy, int phase) {
@@ -620,7 +657,7 @@ int rh_std_ntt_fwd_blocks_small(rh_ring* r, u64* data, size_t block_stride, int 
                        else ntt_fwd_tile_blocks_asm<S, false><<<dim3(n2, ny), 256, 0, st>>>(ta, tb, npoly); } while (0)
   switch (S1) { case 2: RH_BLK(2); break; case 3: RH_BLK(3); break; case 4: RH_BLK(4); break; }
 #undef RH_BLK
-  return check_launch("ntt_fwd_blocks (small batch)");
+  return rh_launch_ok("ntt_fwd_blocks (small batch)");
 }
 int rh_std_ntt_fwd_blocks(rh_ring* r, u64* data, size_t block_stride, int npoly, int nblocks, int Ls, const int* gap0, const int* gap_len,
                           bool lazy_out, int small) {       // small: 1 / 0 = every block in one launch pair / the pipelined stream; -1 = by the ring's ks_small_rows                  // block j: npoly polys of Ls rows, rows [gap0[j], gap0[j] + gap_len[j]) left alone
@@ -646,7 +683,7 @@ int rh_std_ntt_fwd_blocks(rh_ring* r, u64* data, size_t block_stride, int npoly,
     // non-temporal data streams once a block is too large to be re-read from the Infinity Cache by the next launch's tile stages
 #define RH_GAP2(S, Z) do { if (nt) ntt_fwd_fused_gap_asm<S, Z, true><<<grid, 256, 0, st>>>(d1, n1, g1, d2, n2, npoly, g2, r->d_tw_fwd, r->d_twk_fwd, r->d_consts); \
                            else ntt_fwd_fused_gap_asm<S, Z, false><<<grid, 256, 0, st>>>(d1, n1, g1, d2, n2, npoly, g2, r->d_tw_fwd, r->d_twk_fwd, r->d_consts); } while (0)
-    const bool nt = rh_nt_policy(r->nt_streams, (size_t)npoly * (size_t)Ls * (size_t)r->N * 8, (size_t)256 << 20);
+    const bool nt = rh_nt_policy(r->nt_streams, (size_t)npoly * (size_t)Ls * (size_t)r->N * 8, (size_t)256 << 20);   // 256 MiB, not rh_stream_grid's 512: see above
     switch (S1) {
       case 2: if (lazy_out) RH_GAP2(2, true); else RH_GAP2(2, false); break;
       case 3: if (lazy_out) RH_GAP2(3, true); else RH_GAP2(3, false); break;
@@ -654,7 +691,7 @@ int rh_std_ntt_fwd_blocks(rh_ring* r, u64* data, size_t block_stride, int npoly,
     }
 #undef RH_GAP2
   }
-  return check_launch("ntt_fwd_fused_gap_asm");
+  return rh_launch_ok("ntt_fwd_fused_gap_asm");
 }
 int rh_std_ntt_fwd_digits(rh_ring* r, u64* data, size_t digit_stride, int npoly, int beta, int LQ, int LP, bool lazy_out, int small) {
   if (beta <= 0) return RH_OK;
@@ -684,7 +721,7 @@ int rh_std_intt_limb_strided(rh_ring* r, const u64* in, int in_rows, int limb, u
   if (S1 == 4) ntt_inv_cols_asm<4><<<g, 256, 0, st>>>(out, r->d_tw_inv + toff, r->d_lastw + limb, r->d_consts + limb, 1, 0);
   else if (S1 == 3) ntt_inv_cols_asm<3><<<g, 256, 0, st>>>(out, r->d_tw_inv + toff, r->d_lastw + limb, r->d_consts + limb, 1, 0);
   else ntt_inv_cols_asm<2><<<g, 256, 0, st>>>(out, r->d_tw_inv + toff, r->d_lastw + limb, r->d_consts + limb, 1, 0);
-  return check_launch("strided single-limb inverse transform");
+  return rh_launch_ok("strided single-limb inverse transform");
 }
 
 // Inverse canonical transform of limbs 0..Lrows-1 of every poly of a block with in_rows limbs per poly into a block with out_rows limbs per
@@ -701,12 +738,13 @@ int rh_std_intt_rows(rh_ring* r, const u64* in, int in_rows, u64* out, int out_r
   if (S1 == 4) ntt_inv_cols_asm<4><<<g, 256, 0, st>>>(out, r->d_tw_inv, r->d_lastw, r->d_consts, Lrows, out_rows);
   else if (S1 == 3) ntt_inv_cols_asm<3><<<g, 256, 0, st>>>(out, r->d_tw_inv, r->d_lastw, r->d_consts, Lrows, out_rows);
   else ntt_inv_cols_asm<2><<<g, 256, 0, st>>>(out, r->d_tw_inv, r->d_lastw, r->d_consts, Lrows, out_rows);
-  return check_launch("strided inverse transform");
+  return rh_launch_ok("strided inverse transform");
 }
 
 // ---- 3N transform (ntt3n.hip), b = 1: the hand-scheduled layer kernels live in this translation unit with the tile bodies they fuse with
 void rh_3n_launch_layer(bool inverse, int S1, unsigned nblocks, hipStream_t st, const u64* in, u64* out, const N3Layer& a, int nt_streams) {
   // a unit moves 6 * 2^S1 coefficients per thread: nblocks * 256 * 6 * 2^S1 * 8 bytes per direction; non-temporal streams beyond 512 MiB
+  // (rh_stream_grid's threshold on this launch's own byte count: its work comes in blocks, not in rows of N)
   const bool nt = rh_nt_policy(nt_streams, (size_t)nblocks * 256 * 6 * ((size_t)8 << S1), (size_t)512 << 20);   // tuning nt_streams = 0: default policy everywhere, 2: non-temporal at every size
 #define RH_3NL2(S, I) do { if (nt) ntt3n_layer_asm<S, I, true><<<nblocks, 256, 0, st>>>(in, out, a); else ntt3n_layer_asm<S, I, false><<<nblocks, 256, 0, st>>>(in, out, a); } while (0)
 #define RH_3NL(S) do { if (inverse) RH_3NL2(S, true); else RH_3NL2(S, false); } while (0)
@@ -717,9 +755,7 @@ void rh_3n_launch_layer(bool inverse, int S1, unsigned nblocks, hipStream_t st, 
 bool rh_can_fuse_submul(const rh_ring* r) { return r->kind == RH_RING_STANDARD && r->logN >= LT && r->fuse_submul; }
 // Forward canonical transform of `buf` (in place up to its tile stages) fused with out = MRed(2q - y + NTT(buf), s_limb):
 // column stages as usual, then ntt_fwd_tile_submul.  y / out: (poly, limb) blocks with y_rows / out_rows limbs per poly.
-// Cache policy of a launch's data streams: non-temporal once the rows it moves exceed twice the 256 MiB Infinity Cache (the generated
-// bodies exist in both forms, tools/gen_tile_asm.py; smaller working sets are re-read from the caches and run 3-6 % slower with nt)
-static bool rh_streams_beyond_cache(const rh_ring* r, unsigned rows) { return rh_nt_policy(r->nt_streams, (size_t)rows * (size_t)r->N * 8, (size_t)512 << 20); }
+// Cache policy of a launch's data streams: rh_stream_grid's nt (the generated bodies exist in both forms, tools/gen_tile_asm.py)
 
 // rescale: column stages of limbs 0..Lrows-1 fed by the re-expansion of the coefficient-domain last limb `tmp` (N >= 8192)
 int rh_std_ntt_expand_cols_launch(rh_ring* r, const u64* tmp, u64* buf, int npoly, int Lrows, const void* table_dev, int mode, u64 qL) {
@@ -733,7 +769,7 @@ int rh_std_ntt_expand_cols_launch(rh_ring* r, const u64* tmp, u64* buf, int npol
   bool lazy_ok = r->asm_tile && r->asm_cols && S1 >= 2 && S1 <= 4;      // hand-scheduled body: needs qL + q <= 8q for every limb
   for (int i = 0; i < Lrows && lazy_ok; ++i) lazy_ok = qL / 7 <= r->moduli[i] && qL - 1 < 7 * r->moduli[i];
   if (lazy_ok) {
-    const bool nt = rh_streams_beyond_cache(r, rows);          // non-temporal data streams for working sets far beyond the Infinity Cache
+    const bool nt = rh_stream_grid(r, rows).nt;          // non-temporal data streams for working sets far beyond the Infinity Cache
     switch (S1 * 2 + (nt ? 1 : 0)) {
       case 4: ntt_fwd_cols_expand_asm<2, false><<<g, 256, 0, rh_stream(r)>>>(tmp, buf, r->d_tw_fwd, r->d_consts, T, Lrows, mode, qL); break;
       case 5: ntt_fwd_cols_expand_asm<2, true><<<g, 256, 0, rh_stream(r)>>>(tmp, buf, r->d_tw_fwd, r->d_consts, T, Lrows, mode, qL); break;
@@ -742,7 +778,7 @@ int rh_std_ntt_expand_cols_launch(rh_ring* r, const u64* tmp, u64* buf, int npol
       case 8: ntt_fwd_cols_expand_asm<4, false><<<g, 256, 0, rh_stream(r)>>>(tmp, buf, r->d_tw_fwd, r->d_consts, T, Lrows, mode, qL); break;
       case 9: ntt_fwd_cols_expand_asm<4, true><<<g, 256, 0, rh_stream(r)>>>(tmp, buf, r->d_tw_fwd, r->d_consts, T, Lrows, mode, qL); break;
     }
-    return check_launch("ntt_fwd_cols_expand_asm");
+    return rh_launch_ok("ntt_fwd_cols_expand_asm");
   }
   switch (S1) {
     case 1: ntt_fwd_cols_expand<1><<<g, 256, 0, rh_stream(r)>>>(tmp, buf, r->d_tw_fwd, r->d_consts, T, Lrows, r->logN, mode, qL); break;
@@ -751,7 +787,7 @@ int rh_std_ntt_expand_cols_launch(rh_ring* r, const u64* tmp, u64* buf, int npol
     case 4: ntt_fwd_cols_expand<4><<<g, 256, 0, rh_stream(r)>>>(tmp, buf, r->d_tw_fwd, r->d_consts, T, Lrows, r->logN, mode, qL); break;
     case 5: ntt_fwd_cols_expand<5><<<dim3(rows * 16), 256, 0, rh_stream(r)>>>(tmp, buf, r->d_tw_fwd, r->d_consts, T, Lrows, r->logN, mode, qL); break;
   }
-  return check_launch("ntt_fwd_cols_expand");
+  return rh_launch_ok("ntt_fwd_cols_expand");
 }
 
 // Both components of a ModDown in ONE launch: buf holds 2 * npoly polys (component 0 then component 1, column stages done), component c goes with
@@ -768,12 +804,12 @@ int rh_std_ntt_submul_launch_pair(rh_ring* r, u64* buf, int npoly, int Lrows, co
     const u64 q = r->moduli[i];
     sh.w[i] = rh::imform(scalars_host[i] % q, q); sh.wp[i] = rh::shoup_quotient(sh.w[i], q);
   }
-  const bool nt = rh_streams_beyond_cache(r, rows / 2);       // (the policy of one component's launch, as before)
+  const bool nt = rh_stream_grid(r, rows / 2).nt;       // (the policy of one component's launch, as before)
   hipStream_t st = rh_stream(r);
 #define RH_SMP(ADD, NTF) ntt_fwd_tile_submul_asm<ADD, NTF><<<rows << S1, 256, 0, st>>>(buf, r->d_twk_fwd, r->d_consts, Lrows, r->logN, 2 * npoly, y0, y_rows, out0, out_rows, sh, z0, z_rows, npoly, y1, out1, z1)
   if (z0 && nt) RH_SMP(true, true); else if (z0) RH_SMP(true, false); else if (nt) RH_SMP(false, true); else RH_SMP(false, false);
 #undef RH_SMP
-  return check_launch("ntt_fwd_tile_submul_asm (pair)");
+  return rh_launch_ok("ntt_fwd_tile_submul_asm (pair)");
 }
 int rh_std_ntt_submul_launch(rh_ring* r, u64* buf, int npoly, int Lrows, int limb0, const u64* y, int y_rows, u64* out, int out_rows,
                              const u64* scalars_host, bool cols_done, const u64* z, int z_rows) {
@@ -791,7 +827,7 @@ int rh_std_ntt_submul_launch(rh_ring* r, u64* buf, int npoly, int Lrows, int lim
       const u64 q = r->moduli[limb0 + i];
       sh.w[i] = rh::imform(scalars_host[i] % q, q); sh.wp[i] = rh::shoup_quotient(sh.w[i], q);
     }
-    const bool nt = rh_streams_beyond_cache(r, rows);
+    const bool nt = rh_stream_grid(r, rows).nt;
     if (z && nt) ntt_fwd_tile_submul_asm<true, true><<<rows << S1, 256, 0, rh_stream(r)>>>(buf, r->d_twk_fwd + toff, r->d_consts + limb0, Lrows, r->logN, npoly, y, y_rows,
                                                                                                out, out_rows, sh, z, z_rows);
     else if (z) ntt_fwd_tile_submul_asm<true, false><<<rows << S1, 256, 0, rh_stream(r)>>>(buf, r->d_twk_fwd + toff, r->d_consts + limb0, Lrows, r->logN, npoly, y, y_rows,
@@ -800,12 +836,12 @@ int rh_std_ntt_submul_launch(rh_ring* r, u64* buf, int npoly, int Lrows, int lim
                                                                                                 out, out_rows, sh, nullptr, 0);
     else ntt_fwd_tile_submul_asm<false, false><<<rows << S1, 256, 0, rh_stream(r)>>>(buf, r->d_twk_fwd + toff, r->d_consts + limb0, Lrows, r->logN, npoly, y, y_rows,
                                                                                          out, out_rows, sh, nullptr, 0);
-    return check_launch("ntt_fwd_tile_submul_asm");
+    return rh_launch_ok("ntt_fwd_tile_submul_asm");
   }
   LimbScalars sc; memset(&sc, 0, sizeof(sc)); memcpy(sc.s, scalars_host, (size_t)Lrows * 8);
   ntt_fwd_tile_submul<<<rows << S1, 256, 0, rh_stream(r)>>>(buf, r->d_twk_fwd + toff, r->d_consts + limb0, Lrows, r->logN, npoly, y, y_rows,
                                                          out, out_rows, sc, z, z_rows);
-  return check_launch("ntt_fwd_tile_submul");
+  return rh_launch_ok("ntt_fwd_tile_submul");
 }
 
 // ---- conjugate-invariant ring Z[X+X^-1]/(X^2N+1) (ring/ntt.go:716-1311): the negacyclic kernels on the re-indexed
@@ -838,7 +874,7 @@ ci_fold_kernel(const u64* in, u64* out, int logN, const CiFold* __restrict__ fol
 static int ci_ntt_launch(rh_ring* r, const u64* in, u64* out, int npoly, int Lrows, int limb0, bool inverse) {
   const unsigned rows = (unsigned)npoly * Lrows;
   if (!rows) return RH_OK;
-  unsigned chunks = ((unsigned)r->N / 2 + 256) / 256; if (chunks > 64) chunks = 64;
+  unsigned chunks = ((unsigned)r->N / 2 + 256) / 256; if (chunks > 64) chunks = 64;   // ci_fold_kernel: the N/2 + 1 index pairs (j, N - j), one per thread and chunk; not rh_stream_grid's four adjacent pairs
   (void)hipGetLastError();
   const int S1 = r->logN - LT;
   if (r->asm_tile && r->asm_cols && r->fuse_ci && S1 >= 2 && S1 <= 4) {
@@ -876,7 +912,7 @@ static int ci_ntt_launch(rh_ring* r, const u64* in, u64* out, int npoly, int Lro
 #undef RH_CII
         }
       }
-      return check_launch("conjugate-invariant transform (pipelined)");
+      return rh_launch_ok("conjugate-invariant transform (pipelined)");
     }
     const unsigned g8 = rows * 8, g0 = (rows + 63) / 64;
 #define RH_CI(S, INV, SRC, TW, LW) do { ntt_cols_ci_asm<S, INV><<<g8, 256, 0, st>>>(SRC, out, TW, LW, cf, c, Lrows);  \
@@ -884,14 +920,14 @@ static int ci_ntt_launch(rh_ring* r, const u64* in, u64* out, int npoly, int Lro
     if (!inverse) {
       if (S1 == 4) RH_CI(4, false, in, r->d_tw_fwd + toff, nullptr); else if (S1 == 3) RH_CI(3, false, in, r->d_tw_fwd + toff, nullptr);
       else RH_CI(2, false, in, r->d_tw_fwd + toff, nullptr);
-      if (int rc = check_launch("ntt_cols_ci_asm")) return rc;
+      if (int rc = rh_launch_ok("ntt_cols_ci_asm")) return rc;
       return rh_std_ntt_launch(r, out, out, npoly, Lrows, limb0, false, false, 2);          // tile stages
     }
     if (int rc = rh_std_ntt_launch(r, in, out, npoly, Lrows, limb0, true, false, 2)) return rc;   // tile stages
     if (S1 == 4) RH_CI(4, true, out, r->d_tw_inv + toff, r->d_lastw + limb0); else if (S1 == 3) RH_CI(3, true, out, r->d_tw_inv + toff, r->d_lastw + limb0);
     else RH_CI(2, true, out, r->d_tw_inv + toff, r->d_lastw + limb0);
 #undef RH_CI
-    return check_launch("ntt_cols_ci_asm");
+    return rh_launch_ok("ntt_cols_ci_asm");
   }
   if (!inverse) {
     ci_fold_kernel<<<dim3(rows, chunks), 256, 0, rh_stream(r)>>>(in, out, r->logN, r->d_cifold + limb0, r->d_consts + limb0, Lrows, 0);
@@ -899,7 +935,7 @@ static int ci_ntt_launch(rh_ring* r, const u64* in, u64* out, int npoly, int Lro
   }
   if (int rc = rh_std_ntt_launch(r, in, out, npoly, Lrows, limb0, true, false, 0)) return rc;
   ci_fold_kernel<<<dim3(rows, chunks), 256, 0, rh_stream(r)>>>(out, out, r->logN, r->d_cifold + limb0, r->d_consts + limb0, Lrows, 1);
-  return check_launch("ci_fold_kernel");
+  return rh_launch_ok("ci_fold_kernel");
 }
 
 // canonical transform of limbs [limb0, limb0 + Lrows) of a dense block, for a ring of any type (rescale.hip)
@@ -1054,7 +1090,7 @@ static int std_intt_mul_launch(rh_ring* r, const u64* a, const u64* b, u64* out,
     else if (S1 == 3) ntt_inv_cols_asm<3><<<dim3(rows * 16), 256, 0, st>>>(out, r->d_tw_inv, r->d_lastw_r, r->d_consts_r, Lrows, 0);
     else ntt_inv_cols_asm<2><<<dim3(rows * 16), 256, 0, st>>>(out, r->d_tw_inv, r->d_lastw_r, r->d_consts_r, Lrows, 0);
   } else if (S1 > 0) launch_inv_cols(S1, dim3(rows * 16), st, out, r->d_tw_inv, r->d_lastw_r, r->d_consts_r, Lrows, logN, 1);
-  return check_launch("intt_mul");
+  return rh_launch_ok("intt_mul");
 }
 extern "C" int rh_ring_intt_mul(rh_ring* r, const uint64_t* a, const uint64_t* b, uint64_t* out, int npoly, int level) {
   if (!r || !a || !b || !out) return rh_fail(RH_ERR_ARG, "intt_mul: null argument");
@@ -1109,21 +1145,21 @@ extern "C" int rh_ring_polymul(rh_ring* r, uint64_t* a, uint64_t* b, uint64_t* o
       switch (S1) { case 1: RH_PM_FUSED(1); break; case 2: RH_PM_FUSED(2); break; case 3: RH_PM_FUSED(3); break; case 4: RH_PM_FUSED(4); break; default: RH_PM_FUSED(5); break; }
 #undef RH_PM_FUSED
     }
-    return check_launch("polymul (pipelined)");
+    return rh_launch_ok("polymul (pipelined)");
   }
   if (int rc = std_ntt_launch_span(r, a, a, npoly, Lrows, 0, false, false, 1)) return rc;       // column stages only (phase 1), in place
   if (int rc = std_ntt_launch_span(r, b, b, npoly, Lrows, 0, false, false, 1)) return rc;
   (void)hipGetLastError();
-  if (rh_streams_beyond_cache(r, rows)) ntt_polymul_tile_asm<true><<<rows << S1, 256, 0, st>>>(a, b, out, r->d_twk_fwd, r->d_twk_inv, r->d_consts_r, Lrows, r->logN, npoly);
+  if (rh_stream_grid(r, rows).nt) ntt_polymul_tile_asm<true><<<rows << S1, 256, 0, st>>>(a, b, out, r->d_twk_fwd, r->d_twk_inv, r->d_consts_r, Lrows, r->logN, npoly);
   else ntt_polymul_tile_asm<false><<<rows << S1, 256, 0, st>>>(a, b, out, r->d_twk_fwd, r->d_twk_inv, r->d_consts_r, Lrows, r->logN, npoly);
-  const bool nt = rh_streams_beyond_cache(r, rows);
+  const bool nt = rh_stream_grid(r, rows).nt;
   if (S1 >= 2 && S1 <= 4 && r->asm_cols) {
 #define RH_PM_COLS(S) do { if (nt) ntt_inv_cols_asm<S, true><<<dim3(rows * 16), 256, 0, st>>>(out, r->d_tw_inv, r->d_lastw_r, r->d_consts_r, Lrows, 0); \
                            else ntt_inv_cols_asm<S, false><<<dim3(rows * 16), 256, 0, st>>>(out, r->d_tw_inv, r->d_lastw_r, r->d_consts_r, Lrows, 0); } while (0)
     if (S1 == 4) RH_PM_COLS(4); else if (S1 == 3) RH_PM_COLS(3); else RH_PM_COLS(2);
 #undef RH_PM_COLS
   } else launch_inv_cols(S1, dim3(rows * 16), st, out, r->d_tw_inv, r->d_lastw_r, r->d_consts_r, Lrows, r->logN, 1);
-  return check_launch("polymul");
+  return rh_launch_ok("polymul");
 }
 
 extern "C" int rh_ring_ntt3n_reorder(rh_ring* r, const uint64_t* in, uint64_t* out, int npoly, int level, int to_reference) {
@@ -1378,28 +1414,20 @@ template <int OP>
 __global__ void __launch_bounds__(256)
 vec_op_packed(const u64* p1, const u64* p2, u64* p3, unsigned n, ScalarPack s0, ScalarPack s1,
               const LimbConsts* __restrict__ consts, int L, RowStrides rs) {
-  const u32 row = blockIdx.x;
-  const u32 limb = row % (u32)L, poly = row / (u32)L;
-  const LimbConsts c = consts[limb];
-  const u64 a0 = s0.s[limb], a1 = s1.s[limb];
-  const size_t o1 = ((size_t)poly * rs.r1 + limb) * n, o2 = rs.r2 < 0 ? 0 : ((size_t)poly * rs.r2 + limb) * n, o3 = ((size_t)poly * rs.r3 + limb) * n;
-  for (unsigned i = rs.pair0 + blockIdx.y * blockDim.x + threadIdx.x; i < rs.pair1; i += gridDim.y * blockDim.x) {
+  const StreamRow row(consts, L, n);
+  const LimbConsts& c = row.c;
+  const u64 a0 = s0.s[row.limb], a1 = s1.s[row.limb];
+  const size_t o1 = row.at(rs.r1, n), o2 = rs.r2 < 0 ? 0 : row.at(rs.r2, n), o3 = row.at(rs.r3, n);
+  RH_FOR_EACH_PAIR(i, rs.pair0, rs.pair1) {
     const size_t e = 2 * (size_t)i;
-    typedef u64 u64x2_t __attribute__((ext_vector_type(2)));
-    auto ld = [&](const u64* p, bool nt) {
-      if (!nt) return *reinterpret_cast<const ulonglong2*>(p);
-      const u64x2_t v = __builtin_nontemporal_load(reinterpret_cast<const u64x2_t*>(p));
-      return make_ulonglong2(v.x, v.y);
-    };
     ulonglong2 x = make_ulonglong2(0, 0), y = x, z = x;
-    if (op_reads_x(OP)) x = ld(p1 + o1 + e, rs.nt);
-    if (op_reads_y(OP)) y = ld(p2 + o2 + e, rs.nt && rs.r2 >= 0);
-    if (op_reads_z(OP)) z = ld(p3 + o3 + e, rs.nt);
+    if (op_reads_x(OP)) x = rh_ld2(p1 + o1 + e, rs.nt);
+    if (op_reads_y(OP)) y = rh_ld2(p2 + o2 + e, rs.nt && rs.r2 >= 0);       // a broadcast row is re-read by every workgroup: default policy
+    if (op_reads_z(OP)) z = rh_ld2(p3 + o3 + e, rs.nt);
     ulonglong2 w;
     w.x = vec_apply<OP>(x.x, y.x, z.x, a0, a1, c);
     w.y = vec_apply<OP>(x.y, y.y, z.y, a0, a1, c);
-    if (rs.nt) { u64x2_t v; v.x = w.x; v.y = w.y; __builtin_nontemporal_store(v, reinterpret_cast<u64x2_t*>(p3 + o3 + e)); }
-    else *reinterpret_cast<ulonglong2*>(p3 + o3 + e) = w;
+    rh_st2(p3 + o3 + e, w, rs.nt);
   }
 }
 
@@ -1420,15 +1448,11 @@ int rh_vec_launch(rh_ring* r, int opcode, const u64* p1, const u64* p2, u64* p3,
   if (s1) memcpy(b.s, s1, (size_t)Lrows * 8);
   const unsigned rows = (unsigned)npoly * (unsigned)Lrows;
   if (rows == 0) return RH_OK;
-  const unsigned n = (unsigned)r->N;
-  unsigned chunks = (n / 2 + 256 * 4 - 1) / (256 * 4);
-  if (chunks < 1) chunks = 1;
-  if (chunks > 64) chunks = 64;
-  const unsigned npairs = n >> 1;
-  const RowStrides rs{rows1 ? rows1 : Lrows, rows2 ? rows2 : Lrows, rows3 ? rows3 : Lrows, half == 2 ? npairs / 2 : 0u, half == 1 ? npairs / 2 : npairs,
-                      rh_nt_policy(r->nt_streams, (size_t)rows * (size_t)r->N * 8, (size_t)512 << 20) ? 1 : 0};
-  hipLaunchKernelGGL(table[opcode], dim3(rows, chunks), dim3(256), 0, rh_stream(r), p1, p2, p3, n, a, b, r->d_consts + limb0, Lrows, rs);
-  return check_launch("vec_op");
+  const unsigned n = (unsigned)r->N, npairs = n >> 1;
+  const RhStreamGrid g = rh_stream_grid(r, rows);
+  const RowStrides rs{rows1 ? rows1 : Lrows, rows2 ? rows2 : Lrows, rows3 ? rows3 : Lrows, half == 2 ? npairs / 2 : 0u, half == 1 ? npairs / 2 : npairs, g.nt};
+  hipLaunchKernelGGL(table[opcode], g.grid, dim3(256), 0, rh_stream(r), p1, p2, p3, n, a, b, r->d_consts + limb0, Lrows, rs);
+  return rh_launch_ok("vec_op");
 }
 
 // p2 = ONE row of N words used for every (poly, limb): MulByVectorMontgomery(ThenAddLazy) (ring/operations.go:366-377) with the
@@ -1452,59 +1476,6 @@ extern "C" int rh_ring_vec_op_halves(rh_ring* r, int opcode, const uint64_t* p1,
   (void)hipSetDevice(r->device);
   if (int rc = rh_vec_launch(r, opcode, p1, nullptr, p3, npoly, level + 1, 0, s_lo, nullptr, 0, 0, 0, 1)) return rc;
   return rh_vec_launch(r, opcode, p1, nullptr, p3, npoly, level + 1, 0, s_hi, nullptr, 0, 0, 0, 2);
-}
-
-// Degree-1 x degree-1 tensoring of ckks mulRelin (schemes/ckks/evaluator.go:821-834) in one pass: the six ring calls
-//   c00 = MForm(a0); c01 = MForm(a1); c0 = MulCoeffsMontgomery(c00, b0); c2 = MulCoeffsMontgomery(c01, b1);
-//   c1 = MulCoeffsMontgomery(c00, b1); c1 = MulCoeffsMontgomeryThenAdd(c01, b0, c1)
-// with the same formulas element by element (7 operands of traffic instead of 23).  Outputs may alias inputs element-wise.
-__global__ void __launch_bounds__(256)
-tensor_degree1_kernel(const u64* a0, const u64* a1, const u64* b0, const u64* b1, u64* c0, u64* c1, u64* c2, unsigned n,
-                      const LimbConsts* __restrict__ consts, int L, int mform_first, int nt) {   // mform_first 0: no MForm (matrix_ckks.Evaluator.Mul, evaluator.go:166-173); nt: non-temporal streams
-  typedef u64 u64x2_t __attribute__((ext_vector_type(2)));
-  auto ld = [&](const u64* p) {
-    if (!nt) return *reinterpret_cast<const ulonglong2*>(p);
-    const u64x2_t v = __builtin_nontemporal_load(reinterpret_cast<const u64x2_t*>(p));
-    return make_ulonglong2(v.x, v.y);
-  };
-  auto st = [&](u64* p, const ulonglong2& w) {
-    if (nt) { u64x2_t v; v.x = w.x; v.y = w.y; __builtin_nontemporal_store(v, reinterpret_cast<u64x2_t*>(p)); }
-    else *reinterpret_cast<ulonglong2*>(p) = w;
-  };
-  const u32 row = blockIdx.x, limb = row % (u32)L;
-  const LimbConsts c = consts[limb];
-  const size_t ro = (size_t)row * n;
-  for (unsigned i = blockIdx.y * blockDim.x + threadIdx.x; i < (n >> 1); i += gridDim.y * blockDim.x) {
-    const size_t o = ro + 2 * (size_t)i;
-    const ulonglong2 x0 = ld(a0 + o), x1 = ld(a1 + o);
-    const ulonglong2 y0 = ld(b0 + o), y1 = ld(b1 + o);
-    ulonglong2 r0, r1, r2;
-    {
-      const u64 m0 = mform_first ? mform(x0.x, c.q, c.bred0, c.bred1) : x0.x, m1 = mform_first ? mform(x1.x, c.q, c.bred0, c.bred1) : x1.x;
-      r0.x = mred(m0, y0.x, c.q, c.qinv); r2.x = mred(m1, y1.x, c.q, c.qinv);
-      r1.x = cred(mred(m0, y1.x, c.q, c.qinv) + mred(m1, y0.x, c.q, c.qinv), c.q);
-    }
-    {
-      const u64 m0 = mform_first ? mform(x0.y, c.q, c.bred0, c.bred1) : x0.y, m1 = mform_first ? mform(x1.y, c.q, c.bred0, c.bred1) : x1.y;
-      r0.y = mred(m0, y0.y, c.q, c.qinv); r2.y = mred(m1, y1.y, c.q, c.qinv);
-      r1.y = cred(mred(m0, y1.y, c.q, c.qinv) + mred(m1, y0.y, c.q, c.qinv), c.q);
-    }
-    st(c0 + o, r0); st(c1 + o, r1); st(c2 + o, r2);
-  }
-}
-extern "C" int rh_ring_tensor_degree1(rh_ring* r, const uint64_t* a0, const uint64_t* a1, const uint64_t* b0, const uint64_t* b1,
-                                      uint64_t* c0, uint64_t* c1, uint64_t* c2, int npoly, int level, int mform_first) {
-  if (!r || !a0 || !a1 || !b0 || !b1 || !c0 || !c1 || !c2) return rh_fail(RH_ERR_ARG, "tensor_degree1: null argument");
-  if (level < 0 || level >= r->L) return rh_fail(RH_ERR_ARG, "tensor_degree1: level %d out of range [0,%d)", level, r->L);
-  if (npoly < 0) return rh_fail(RH_ERR_ARG, "tensor_degree1: npoly < 0");
-  const unsigned rows = (unsigned)npoly * (unsigned)(level + 1), n = (unsigned)r->N;
-  if (rows == 0) return RH_OK;
-  (void)hipSetDevice(r->device);
-  (void)hipGetLastError();
-  unsigned chunks = (n / 2 + 1023) / 1024; if (chunks < 1) chunks = 1; if (chunks > 64) chunks = 64;
-  tensor_degree1_kernel<<<dim3(rows, chunks), 256, 0, rh_stream(r)>>>(a0, a1, b0, b1, c0, c1, c2, n, r->d_consts, level + 1, mform_first,
-                                                                      rh_streams_beyond_cache(r, rows) ? 1 : 0);
-  return check_launch("tensor_degree1");
 }
 
 extern "C" int rh_ring_vec_op(rh_ring* r, int opcode, const uint64_t* p1, const uint64_t* p2, uint64_t* p3, int npoly, int level,

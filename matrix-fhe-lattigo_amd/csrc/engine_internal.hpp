@@ -71,6 +71,29 @@ struct rh_ring {
   int chunk_polys = -1;           // -1 = auto (128-poly spans for batches >= 256), 0 = whole batch in two launches, >0 = polys per span
 };
 
+// ---- launch plumbing shared by every translation unit (engine.hip) ----
+int rh_launch_ok(const char* what);                          // RH_OK, or "<what> launch failed: <the runtime's error string>"
+// The launch shape of the row-streaming kernels (stream_kernels.hip.hpp): one row per blockIdx.x, 1024 coefficient pairs (four per thread)
+// per chunk on blockIdx.y, at most 64 chunks; nt: non-temporal streams once the rows move 512 MiB, twice the 256 MiB Infinity Cache
+// (smaller working sets are re-read from the caches and run 3-6 % slower with nt).
+struct RhStreamGrid { dim3 grid; int nt; };
+unsigned rh_stream_chunks(const rh_ring* r);                 // blockIdx.y extent alone (a launch with rows of its own: gadget_mac_all_kernel)
+RhStreamGrid rh_stream_grid(const rh_ring* r, unsigned rows);
+inline RhStreamGrid rh_stream_begin(const rh_ring* r, unsigned rows) {   // ... on the ring's device, any stale error of an earlier call dropped
+  (void)hipSetDevice(r->device);
+  (void)hipGetLastError();
+  return rh_stream_grid(r, rows);
+}
+// Argument checks of the scheme-level entry points (bgv.hip, ckks.hip): kinds: a mask of 1 << RH_RING_* admitted (the refusal names the scheme
+// the mask belongs to); N a multiple of n_multiple
+int rh_scheme_args(const rh_ring* r, int level, int npoly, unsigned kinds, int n_multiple, const char* who);
+// 1, 2 or 3 components, each with an input and an output; trailing NULLs mean fewer
+int rh_comps3(const void* in0, const void* in1, const void* in2, const void* out0, const void* out1, const void* out2, const char* who);
+// Two per-limb host scalars -> the by-value pack (1 KiB of kernel arguments); a / b may be null (zeros).  Every scalar must be a residue of
+// its limb (the refusal calls it a `noun`); mont: each is taken to Montgomery form.
+struct RhScalars { u64 a[RH_MAX_LIMBS]; u64 b[RH_MAX_LIMBS]; };
+int rh_pack_scalars(const rh_ring* r, int level, const u64* a, const u64* b, bool mont, RhScalars* s, const char* who, const char* noun = "scalar");
+
 // ---- per-call context of the calling thread -----------------------------------------------------------------------
 // A handle is shared by concurrent callers (ring/ring.go:192-194: transformers immutable, AtLevel views concurrency-safe), so
 // nothing a call needs may live in the handle as mutable state.  The stream a launch goes to and the 3N transform's workspace

@@ -11,8 +11,10 @@
 #include <vector>
 #include "engine_internal.hpp"
 #include "bext_internal.hpp"
+#include "stream_kernels.hip.hpp"
 
 // acc_c[row] (=|+=) MRedLazy(evk_c[limb], c2[row]) for c = 0,1.  rows = npoly * L; evk is shared by every poly.
+// The launch shape of stream_kernels.hip.hpp with plain loads and stores at every size: the key rows are re-read by every poly.
 __global__ void __launch_bounds__(256)
 gadget_mac_kernel(const u64* c2, const u64* __restrict__ evk0, const u64* __restrict__ evk1, u64* acc0, u64* acc1,
                   unsigned n, const LimbConsts* __restrict__ consts, int L, int first) {
@@ -20,7 +22,7 @@ gadget_mac_kernel(const u64* c2, const u64* __restrict__ evk0, const u64* __rest
   const u64 q = consts[limb].q, qi = consts[limb].qinv;
   const size_t ro = (size_t)row * n, eo = (size_t)limb * n;
   const unsigned npairs = n >> 1;
-  for (unsigned i = blockIdx.y * blockDim.x + threadIdx.x; i < npairs; i += gridDim.y * blockDim.x) {
+  RH_FOR_EACH_PAIR(i, 0, npairs) {
     const ulonglong2 x = *reinterpret_cast<const ulonglong2*>(c2 + ro + 2 * (size_t)i);
     const ulonglong2 k0 = *reinterpret_cast<const ulonglong2*>(evk0 + eo + 2 * (size_t)i);
     const ulonglong2 k1 = *reinterpret_cast<const ulonglong2*>(evk1 + eo + 2 * (size_t)i);
@@ -39,11 +41,8 @@ gadget_mac_kernel(const u64* c2, const u64* __restrict__ evk0, const u64* __rest
 
 int rh_gadget_mac(rh_ring* r, const u64* c2, const u64* e0, const u64* e1, u64* a0, u64* a1, int npoly, int L, int first) {
   const unsigned rows = (unsigned)npoly * L, n = (unsigned)r->N;
-  unsigned chunks = (n / 2 + 1023) / 1024; if (chunks < 1) chunks = 1; if (chunks > 64) chunks = 64;
-  gadget_mac_kernel<<<dim3(rows, chunks), 256, 0, rh_stream(r)>>>(c2, e0, e1, a0, a1, n, r->d_consts, L, first);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return rh_fail(RH_ERR_DEVICE, "gadget_mac_kernel launch failed: %s", hipGetErrorString(e));
-  return RH_OK;
+  gadget_mac_kernel<<<rh_stream_grid(r, rows).grid, 256, 0, rh_stream(r)>>>(c2, e0, e1, a0, a1, n, r->d_consts, L, first);
+  return rh_launch_ok("gadget_mac_kernel");
 }
 
 // All digits in one pass (used when the whole decomposition is resident: the hoisted layout [digit][poly][limb][N]):
@@ -120,8 +119,7 @@ gadget_mac_all_kernel(const u64* c2, size_t digit_stride, const u64* __restrict_
 // digit l / digit_limbs (the unsharded chain)
 int rh_gadget_mac_all(rh_ring* r, const u64* c2, size_t digit_stride, const u64* evk, int beta, int overf, u64* a0, u64* a1, int npoly, int L,
                       const u64* cx, const int* own_digit, int digit_limbs) {
-  const unsigned n = (unsigned)r->N;
-  unsigned chunks = (n / 2 + 1023) / 1024; if (chunks < 1) chunks = 1; if (chunks > 64) chunks = 64;
+  const unsigned n = (unsigned)r->N, chunks = rh_stream_chunks(r);     // its rows are (poly group, limb), its chunks the usual ones
   LimbDigit own;
   for (int l = 0; l < RH_MAX_LIMBS; ++l) own.d[l] = (signed char)(l < L && cx ? (own_digit ? own_digit[l] : l / (digit_limbs > 0 ? digit_limbs : 1)) : -1);
   const int PPE = npoly >= 8 ? 4 : 1;             // polys per workgroup (same-box A/B at batch 64: 1 / 2 / 4 / 8 -> 9.04 / 8.93 / 8.89 / 8.92 ms per product)
@@ -136,9 +134,7 @@ int rh_gadget_mac_all(rh_ring* r, const u64* c2, size_t digit_stride, const u64*
   }
 #undef RH_MAC_PP
 #undef RH_MAC_ALL
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return rh_fail(RH_ERR_DEVICE, "gadget_mac_all_kernel launch failed: %s", hipGetErrorString(e));
-  return RH_OK;
+  return rh_launch_ok("gadget_mac_all_kernel");
 }
 static int mac_all(rh_ring* r, const u64* c2, size_t digit_stride, const u64* evk, int beta, int overf, u64* a0, u64* a1, int npoly, int L,
                    const u64* cx = nullptr, int digit_limbs = 1) {
@@ -480,7 +476,7 @@ static int single_p_core(rh_bext* be, int levelQ, int levelP, const uint64_t* cx
     for (int j = 0; j < nd; ++j, ++e) {
       if (maskform) {
         mask_broadcast_kernel<<<grid, 256, 0, rh_stream(RQ)>>>(cxInv, LQ, i, j * pw2, pw2 ? mask : mask_all, c2Q, LQ, c2P, LP, N, RQ->d_consts, LP ? RP->d_consts : nullptr);   // (:249-252)
-        if (hipGetLastError() != hipSuccess) return rh_fail(RH_ERR_DEVICE, "mask_broadcast_kernel launch failed");
+        if (int rc = rh_launch_ok("mask_broadcast_kernel")) return rc;
       }
       if (maskform || j == 0) {                                        // s.NTTLazy under every modulus (:258-262, :285-289)
         if (int rc = rh_ring_ntt_any(RQ, c2Q, c2Q, npoly, LQ, 0, false)) return rc;

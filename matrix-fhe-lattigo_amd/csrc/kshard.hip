@@ -350,8 +350,7 @@ static int exchange_chain(rh_kshard* ks, hipStream_t st, const u64* loc, int now
   if (int rc = ag(ctx, send, xrecv, (size_t)npoly * cmax * N, (void*)st)) return rh_fail(RH_ERR_DEVICE, "rh_kshard_gadget_product: the caller's all-gather returned %d", rc);
   unsigned cy = ((unsigned)N + 2047) / 2048; if (cy > 16) cy = 16;
   kshard_unpack_kernel<<<dim3((unsigned)npoly * nl, cy), 256, 0, st>>>(xrecv, out, npoly, nl, cmax, N, m);
-  if (hipGetLastError() != hipSuccess) return rh_fail(RH_ERR_DEVICE, "kshard_unpack_kernel launch failed");
-  return RH_OK;
+  return rh_launch_ok("kshard_unpack_kernel");
 }
 
 static int product_chunk(rh_kshard* ks, hipStream_t st, const u64* cx, const u64* evkQ, const u64* evkP, u64* ct0, u64* ct1, int pc, u64* xsend,

@@ -556,9 +556,7 @@ static int ntt3n_block_order_launch(rh_ring* r, const u64* in, u64* out, int npo
       ntt3n_post_b1_inv<<<dim3(rows, chunks(N / 6)), 256, 0, st>>>(out, out, N, r3i + s->r3_off[1], s->r3_stride, l3, c, Lrows);
     }
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return rh_fail(RH_ERR_DEVICE, "3N transform (block order) launch failed: %s", hipGetErrorString(e));
-  return RH_OK;
+  return rh_launch_ok("3N transform (block order)");
 }
 
 // tiled permutation with tile shape (A, B) encoded as 10*A + B (block-order runs of 2^A words, rank-order runs of nb * 2^B words);
@@ -595,9 +593,7 @@ int rh_ring3n_reorder_launch(rh_ring* r, const u64* in, u64* out, int npoly, int
     if (!(tiled && launch_perm_tiled<false>(r->perm_inv_shape, rows, s->log_n2, nb, st, in, out, N, s->d_rank)))
       ntt3n_perm_inv<<<dim3(rows, chunks(N)), 256, 0, st>>>(in, out, N, nb, s->log_n2, s->d_block_of_rank);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return rh_fail(RH_ERR_DEVICE, "3N reorder launch failed: %s", hipGetErrorString(e));
-  return RH_OK;
+  return rh_launch_ok("3N reorder");
 }
 
 int rh_ring3n_ntt_launch(rh_ring* r, const u64* in, u64* out, int npoly, int Lrows, int limb0, bool inverse, bool block_order) {
@@ -660,9 +656,7 @@ int rh_ring3n_ntt_launch(rh_ring* r, const u64* in, u64* out, int npoly, int Lro
       ntt3n_split_inv<<<dim3(rows, chunks(N / 2)), 256, 0, st>>>(tmp, out, N, l3, c, Lrows);
     }
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return rh_fail(RH_ERR_DEVICE, "3N transform launch failed: %s", hipGetErrorString(e));
-  return RH_OK;
+  return rh_launch_ok("3N transform");
 }
 
 // tuning keys that must reach the radix-2 sub-ring as well (its tile stages choose their cache policy by size like any standard ring)

@@ -119,11 +119,6 @@ static int copy_leading_limbs(rh_ring* r, u64* dst, int dst_rows, const u64* src
                        rh_stream(r)) != hipSuccess) return rh_fail(RH_ERR_DEVICE, "rescale: strided copy failed");
   return RH_OK;
 }
-static int launched(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return rh_fail(RH_ERR_DEVICE, "%s launch failed: %s", what, hipGetErrorString(e));
-  return RH_OK;
-}
 
 // coefficient domain, nb sequential divisions.  p0 has level+1 limbs per poly and is modified like the reference's
 // buffers are; p1 has p1_rows limbs per poly.
@@ -141,7 +136,7 @@ extern "C" int rh_ring_div_by_last_modulus_many(rh_ring* r, int round, int level
     const bool last = j == nb - 1;
     rescale_step_kernel<<<grid, 256, 0, rh_stream(r)>>>(round ? 1 : 0, p0, level + 1, last ? p1 : p0, last ? p1_rows : level + 1, lv, N, r->moduli[lv], T);
   }
-  return launched("rescale_step_kernel");
+  return rh_launch_ok("rescale_step_kernel");
 }
 
 // NTT domain (DivFloorByLastModulusManyNTT / DivRoundByLastModulusManyNTT).  p0 is not modified.
@@ -166,7 +161,7 @@ extern "C" int rh_ring_div_by_last_modulus_many_ntt(rh_ring* r, int round, int l
       rescale_expand_kernel<<<grid, 256, 0, rh_stream(r)>>>(round ? 1 : 0, tmp, buff, level, level, N, r->moduli[level], T);
       if (level > 0) if (int rc = rh_ring_ntt_any(r, buff, buff, npoly, level, 0, false)) return rc;
       rescale_finish_kernel<<<grid, 256, 0, rh_stream(r)>>>(buff, level, p0, level + 1, p1, p1_rows, level, N, T);
-      return launched("rescale (NTT domain)");
+      return rh_launch_ok("rescale (NTT domain)");
     }
     if (rh_can_intt_limb_strided(r)) {               // the inverse tile stages read the last limb where it lies
       if (int rc = rh_std_intt_limb_strided(r, p0, level + 1, level, tmp, npoly)) return rc;
@@ -185,7 +180,7 @@ extern "C" int rh_ring_div_by_last_modulus_many_ntt(rh_ring* r, int round, int l
     rescale_expand_kernel<<<grid, 256, 0, rh_stream(r)>>>(round ? 1 : 0, tmp, buff, level, level, N, r->moduli[level], T);
     if (level > 0) if (int rc = rh_std_ntt_launch(r, buff, buff, npoly, level, 0, false, false, 0)) return rc;
     rescale_finish_kernel<<<grid, 256, 0, rh_stream(r)>>>(buff, level, p0, level + 1, p1, p1_rows, level, N, T);
-    return launched("rescale (NTT domain)");
+    return rh_launch_ok("rescale (NTT domain)");
   }
   // nb > 1: INTT everything, divide nb times in the coefficient domain, NTT what is left (:44-51, :142-150)
   if (int rc = ensure_scratch(r, 1, (size_t)npoly * (level + 1) * N)) return rc;
@@ -203,7 +198,7 @@ extern "C" int rh_ring_div_by_last_modulus_many_ntt(rh_ring* r, int round, int l
   if (int rc = copy_leading_limbs(r, cmp, out_limbs, buff, level + 1, out_limbs, npoly)) return rc;
   if (int rc = rh_ring_ntt_any(r, cmp, cmp, npoly, out_limbs, 0, false)) return rc;
   if (int rc = copy_leading_limbs(r, p1, p1_rows, cmp, out_limbs, out_limbs, npoly)) return rc;
-  return launched("rescale many (NTT domain)");
+  return rh_launch_ok("rescale many (NTT domain)");
 }
 
 // the same with the NTT-domain layout of a 3N ring's data as a per-call argument (see rh_ring_ntt_layout)

@@ -1,0 +1,33 @@
+// stream_kernels.hip.hpp -- the scaffold of the element-wise "row-streaming" kernels (engine.hip, bfv.hip, bgv.hip, ckks.hip, keyswitch.hip):
+// one (poly, limb) row per blockIdx.x so the per-limb constants are wave-uniform, the row's coefficient PAIRS split over blockIdx.y by a
+// grid-stride loop, 16-byte loads and stores, non-temporal when the launch's `nt` says so.  The host half -- which grid, which `nt` -- is
+// rh_stream_grid (engine_internal.hpp).
+#pragma once
+#include "ring_types.hip.hpp"
+
+// 16 bytes at p (16-byte aligned); nt: non-temporal (the launch streams past the Infinity Cache), else the default policy
+typedef u64 rh_u64x2_t __attribute__((ext_vector_type(2)));
+RH_DEV ulonglong2 rh_ld2(const u64* p, bool nt) {
+  if (!nt) return *reinterpret_cast<const ulonglong2*>(p);
+  const rh_u64x2_t v = __builtin_nontemporal_load(reinterpret_cast<const rh_u64x2_t*>(p));
+  return make_ulonglong2(v.x, v.y);
+}
+RH_DEV void rh_st2(u64* p, const ulonglong2& w, bool nt) {
+  if (nt) { rh_u64x2_t v; v.x = w.x; v.y = w.y; __builtin_nontemporal_store(v, reinterpret_cast<rh_u64x2_t*>(p)); }
+  else *reinterpret_cast<ulonglong2*>(p) = w;
+}
+
+// The row of this workgroup in a launch of (npoly * L, chunks) workgroups over blocks of L limbs per poly
+struct StreamRow {
+  u32 row, limb, poly;
+  LimbConsts c;
+  size_t ro;                       // word offset of the row in a dense (npoly, L, n) block
+  RH_DEV StreamRow(const LimbConsts* __restrict__ consts, int L, unsigned n)
+      : row(blockIdx.x), limb(row % (u32)L), poly(row / (u32)L), c(consts[limb]), ro((size_t)row * n) {}
+  // ... in a block with `rows` >= L limbs per poly (a ring.AtLevel view)
+  RH_DEV size_t at(int rows, unsigned n) const { return ((size_t)poly * rows + limb) * n; }
+};
+
+// The loop head over this thread's share of the pairs [pair0, pair1) of its row; pair i is the words 2 i, 2 i + 1
+#define RH_FOR_EACH_PAIR(i, pair0, pair1) \
+  for (unsigned i = (pair0) + blockIdx.y * blockDim.x + threadIdx.x; i < (pair1); i += gridDim.y * blockDim.x)

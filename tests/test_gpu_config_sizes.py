@@ -288,7 +288,7 @@ def test_config4_per_gpu_share_128_ciphertext_pairs(rh, oracle):
 
 
 def test_working_sets_beyond_the_infinity_cache_take_the_non_temporal_bodies(rh, oracle):
-    """launches whose rows exceed 512 MiB run the generated bodies with non-temporal data streams (engine.hip: rh_streams_beyond_cache; the same
+    """launches whose rows exceed 512 MiB run the generated bodies with non-temporal data streams (engine.hip: rh_stream_grid; the same
     instructions with a cache-policy hint): a two-launch forward / inverse transform (70 polys x 16 limbs at N = 2^16 = 560 MiB, not pipelined)
     and DivRoundByLastModulusNTT on the same block (re-expansion column stages + subtract-multiply tile stages), spot rows against the oracle"""
     import torch

@@ -163,3 +163,72 @@ def test_double_rns_scalars_vector_shift_and_monomial(rh):
     ring.MultByMonomial(pa, 1, t1); ring.MultByMonomial(t1, 8, t1); ring.MultByMonomial(pa, 9, po)
     assert np.array_equal(t1.numpy(), po.numpy())
     ring.close()
+
+
+# ---- the degree-1 x degree-1 tensoring: one kernel behind two entry points -----------------------------------------------------------------
+# N = 32: 16 pairs, fewer than one workgroup's 256 threads; N = 2^12: 2048 pairs, two chunks of a row.  Limbs of 61, 36 and 45 bits; the 3N
+# ring (element-wise code sees only its moduli) is the smallest the suite builds.
+TENSOR_RINGS = [("standard", 32), ("standard", 1 << 12), ("3n", 48)]
+_tensor_cases = {}
+
+
+def tensor_case(oracle, OPS, kind, N):
+    """moduli, the operands a0, a1, b0, b1 as (3, limbs, N) blocks -- poly 0 uniform, poly 1 all q_i - 1, poly 2 zero (a) times uniform (b) --
+    and, per mform_first, the reference's call sequence on the oracle (schemes/ckks/evaluator.go:821-834): computed once, read-only"""
+    if (kind, N) not in _tensor_cases:
+        if kind == "3n":
+            from test_gpu_schemes import primes_3n
+            mods = primes_3n(oracle, N, 2)
+        else:
+            from oracle import primes
+            mods = [int(q) for q in primes.gen_moduli(N.bit_length(), [61, 36, 45], [])[0]]
+        rng = np.random.default_rng(N)
+        qs = np.array(mods, dtype=np.uint64)[:, None]
+
+        def operand(zero):
+            u = lambda: np.stack([uniform_mod(rng, q, N) for q in mods])
+            return np.stack([u(), np.broadcast_to(qs - np.uint64(1), (len(mods), N)), np.zeros((len(mods), N), dtype=np.uint64) if zero else u()])
+        a0, a1, b0, b1 = operand(True), operand(True), operand(False), operand(False)
+        z = np.zeros(N, dtype=np.uint64)
+        vop = lambda name, p, r, t, q: oracle.vec_op(OPS[name], p, r, t, 0, 0, q)
+        want = {}
+        for mform_first in (1, 0):
+            c = [np.empty_like(a0) for _ in range(3)]
+            for k in range(3):
+                for i, q in enumerate(mods):
+                    c00, c01 = (vop("MFORM", a0[k, i], None, z, q), vop("MFORM", a1[k, i], None, z, q)) if mform_first else (a0[k, i], a1[k, i])
+                    c[0][k, i] = vop("MUL_MONT", c00, b0[k, i], z, q)
+                    c[2][k, i] = vop("MUL_MONT", c01, b1[k, i], z, q)
+                    c[1][k, i] = vop("MUL_MONT_THEN_ADD", c01, b0[k, i], vop("MUL_MONT", c00, b1[k, i], z, q), q)
+            want[mform_first] = c
+        for arr in [a0, a1, b0, b1] + want[0] + want[1]:
+            arr.setflags(write=False)
+        _tensor_cases[kind, N] = (mods, (a0, a1, b0, b1), want)
+    return _tensor_cases[kind, N]
+
+
+@pytest.mark.parametrize("nt", [0, 2])
+@pytest.mark.parametrize("kind,N", TENSOR_RINGS)
+def test_tensor_degree1_both_doors(rh, oracle, kind, N, nt):
+    """rh_ring_tensor_degree1(mform_first = 1) and rh_ckks_tensor(accumulate 0, square 0) launch one kernel and give the same whole outputs,
+    equal to the oracle's six-call sequence; mform_first = 0 equals its four products, on the 3N ring too; outputs may be inputs"""
+    mods, ops, want = tensor_case(oracle, rh.OPS, kind, N)
+    ring = rh.Ring(N, mods, kind=rh.Matrix3N) if kind == "3n" else rh.Ring(N, mods)
+    ring.set_tuning("nt_streams", nt)
+    up = lambda: [rh.DevicePoly.from_numpy(ring, x) for x in ops]
+    same = lambda polys, w: all(np.array_equal(p.numpy(), x) for p, x in zip(polys, w))
+    L, level = rh.lib(), len(mods) - 1
+    for mform_first in (1, 0):
+        p, c = up(), [ring.NewPoly(3) for _ in range(3)]
+        ring.TensorDegree1(*p, *c, mform_first=bool(mform_first))
+        assert same(c, want[mform_first]), ("tensor_degree1", mform_first)
+        assert same(p, ops), "inputs untouched"
+        ring.TensorDegree1(*p, p[0], c[1], c[2], mform_first=bool(mform_first))          # c0 is a0
+        assert same([p[0], c[1], c[2]], want[mform_first]), ("in place", mform_first)
+    if kind == "standard":
+        p, c = up(), [ring.NewPoly(3) for _ in range(3)]
+        assert L.rh_ckks_tensor(ring._h, level, *[x.ptr for x in p], *[x.ptr for x in c], 3, 0, 0) == 0
+        d = [ring.NewPoly(3) for _ in range(3)]
+        ring.TensorDegree1(*p, *d)
+        assert same(c, [x.numpy() for x in d]) and same(c, want[1]), "rh_ckks_tensor"
+    ring.close()

@@ -21,7 +21,9 @@ NT_ARG = {"ntt_fwd_onepass_asm": 1, "ntt_inv_onepass_asm": 1, "ntt_fwd_cols_asm"
           "ntt_polymul_tile_asm": 0, "ntt_fwd_fused_asm": 2, "ntt_inv_fused_asm": 3, "ntt_ci_fwd_fused_asm": 1, "ntt_ci_inv_fused_asm": 1,
           "ntt_polymul_fused_asm": 1}
 PIPELINED = ("ntt_fwd_fused_asm", "ntt_inv_fused_asm", "ntt_ci_fwd_fused_asm", "ntt_ci_inv_fused_asm", "ntt_polymul_fused_asm")
-RUNTIME_NT = ("vec_op_packed", "tensor_degree1_kernel", "bgv_tensor_kernel", "bgv_mul_plain_kernel", "bgv_axpby_kernel", "bfv_tensor_kernel")
+# the row-streaming kernels of csrc/stream_kernels.hip.hpp: non-temporal by a runtime argument
+RUNTIME_NT = ("vec_op_packed", "bfv_tensor_kernel", "bgv_tensor_kernel", "bgv_mul_plain_kernel", "bgv_axpby_kernel",
+              "ckks_tensor_kernel", "ckks_mul_plain_kernel", "ckks_scalar_kernel", "ckks_scale_then_add_kernel")
 
 
 def short(name):
