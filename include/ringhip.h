@@ -455,6 +455,49 @@ int rh_ckks_scale_then_add(rh_ring* r, int level, const uint64_t* a0_dev, const 
                            const uint64_t* b1_dev, const uint64_t* b2_dev, uint64_t* out0_dev, uint64_t* out1_dev, uint64_t* out2_dev, int npoly,
                            const uint64_t* ratio, int sub, int scaled_is_b);
 
+/* ---- CKKS encoder: the float64 path of schemes/ckks/encoder.go on device batches of nvec vectors ------------------------------------
+ * A handle on a STANDARD ring.  Refused by name (RH_ERR_UNSUPPORTED): conjugate-invariant rings, 3N rings, prec > 53 (the *big.Float /
+ * *bignum.Complex encoder), rh_ckks_decode with batched = 0 at a level that is neither 0 nor the ring's top level.  Values are IEEE doubles, complex values interleaved (re, im); a block of
+ * values is (nvec, 2^log_slots) complex, a plaintext block (nvec, level+1, N) words.  Calls are asynchronous on the ring's stream and lock
+ * the handle for the enqueue only; the scratch (two value blocks, one poly block) belongs to the handle and grows with the largest shape
+ * seen -- after rh_ckks_encoder_reserve(nvec) no call on up to nvec vectors allocates.  Finite inputs are assumed.
+ *   rh_ckks_encoder_create   NewEncoder (encoder.go:72-120).  roots: the NthRoot + 1 = 2N + 1 complex doubles of GetRootsComplex128 (utils.go:53-77),
+ *                            RECEIVED like every constant of this engine: results are bit-exact for the table given (Go's math.Cos is not
+ *                            libm's cos).  rotGroup (5^j mod 2N) and the CRT tables of the decoder are computed here.
+ *   rh_ckks_encoder_set_tuning  "ckks_fft_lds_log": the largest log2 block of a transform kept in one workgroup's LDS, 1 .. 12 (default 12:
+ *                            64 KiB); longer vectors run their leading (IFFT) / trailing (FFT) stages as global-memory launches.  Same bits.
+ *   rh_ckks_special_ifft / _fft  SpecialIFFTDouble / SpecialFFTDouble (ckks_vector_ops.go:18-76; the unrolled-8 variants compute the same
+ *                            butterflies), in place; the IFFT's division by n is Go's complex128 division by complex(n, 0).
+ *   rh_ckks_encode           embedDouble (encoder.go:204-320) from a FULL block of values (a caller with fewer values pads with zeros,
+ *                            :292-295): copy, IFFT, Complex128ToFixedPointCRT (utils.go:130-234) with the stride-N/(2 slots) spread of
+ *                            NTTSparseAndMontgomery (core/rlwe/utils.go:187-245), MForm if is_montgomery, Ring.NTT if is_ntt.  With neither
+ *                            flag the words are the reference's own (positive values unreduced up to 2^61 - 1, the word q for a negative
+ *                            multiple of q); with either they are the canonical residues the reference's transform / MForm gives.
+ *                            values_dev is not modified.
+ *   rh_ckks_encode_coeffs    Encode with IsBatched = false (:147-170): Float64ToFixedPointCRT of (nvec, nvals) doubles, nvals <= N, NTT if is_ntt
+ *   rh_ckks_decode           decodePublic with IsBatched (:476-575): INTT if is_ntt, polyToComplexNoCRT / polyToComplexCRT (:796-1003) with the
+ *                            integer rebuilt exactly and rounded to nearest even (scaleDown, scaling.go:46-52), the FFT, and for
+ *                            logprec != 0 math.Round(x * 2^logprec) / 2^logprec on both parts -- on the real part alone, the imaginary one
+ *                            zeroed, with real_only (the []float64 output; zeroed whatever logprec is).  values_dev: (nvec, 2^log_slots)
+ *                            complex, written whole; poly_dev is not modified.
+ *                            batched = 0: plaintextToFloat (:467-472, polyToFloatNoCRT / polyToFloatCRT :1006-1185), the inverse of
+ *                            rh_ckks_encode_coeffs: INTT if is_ntt, then every coefficient as its centred integer / scale; values_dev is
+ *                            (nvec, N) DOUBLES, log_slots, logprec and real_only are not used (the reference ignores logprec there, :731).
+ *                            Level 0 and the ring's top level only: polyToFloatCRT reconstructs over the encoder's FULL ring, so at a
+ *                            level in between the reference's result depends on stale limbs of its buffer -- RH_ERR_UNSUPPORTED. */
+typedef struct rh_ckks_encoder rh_ckks_encoder;
+int rh_ckks_encoder_create(rh_ckks_encoder** out, rh_ring* ring, const double* roots, size_t nroots, unsigned prec);
+void rh_ckks_encoder_destroy(rh_ckks_encoder* e);
+int rh_ckks_encoder_reserve(rh_ckks_encoder* e, int nvec);
+int rh_ckks_encoder_set_tuning(rh_ckks_encoder* e, const char* key, long value);
+int rh_ckks_special_ifft(rh_ckks_encoder* e, double* values_dev, int log_slots, int nvec);
+int rh_ckks_special_fft(rh_ckks_encoder* e, double* values_dev, int log_slots, int nvec);
+int rh_ckks_encode(rh_ckks_encoder* e, int level, int log_slots, double scale, const double* values_dev, int nvec, uint64_t* out_dev,
+                   int is_ntt, int is_montgomery);
+int rh_ckks_encode_coeffs(rh_ckks_encoder* e, int level, double scale, const double* values_dev, int nvals, int nvec, uint64_t* out_dev, int is_ntt);
+int rh_ckks_decode(rh_ckks_encoder* e, int level, int log_slots, double scale, double logprec, int is_ntt, int batched, int real_only,
+                   const uint64_t* poly_dev, int nvec, double* values_dev);
+
 /* ---- limb-sharded hybrid key switch (BASELINE config 5): one process per GPU owns a subset of the limbs
  * of Q and P and the matching slice of the evaluation key.  Same arithmetic as rh_bext_gadget_product, cut where
  * reconstructRNS (ring/basis_extension.go:550-594) needs limbs of other owners; the exchange (an all-gather of the

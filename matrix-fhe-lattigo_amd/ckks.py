@@ -1,6 +1,7 @@
 """Host-side mirror of ckks.Evaluator, schemes/ckks/evaluator.go, on device-resident batches in the NTT domain: call sequences and the scale
-bookkeeping only -- the arithmetic is the HIP library's (csrc/ckks.hip and the ring entry points); encoders and key generation stay with
-the reference, so slice operands ([]complex128 / []float64 ...) are refused by name.
+bookkeeping only -- the arithmetic is the HIP library's (csrc/ckks.hip and the ring entry points); key generation stays with the reference.
+Slice operands ([]complex128 / []float64) are encoded on the device when the evaluator is given an Encoder (the class at the end of this
+file, csrc/ckks_encoder.hip) and refused by name when it is not.
 
   Add(New) / Sub(New)   :59-244      evaluateInPlace   :246-431     evaluateWithScalar  :433-447     ScaleUp / SetScale  :449-478
   DropLevel(New)        :480-492     Rescale           :500-535     RescaleTo           :543-602     Mul(New)            :604-728
@@ -132,8 +133,9 @@ class Evaluator:
 
     FUSED_DEFAULT = {"tensor": True, "mul_plain": True, "scalar": False, "scale_then_add": True}   # profiles/ckks_ops.json: the scalar kernel is not faster than the four half-row launches
 
-    def __init__(self, ringQ, ringP=None, rlk=None, levels_consumed_per_rescaling=1, galois_keys=None, fused=None, encoding_precision=53):
+    def __init__(self, ringQ, ringP=None, rlk=None, levels_consumed_per_rescaling=1, galois_keys=None, fused=None, encoding_precision=53, encoder=None):
         self.ringQ, self.ringP, self.rlk = ringQ, ringP, rlk
+        self.encoder = encoder             # ckks.Encoder: with one, slice operands take the reference's slice branches; without, they are refused
         self.nb_rescales = int(levels_consumed_per_rescaling)
         self.fused = dict(self.FUSED_DEFAULT) if fused is None else {k: bool(fused) for k in self.FUSED_DEFAULT}
         self.fused_tensor = fused is None or bool(fused)   # regular ct x ct case: rh_ring_tensor_degree1 instead of six element-wise launches (same bits)
@@ -183,11 +185,21 @@ class Evaluator:
         return level
 
     def _refuse(self, op1, who):
+        if _is_slice(op1) and self.encoder is not None:
+            return
         if _is_slice(op1):
             raise RingHipError("cannot %s: op1 of type %s (a slice, []complex128 / []float64 ...) needs the CKKS encoder, which the device path does not build"
                                % (who, type(op1).__name__))
         if not (_is_scalar(op1) or isinstance(op1, Ciphertext)):
             raise RingHipError("cannot %s: invalid op1.(type): must be a Ciphertext, int, float, complex or Fraction, but is %s" % (who, type(op1).__name__))
+
+    def _encode_slice(self, op0, op1, level, scale):
+        """the plaintext of the slice branches (:112-126, :697-718, :1021-1035): eval.buffQ[0] at op0's level with op0's metadata and the scale
+        given, the vector encoded into it on the device (one vector shared by the batch, or one per ciphertext)"""
+        pt = Plaintext(self._buffer("buffQ0", self.ringQ.AtLevel(level), op0.Value[0].npoly, level + 1), scale,
+                       getattr(op0, "LogDimensions", self.encoder.LogMaxSlots), is_ntt=op0.IsNTT, is_montgomery=getattr(op0, "IsMontgomery", False))
+        self.encoder.Encode(op1, pt)
+        return pt
 
     def _qs(self, level):
         return [int(q) for q in self.ringQ.moduli[:level + 1]]
@@ -259,6 +271,9 @@ class Evaluator:
                     rq.CopyLvl(op0.Value[i], opOut.Value[i])
             opOut.Scale, opOut.IsNTT = scale0, True
             return
+        if _is_slice(op1):                                                         # (:103-129, :199-225)
+            level = self._operands(who, op0, opOut)
+            op1 = self._encode_slice(op0, op1, level, self._scale(op0, who))
         level = self._operands(who, op0, op1, opOut)
         c0Scale, c1Scale = self._scale(op0, who), self._scale(op1, who)
         d0, d1 = op0.Degree(), op1.Degree()
@@ -459,6 +474,12 @@ class Evaluator:
         self._refuse(op1, "Mul")
         if _is_scalar(op1):
             return self._mul_scalar(op0, op1, opOut, "Mul")
+        if _is_slice(op1):                                                         # (:685-723)
+            level = self._operands("Mul", op0, opOut)
+            self._scale(op0, "Mul")
+            if opOut.Degree() != op0.Degree():
+                raise RingHipError("cannot Mul: opOut must have degree %d" % op0.Degree())
+            op1 = self._encode_slice(op0, op1, level, self._rescale_scale(level))
         self._scale(op0, "Mul"), self._scale(op1, "Mul")
         self.MulRelin(op0, op1, opOut, relin=False)
 
@@ -486,6 +507,8 @@ class Evaluator:
         A scalar op1 goes to Mul (:778-781).  Operands that carry scales give opOut their product (:790)."""
         if not isinstance(op1, Ciphertext):
             self._refuse(op1, "MulRelin")
+            if _is_slice(op1):
+                return self.Mul(op0, op1, opOut)                                   # (:778-781)
             return self._mul_scalar(op0, op1, opOut, "MulRelin")
         if not (op0.IsNTT and op1.IsNTT):
             raise RingHipError("MulRelin: operands must be in the NTT domain")
@@ -560,6 +583,17 @@ class Evaluator:
         scale0, scaleOut = self._scale(op0, who), self._scale(opOut, who)
         if opOut.Degree() != op0.Degree():
             raise RingHipError("cannot MulThenAdd: opOut must have degree %d" % op0.Degree())
+        if _is_slice(op1):                                                         # (:986-1039)
+            cmp = scale0.Cmp(scaleOut)
+            if cmp == 0:
+                scaleRLWE = self._rescale_scale(level)
+                self._mul_scalar(opOut, int(scaleRLWE.Value), opOut, who)          # eval.Mul(opOut, scaleInt, opOut)
+                opOut.Scale = scaleOut.Mul(scaleRLWE)
+            elif cmp == -1:
+                scaleRLWE = scaleOut.Div(scale0)
+            else:
+                raise RingHipError("cannot MulThenAdd: op0.Scale > opOut.Scale is not supported")
+            return self.MulThenAdd(op0, self._encode_slice(op0, op1, level, scaleRLWE), opOut)
         cmplx = to_complex(op1, self.encoding_precision)
         cmp = scale0.Cmp(scaleOut)
         if cmp == 0:                                                               # (:957-974)
@@ -700,3 +734,251 @@ class Evaluator:
         opOut = {i: self._new(1, ctIn) for i in rotations}
         self.RotateHoisted(ctIn, rotations, opOut)
         return opOut
+
+
+# ---- ckks.Encoder, schemes/ckks/encoder.go: the float64 path (prec <= 53) on standard rings -------------------------------------------------
+def GetRootsComplex128(NthRoot):
+    """utils.go:53-77 by its rule: one cosine per entry of the first quarter, the rest by symmetry; (NthRoot + 1, 2) float64 (re, im).  The
+    cosine is libm's; Go's math.Cos is pure Go and may differ from it in the last place, so a Go caller hands its own table to
+    rh_ckks_encoder_create: the device is bit-exact for a GIVEN table."""
+    import math
+    m = int(NthRoot)
+    quarm = m >> 2
+    r = np.zeros((m + 1, 2), dtype=np.float64)
+    angle = 2 * 3.141592653589793 / float(m)
+    for i in range(quarm):
+        r[i, 0] = math.cos(angle * float(i))
+    for i in range(quarm):
+        r[quarm - i, 1] += r[i, 0]
+    for i in range(1, quarm + 1):
+        r[i + quarm] = (-r[quarm - i, 0], r[quarm - i, 1])
+        r[i + 2 * quarm] = (-r[i, 0], -r[i, 1])
+        r[i + 3 * quarm] = (r[quarm - i, 0], -r[quarm - i, 1])
+    r[m] = r[0]
+    return r
+
+
+class DeviceValues:
+    """(nvec, n) complex128 -- or float64 with complex=False -- on the device: the []complex128 / []float64 of a batch of vectors"""
+
+    def __init__(self, ring, nvec, n, complex=True):
+        import ctypes as C
+        self.ring, self.nvec, self.n, self.complex = ring, int(nvec), int(n), bool(complex)
+        self.words = self.nvec * self.n * (2 if complex else 1)
+        p = C.c_void_p()
+        _check(lib().rh_dev_alloc(ring._h, max(self.words, 1), C.byref(p)))
+        self.ptr = int(p.value)
+
+    @classmethod
+    def from_numpy(cls, ring, arr):
+        arr = np.asarray(arr)
+        cplx = np.iscomplexobj(arr)
+        arr = np.ascontiguousarray(arr, dtype=np.complex128 if cplx else np.float64)
+        if arr.ndim == 1:
+            arr = arr[None]
+        assert arr.ndim == 2, arr.shape
+        v = cls(ring, arr.shape[0], arr.shape[1], cplx)
+        if v.words:
+            _check(lib().rh_dev_upload(ring._h, v.ptr, _p(arr.view(np.uint64).reshape(-1)), v.words))
+        return v
+
+    def numpy(self):
+        out = np.empty(self.words, dtype=np.uint64)
+        if self.words:
+            _check(lib().rh_dev_download(self.ring._h, _p(out), self.ptr, self.words))
+        return out.view(np.complex128 if self.complex else np.float64).reshape(self.nvec, self.n)
+
+    def free(self):
+        if self.ptr:
+            lib().rh_dev_free(None, self.ptr)
+            self.ptr = 0
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class Plaintext(Ciphertext):
+    """rlwe.Plaintext: one poly block (npoly vectors) with its MetaData -- Scale, LogDimensions (the log2 of the slot count; the reference's
+    Rows is always 0 for CKKS), IsNTT, IsMontgomery, IsBatched -- carried the way Ciphertext carries Scale"""
+
+    def __init__(self, poly, scale, log_slots, is_ntt=True, is_montgomery=False, is_batched=True):
+        Ciphertext.__init__(self, [poly], is_ntt=is_ntt)
+        self.Scale = scale if isinstance(scale, Scale) else Scale(scale)
+        self.LogDimensions = int(log_slots)
+        self.IsMontgomery, self.IsBatched = bool(is_montgomery), bool(is_batched)
+
+
+class Encoder:
+    """ckks.Encoder on device batches: Encode / Decode / DecodePublic / Embed / FFT / IFFT of nvec vectors at once (csrc/ckks_encoder.hip).
+    Refused by name: conjugate-invariant and 3N rings, precision > 53 (the *big.Float / *bignum.Complex path), Decode with IsBatched = false
+    at a level that is neither 0 nor the ring's top level."""
+
+    def __init__(self, ringQ, precision=53, roots=None):
+        import ctypes as C
+        self.ringQ, self.prec = ringQ, int(precision)
+        self._h = None
+        if self.prec < 0:
+            raise RingHipError("cannot NewEncoder: negative precision")
+        self.m = 2 * ringQ.N
+        r = np.ascontiguousarray(GetRootsComplex128(self.m) if roots is None else roots, dtype=np.float64)
+        h = C.c_void_p()
+        _check(lib().rh_ckks_encoder_create(C.byref(h), ringQ._h, r.ctypes.data_as(C.POINTER(C.c_double)), r.size // 2, self.prec))
+        self._h = h
+        self.LogMaxSlots = ringQ.N.bit_length() - 2
+        import threading
+        self._tls = threading.local()      # per host thread: the upload blocks host values go through, kept so that no call frees device memory
+
+    def close(self):
+        if self._h:
+            lib().rh_ckks_encoder_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def Prec(self):
+        return self.prec
+
+    def reserve(self, nvec):
+        _check(lib().rh_ckks_encoder_reserve(self._h, int(nvec)))
+
+    def set_tuning(self, key, value):
+        _check(lib().rh_ckks_encoder_set_tuning(self._h, key.encode(), int(value)))
+
+    def NewPlaintext(self, level, scale, nvec=1, log_slots=None, is_ntt=True, is_montgomery=False, is_batched=True):
+        return Plaintext(self.ringQ.AtLevel(level).NewPoly(nvec), scale, self.LogMaxSlots if log_slots is None else log_slots,
+                         is_ntt, is_montgomery, is_batched)
+
+    # ---- values on their way to the device -----------------------------------------------------------------------------------------------
+    def _block(self, values, nvec, slots, who):
+        """(nvec, slots) complex block on the device from a slice (one vector, shared by the batch), a (nvec, n) array or a DeviceValues"""
+        if isinstance(values, DeviceValues):
+            if not values.complex or values.n != slots or values.nvec != nvec:
+                raise RingHipError("cannot %s: a device block of values must be complex128 of shape (%d, %d)" % (who, nvec, slots))
+            return values
+        a = np.asarray(values)
+        if a.dtype == object or not (np.issubdtype(a.dtype, np.number)):
+            raise RingHipError("cannot %s: values.(Type) must be []complex128 or []float64 ([]*bignum.Complex and []*big.Float stay with the reference), but is %s"
+                               % (who, type(values).__name__))
+        if a.ndim == 1:
+            a = np.broadcast_to(a, (nvec, a.shape[0]))
+        if a.ndim != 2 or a.shape[0] != nvec:
+            raise RingHipError("cannot %s: %d vectors given for a block of %d polys" % (who, a.shape[0] if a.ndim == 2 else -1, nvec))
+        maxCols = self.ringQ.N >> 1
+        if a.shape[1] > maxCols or a.shape[1] > slots:
+            raise RingHipError("cannot %s: ensure that #values (%d) <= slots (%d) <= maxCols (%d)" % (who, a.shape[1], slots, maxCols))
+        full = np.zeros((nvec, slots), dtype=np.complex128)                      # zeroes all other values (:292-295)
+        full[:, :a.shape[1]] = a
+        return self._upload(full)
+
+    def _upload(self, arr):
+        """host values -> this thread's upload block of that shape (allocated once).  The copy is ordered on the ring's stream behind the
+        calls that still read the block, and nothing is freed, so a call from host values costs the copy and no device-wide synchronisation."""
+        cplx = np.iscomplexobj(arr)
+        arr = np.ascontiguousarray(arr, dtype=np.complex128 if cplx else np.float64)
+        pool = self._tls.__dict__.setdefault("blocks", {})
+        key = (arr.shape, cplx)
+        dv = pool.get(key)
+        if dv is None:
+            dv = pool[key] = DeviceValues(self.ringQ, arr.shape[0], arr.shape[1], cplx)
+        if dv.words:
+            _check(lib().rh_dev_upload(self.ringQ._h, dv.ptr, _p(arr.view(np.uint64).reshape(-1)), dv.words))
+        return dv
+
+    def _log_slots(self, log_slots, who):
+        if log_slots < 0 or log_slots > self.LogMaxSlots:
+            raise RingHipError("cannot %s: logSlots (%d) must be greater or equal to %d and smaller than %d" % (who, log_slots, 0, self.LogMaxSlots))
+        return int(log_slots)
+
+    # ---- Encode / Embed (:141-320) -------------------------------------------------------------------------------------------------------
+    def Embed(self, values, metadata, polyOut):
+        """embedDouble: metadata is anything with Scale, LogDimensions, IsNTT and IsMontgomery (a Plaintext, a Ciphertext given them);
+        polyOut a DevicePoly whose limb count sets the level"""
+        logs = self._log_slots(metadata.LogDimensions, "Embed")
+        scale = metadata.Scale if isinstance(metadata.Scale, Scale) else Scale(metadata.Scale)
+        block = self._block(values, polyOut.npoly, 1 << logs, "Embed")
+        _check(lib().rh_ckks_encode(self._h, polyOut.limbs - 1, logs, scale.Float64(), block.ptr, polyOut.npoly, polyOut.ptr,
+                                    1 if metadata.IsNTT else 0, 1 if getattr(metadata, "IsMontgomery", False) else 0))
+
+    def Encode(self, values, pt):
+        if pt.IsBatched:
+            return self.Embed(values, pt, pt.Value[0])
+        p = pt.Value[0]
+        if isinstance(values, DeviceValues):
+            if values.complex or values.nvec != p.npoly:
+                raise RingHipError("cannot Encode: supported values.(type) for IsBatched=False is []float64")
+            dv = values
+        else:
+            a = np.asarray(values)
+            if np.iscomplexobj(a) or a.dtype == object:
+                raise RingHipError("cannot Encode: supported values.(type) for IsBatched=False is []float64 or []*big.Float, but %s was given" % a.dtype)
+            if a.ndim == 1:
+                a = np.broadcast_to(a, (p.npoly, a.shape[0]))
+            if a.shape[-1] > self.ringQ.N:
+                raise RingHipError("cannot Encode: maximum number of values is %d but len(values) is %d" % (self.ringQ.N, a.shape[-1]))
+            dv = self._upload(np.ascontiguousarray(a, dtype=np.float64).reshape(p.npoly, -1))
+        _check(lib().rh_ckks_encode_coeffs(self._h, p.limbs - 1, pt.Scale.Float64(), dv.ptr, dv.n, p.npoly, p.ptr, 1 if pt.IsNTT else 0))
+
+    # ---- Decode (:177-186, :476-575) -------------------------------------------------------------------------------------------------------
+    def DecodePublic(self, pt, values=None, logprec=0):
+        """values: None (a new (nvec, slots) complex128 array is returned), a numpy array of dtype complex128 or float64 -- (nvec, k), or (k,)
+        for a single vector -- filled with up to slots values per vector (the real parts for float64) and returned, or a complex
+        DeviceValues of shape (nvec, slots), filled on the device.  IsBatched = false (plaintextToFloat, :467-472): the N coefficients
+        over the scale, real; values None (a new (nvec, N) float64 array), a numpy array as above, or a float64 DeviceValues of shape
+        (nvec, N); level 0 and the ring's top level only (csrc/ckks_encoder.hip says why), and logprec is not used (:731)."""
+        batched = bool(pt.IsBatched)
+        logs = self._log_slots(pt.LogDimensions, "Decode")
+        p = pt.Value[0]
+        cols = 1 << logs if batched else self.ringQ.N
+        on_dev = isinstance(values, DeviceValues)
+        real = values is not None and not on_dev and not np.iscomplexobj(values)
+        if on_dev and (values.complex != batched or values.n != cols or values.nvec != p.npoly):
+            raise RingHipError("cannot Decode: a device block of values must be %s of shape (%d, %d)" % ("complex128" if batched else "float64", p.npoly, cols))
+        if values is not None and not on_dev:
+            if not isinstance(values, np.ndarray) or values.dtype not in (np.float64, np.complex128):
+                raise RingHipError("cannot decode: values.(type) accepted are []complex128 and []float64 (numpy arrays), but is %s" % type(values).__name__)
+            if not (values.ndim == 2 and values.shape[0] == p.npoly) and not (values.ndim == 1 and p.npoly == 1):
+                raise RingHipError("cannot Decode: values of shape %s for a plaintext block of %d vectors: give (%d, k)" % (values.shape, p.npoly, p.npoly))
+        dv = values if on_dev else self._tls.__dict__.setdefault("blocks", {}).get(((p.npoly, cols), batched))
+        if dv is None:
+            dv = self._tls.blocks[((p.npoly, cols), batched)] = DeviceValues(self.ringQ, p.npoly, cols, batched)
+        _check(lib().rh_ckks_decode(self._h, p.limbs - 1, logs if batched else 0, pt.Scale.Float64(), float(logprec), 1 if pt.IsNTT else 0,
+                                    1 if batched else 0, 1 if real else 0, p.ptr, p.npoly, dv.ptr))
+        if on_dev:
+            return values
+        got = dv.numpy()
+        if values is None:
+            return got
+        k = min(values.shape[-1], cols)
+        values.reshape(p.npoly, -1)[:, :k] = (got.real if real or not batched else got)[:, :k]
+        return values
+
+    def Decode(self, pt, values=None):
+        return self.DecodePublic(pt, values, 0)
+
+    # ---- the transforms alone (:738-793) -----------------------------------------------------------------------------------------------
+    def _transform(self, values, logN, fn, who):
+        logN = self._log_slots(int(logN), who)
+        if isinstance(values, DeviceValues):
+            if not values.complex or values.n != 1 << logN:
+                raise RingHipError("cannot %s: a device block of values must be complex128 with %d columns" % (who, 1 << logN))
+            _check(fn(self._h, values.ptr, logN, values.nvec))
+            return values
+        a = np.asarray(values, dtype=np.complex128)
+        if a.shape[-1] != 1 << logN:
+            raise RingHipError("cannot %s: %d values for logN = %d" % (who, a.shape[-1], logN))
+        dv = self._upload(a.reshape(-1, a.shape[-1]))
+        _check(fn(self._h, dv.ptr, logN, dv.nvec))
+        return dv.numpy().reshape(a.shape)
+
+    def IFFT(self, values, logN):
+        return self._transform(values, logN, lib().rh_ckks_special_ifft, "IFFT")
+
+    def FFT(self, values, logN):
+        return self._transform(values, logN, lib().rh_ckks_special_fft, "FFT")

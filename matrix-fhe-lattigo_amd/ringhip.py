@@ -138,6 +138,11 @@ def lib():
         "rh_bgv_axpby": (i, [vp, i, vp, vp, vp, i, U64P, U64P, i]),
         "rh_ckks_tensor": (i, [vp, i] + [vp] * 7 + [i, i, i]), "rh_ckks_mul_plain": (i, [vp, i] + [vp] * 7 + [i, i]),
         "rh_ckks_scalar": (i, [vp, i, i] + [vp] * 6 + [i, U64P, U64P]), "rh_ckks_scale_then_add": (i, [vp, i] + [vp] * 9 + [i, U64P, i, i]),
+        "rh_ckks_encoder_create": (i, [C.POINTER(vp), vp, C.POINTER(C.c_double), sz, C.c_uint]), "rh_ckks_encoder_destroy": (None, [vp]),
+        "rh_ckks_encoder_reserve": (i, [vp, i]), "rh_ckks_encoder_set_tuning": (i, [vp, C.c_char_p, C.c_long]),
+        "rh_ckks_special_ifft": (i, [vp, vp, i, i]), "rh_ckks_special_fft": (i, [vp, vp, i, i]),
+        "rh_ckks_encode": (i, [vp, i, i, C.c_double, vp, i, vp, i, i]), "rh_ckks_encode_coeffs": (i, [vp, i, C.c_double, vp, i, i, vp, i]),
+        "rh_ckks_decode": (i, [vp, i, i, C.c_double, C.c_double, i, i, i, vp, i, vp]),
         "rh_kshard_create": (i, [C.POINTER(vp), vp, vp, U64P, i, U64P, i, C.POINTER(i), i, C.POINTER(i), i]),
         "rh_kshard_destroy": (None, [vp]), "rh_kshard_num_digits": (i, [vp]),
         "rh_kshard_digit_range": (i, [vp, i, C.POINTER(i), C.POINTER(i)]),

@@ -4,7 +4,9 @@ transform at the BASELINE config sizes, each against its algorithmic bytes (SURV
 `bench_ops.py bfv [OUT.json]` runs the BFV group alone (quantize composed vs fused, the whole scale-invariant multiply) and writes
 profiles/bfv_ops.json (or OUT.json); `bench_ops.py bgv [OUT.json]` the BGV group (standard tensoring and multiply-accumulate, one kernel each
 against the reference's sequence of ring calls) and writes profiles/bgv_ops.json; `bench_ops.py ckks [OUT.json]` the CKKS group
-(MulThenAdd, MulRelinThenAdd, scale-matched Add and scalar Mul at the config 5 ring, fused against composed) and writes profiles/ckks_ops.json."""
+(MulThenAdd, MulRelinThenAdd, scale-matched Add and scalar Mul at the config 5 ring, fused against composed) and writes profiles/ckks_ops.json;
+`bench_ops.py ckks_encoder [OUT.json]` the CKKS encoder (Encode, Decode and the two transforms at N = 2^16, 24 limbs, full slots, 64 vectors)
+against its algorithmic bytes, and writes profiles/ckks_encoder.json."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -257,6 +259,66 @@ def ckks_group(out_path):
     for ev in evs.values():
         ev.close()
     rq.close(); rp.close()
+
+
+def ckks_encoder_group(out_path):
+    """The CKKS encoder (csrc/ckks_encoder.hip) at N = 2^16, 24 limbs of Qi60, full slots (2^15), nvec = 64, device-resident values and
+    plaintexts: Encode and Decode in the NTT domain, and the two transforms alone.  There is no earlier implementation to compare with, so
+    each line stands against its algorithmic bytes: per vector 16 slots in and 8 L N out for the quantizer plus 16 N per limb for the
+    Ring.NTT pass (Encode); the mirror image for Decode (16 N per limb for Ring.INTT, 8 L 2 slots gathered, 16 slots out); 16 slots in and
+    16 slots out for a transform alone -- its global stages (3 at 2^15 slots with 2^12-value LDS blocks) are overhead against that figure.
+    Medians of `rounds` alternating windows of `reps` calls, device events, 2 warm-up calls per window."""
+    import statistics
+    N, L, B, rounds, reps = 1 << 16, 24, 64, 7, 5
+    logs, slots = 15, 1 << 15
+    Q = QI60[:L]
+    rq = rh.Ring(N, Q); rq.set_stream(stream.cuda_stream)
+    enc = rh.ckks.Encoder(rq)
+    enc.reserve(B)
+    rng = np.random.default_rng(0)
+    host = rng.uniform(-1, 1, (B, slots)) + 1j * rng.uniform(-1, 1, (B, slots))
+    vals, work, out = (rh.ckks.DeviceValues.from_numpy(rq, host) for _ in range(3))
+    pt = enc.NewPlaintext(L - 1, 2.0 ** 45, nvec=B)
+    enc.Encode(vals, pt)
+    enc.Decode(pt, out)
+    err = float(np.max(np.abs(out.numpy() - host)))
+    assert err < 2.0 ** -28, "Encode then Decode lost the values: %g" % err      # log2(scale) - (logN + 2) = 27 bits (ckks_test.go:272-298)
+    per_ntt = 16.0 * N * L
+    cases = {
+        "Encode (IFFT, quantize, NTT)": (lambda: enc.Encode(vals, pt), 16.0 * slots + 8.0 * L * N + per_ntt),
+        "Decode (INTT, CRT to double, FFT)": (lambda: enc.Decode(pt, out), per_ntt + 8.0 * L * 2 * slots + 16.0 * slots),
+        "special IFFT alone": (lambda: enc.IFFT(work, logs), 32.0 * slots),
+        "special FFT alone": (lambda: enc.FFT(work, logs), 32.0 * slots),
+    }
+    times = {k: [] for k in cases}
+    for _ in range(rounds):
+        for name, (fn, _) in cases.items():
+            times[name].append(timed(fn, reps=reps))
+    results = []
+    for name, (_, vec_bytes) in cases.items():
+        v = times[name]
+        ms = statistics.median(v)
+        gbs = vec_bytes * B / (ms * 1e-3) / 1e9
+        results.append({"op": name, "ms_median": round(ms, 4), "ms_min": round(min(v), 4), "ms_max": round(max(v), 4),
+                        "vectors_per_s": round(B / (ms * 1e-3), 1), "algorithmic_bytes_per_vector": vec_bytes,
+                        "algorithmic_GBps": round(gbs, 1), "frac_of_8TBps": round(gbs / PEAK, 4)})
+    from bench import csrc_tree_hash
+    res = {"device": torch.cuda.get_device_name(0), "csrc_tree": csrc_tree_hash(), "shape": {"N": N, "limbs_Q": L, "log_slots": logs, "nvec": B},
+           "round_trip_max_abs_error": err,
+           "method": "%d alternating windows of %d calls each, device events, 2 warm-up calls per window; clocks left to the driver's default governor"
+                     % (rounds, reps),
+           "results": results}
+    with open(out_path, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(res, indent=1))
+    enc.close()
+    rq.close()
+
+
+if sys.argv[1:2] == ["ckks_encoder"]:
+    ckks_encoder_group(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "ckks_encoder.json"))
+    sys.exit(0)
 
 
 if sys.argv[1:2] == ["ckks"]:
