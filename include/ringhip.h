@@ -498,6 +498,46 @@ int rh_ckks_encode_coeffs(rh_ckks_encoder* e, int level, double scale, const dou
 int rh_ckks_decode(rh_ckks_encoder* e, int level, int log_slots, double scale, double logprec, int is_ntt, int batched, int real_only,
                    const uint64_t* poly_dev, int nvec, double* values_dev);
 
+/* ---- BGV encoder: schemes/bgv/encoder.go on device batches of nvec vectors -----------------------------------------------------------
+ * A handle on a STANDARD ringQ and the plaintext ring ringT the caller makes: one modulus T, degree n = min(N, order(T) / 2) with order(T)
+ * the largest power of two dividing T - 1 (bgv/params.go:110-121).  Values are uint64 words -- []uint64, or []int64 in two's complement
+ * with is_signed -- in blocks of (nvec, nvals), nvals <= n; a block modulo T is (nvec, n) words, a plaintext block (nvec, level+1, N).
+ * Calls are asynchronous on ringQ's stream (ringT and the target ring are pinned to it for the call) and lock the handle for the enqueue
+ * only; the scratch belongs to the handle -- after rh_bgv_encoder_reserve(nvec) no call on up to nvec vectors allocates.
+ *   rh_bgv_encoder_create    NewEncoder (:49-96).  Refused by name: a degree of ringT that does not divide N, T a modulus of Q,
+ *                            gcd(T, Q) != 1, order(T) < 16; conjugate-invariant and 3N rings (RH_ERR_UNSUPPORTED).  indexMatrix
+ *                            (permuteMatrix :98-121) and its inverse, T^-1 mod q_i, the ModUp constants onto {T} per level (:61-65) and the
+ *                            mixed-radix tables of the exact branch are computed here.
+ *   rh_bgv_encoder_set_tuning  "fused": 1 the lift and Q to T as one kernel each; 0 the reference's own sequence of ring and basis-extension
+ *                            calls; -1 (the state at create) whichever the measurement favours for each -- the kernel, for all of
+ *                            them, in profiles/bgv_encoder.json.  "fused_lift" / "fused_q2t" set one of the two.  Same bits.  (The
+ *                            branch the reference takes through math/big has one form.)
+ *   rh_bgv_encode_ring_t     EncodeRingT (:187-246): pT[indexMatrix[i]] = values[i] modulo T, zero past nvals, ringT.INTT, MulScalar(scale)
+ *   rh_bgv_decode_ring_t     DecodeRingT (:323-353): MulScalar(scale^-1), ringT.NTT, values[i] = pT[indexMatrix[i]], the signed form minus T
+ *                            from T >> 1 on.  pT_dev is not modified.  A scale that is zero or not invertible modulo T is refused.
+ *   rh_bgv_ring_t2q          RingT2Q (:357-386): every limb takes pT UNREDUCED at stride N / n and zero elsewhere; scale_up multiplies by
+ *                            T^-1 mod Q_level.  ring: ringQ, or another standard ring of degree N (the key-switch ring P, for Embed into a
+ *                            ringqp.Poly) WITHOUT scale_up: the reference multiplies the limbs of P under the moduli of Q there (:282, :384).
+ *   rh_bgv_ring_q2t          RingQ2T (:391-439) with scaleDown = true, all four branches (level 0 / level > 0, gap 1 / gap > 1)
+ *   rh_bgv_encode            Encode (:130-184) / EmbedScale (:252-316): batched: EncodeRingT, RingT2Q, Ring.NTT if is_ntt, MForm if
+ *                            is_montgomery; batched = 0: the values at coefficients 0 .. nvals-1, MulScalar(scale), RingT2Q, NTT.  Without
+ *                            scale_up, is_ntt and is_montgomery the words are the raw residues modulo T the reference leaves.
+ *   rh_bgv_decode            Decode (:442-487): Ring.INTT if is_ntt, RingQ2T, then DecodeRingT (batched) or MulScalar(scale^-1) and the
+ *                            values in coefficient order.  in_dev is not modified. */
+typedef struct rh_bgv_encoder rh_bgv_encoder;
+int rh_bgv_encoder_create(rh_bgv_encoder** out, rh_ring* ringQ, rh_ring* ringT);
+void rh_bgv_encoder_destroy(rh_bgv_encoder* e);
+int rh_bgv_encoder_reserve(rh_bgv_encoder* e, int nvec);
+int rh_bgv_encoder_set_tuning(rh_bgv_encoder* e, const char* key, long value);
+int rh_bgv_encode(rh_bgv_encoder* e, rh_ring* ring, int level, uint64_t scale, const uint64_t* values_dev, int nvals, int is_signed, int nvec,
+                  uint64_t* out_dev, int batched, int scale_up, int is_ntt, int is_montgomery);
+int rh_bgv_decode(rh_bgv_encoder* e, int level, uint64_t scale, const uint64_t* in_dev, int nvec, uint64_t* values_dev, int nvals, int is_signed,
+                  int batched, int is_ntt);
+int rh_bgv_encode_ring_t(rh_bgv_encoder* e, uint64_t scale, const uint64_t* values_dev, int nvals, int is_signed, int nvec, uint64_t* pT_dev);
+int rh_bgv_decode_ring_t(rh_bgv_encoder* e, uint64_t scale, const uint64_t* pT_dev, int nvec, uint64_t* values_dev, int nvals, int is_signed);
+int rh_bgv_ring_t2q(rh_bgv_encoder* e, rh_ring* ring, int level, int scale_up, const uint64_t* pT_dev, uint64_t* out_dev, int nvec);
+int rh_bgv_ring_q2t(rh_bgv_encoder* e, int level, const uint64_t* in_dev, uint64_t* pT_dev, int nvec);
+
 /* ---- limb-sharded hybrid key switch (BASELINE config 5): one process per GPU owns a subset of the limbs
  * of Q and P and the matching slice of the evaluation key.  Same arithmetic as rh_bext_gadget_product, cut where
  * reconstructRNS (ring/basis_extension.go:550-594) needs limbs of other owners; the exchange (an all-gather of the

@@ -1,7 +1,9 @@
 """Host-side mirror of bgv.Evaluator, schemes/bgv/evaluator.go, on device-resident batches in the NTT domain: the scale-invariant (BFV)
-multiply and the BGV half -- standard tensoring, multiply-accumulate, Add / Sub with scale matching, scalar operands, Rescale.  Call sequences
-and the scale bookkeeping (Python ints modulo T) only: the arithmetic is the HIP library's (csrc/bfv.hip, csrc/bgv.hip); key generation and the
-BGV encoder stay with the reference, so slice operands ([]uint64 / []int64) are refused by name.
+multiply and the BGV half -- standard tensoring, multiply-accumulate, Add / Sub with scale matching, scalar operands, Rescale -- and of
+bgv.Encoder, schemes/bgv/encoder.go, on device batches of vectors.  Call sequences and the scale bookkeeping (Python ints modulo T) only: the
+arithmetic is the HIP library's (csrc/bfv.hip, csrc/bgv.hip, csrc/bgv_encoder.hip); key generation stays with the reference.  An evaluator
+built with encoder= takes slice operands ([]uint64 / []int64) the way the reference does: encoded into its buffer at the scale the method
+sets, then the plaintext branch.  Without one they are refused by name.
 
   newEvaluatorPrecomp      :46-78        MulScaleInvariant(New)       :771-857     MulRelinScaleInvariant(New)  :877-972
   tensorScaleInvariant     :975-1040     MulScaleInvariant (scale)    :1045-1051   quantize                     :1104-1124
@@ -9,6 +11,8 @@ BGV encoder stay with the reference, so slice operands ([]uint64 / []int64) are 
   Mul(New) / MulRelin(New) :458-663      tensorStandard               :665-751     MulThenAdd / MulRelinThenAdd :1142-1287
   mulRelinThenAdd          :1289-1403    Rescale                      :1415-1445   MatchScalesAndLevel          :1593-1614
   matchScalesBinary        :1620-1659
+  encoder.go: NewEncoder :49-96, permuteMatrix :98-121, Encode :130-184, EncodeRingT :187-246, EmbedScale / Embed :252-320,
+  DecodeRingT :323-353, RingT2Q :357-386, RingQ2T :391-439, Decode :442-487
 
 A batch of B ciphertexts is one Ciphertext whose polys have npoly = B; all operands of a call sit at the same level (dense
 (npoly, level+1, N) blocks), which may be lower than the ring's top: a mismatch raises.  A degree-0 Ciphertext plays the role of a plaintext.
@@ -16,10 +20,11 @@ Scales are Python ints modulo T in the attribute Scale (1 when a ciphertext carr
 phase c0 + c1 s = (m s) T^-1 + e modulo Q: T times the phase is m s + T e."""
 import ctypes as C
 import math
+import threading
 
 import numpy as np
 
-from .ringhip import RingHipError, _check, _p, _u64, lib
+from .ringhip import ConjugateInvariant, DevicePoly, Ring, RingHipError, Standard, _check, _p, _u64, lib
 from .schemes import Ciphertext
 from . import rlwe
 
@@ -69,6 +74,10 @@ def _is_slice(op):
     return isinstance(op, (list, tuple, np.ndarray))
 
 
+def _is_values(op):
+    return _is_slice(op) or isinstance(op, DeviceValues)
+
+
 def _is_int(op):
     return isinstance(op, (int, np.integer)) and not isinstance(op, bool)
 
@@ -78,12 +87,16 @@ class Evaluator(rlwe.Evaluator):
     scale-invariant methods only: None builds a pure BGV evaluator, whose scale-invariant methods raise.  ringP / rlk: the key-switch ring and the
     relinearisation key (rlwe.GadgetCiphertext) for the Relin forms.  scaleInvariant: NewEvaluator's flag (:125-134): Mul / MulRelin dispatch
     to the scale-invariant forms (:460-465, :604-606) and Rescale does nothing (:1417).  fused: the BGV hot paths as one kernel each
-    (rh_bgv_tensor, rh_bgv_mul_plain, rh_bgv_axpby); False issues the reference's own sequence of Ring calls -- the same bits."""
+    (rh_bgv_tensor, rh_bgv_mul_plain, rh_bgv_axpby); False issues the reference's own sequence of Ring calls -- the same bits.  encoder: a
+    bgv.Encoder over the same ringQ and t; with it Add, Sub, Mul, MulRelin, MulThenAdd and MulRelinThenAdd take []uint64 / []int64 operands."""
 
-    def __init__(self, ringQ, ringQMul=None, t=None, ringP=None, rlk=None, scaleInvariant=False, fused=True):
+    def __init__(self, ringQ, ringQMul=None, t=None, ringP=None, rlk=None, scaleInvariant=False, fused=True, encoder=None):
         if t is None:
             raise RingHipError("bgv.Evaluator: the plaintext modulus t is missing")
+        if encoder is not None and (encoder.t != int(t) or encoder.ringQ._h.value != ringQ._h.value):
+            raise RingHipError("bgv.Evaluator: the encoder was built for another ringQ or plaintext modulus")
         super().__init__(ringQ, ringP, galois_keys={"rlk": rlk} if rlk is not None else None)
+        self.encoder = encoder             # bgv.Encoder: with one, slice operands take the reference's slice branches; without, they are refused
         self.ringQMul, self.t = ringQMul, int(t)
         self.ScaleInvariant, self.fused = bool(scaleInvariant), bool(fused)
         self._bfv, self.levelQMul = None, None
@@ -195,13 +208,18 @@ class Evaluator(rlwe.Evaluator):
         opOut.IsNTT = True
 
     def MulScaleInvariant(self, op0, op1, opOut):
-        """:771-830, ciphertext branch: opOut (degree 2) = op0 x op1 * T / Q"""
+        """:771-830, ciphertext branch: opOut (degree 2) = op0 x op1 * T / Q.  A slice (with encoder=) is encoded at scale 1 and goes to
+        tensorStandard (:794-821)"""
+        if self.encoder is not None and _is_values(op1):
+            return self.tensorStandard(op0, self._slice_pt(op0, op1, 1), False, opOut, "MulInvariant")
         self._need_qmul("MulScaleInvariant")
         self._operands(op0, op1, opOut, False, "MulInvariant")
         self.tensorScaleInvariant(op0, op1, False, opOut)
 
     def MulRelinScaleInvariant(self, op0, op1, opOut):
-        """:877-941, ciphertext branch: the same, relinearised to degree 1"""
+        """:877-941, ciphertext branch: the same, relinearised to degree 1.  A slice (with encoder=): as above (:901-930)"""
+        if self.encoder is not None and _is_values(op1):
+            return self.tensorStandard(op0, self._slice_pt(op0, op1, 1), True, opOut, "MulRelinInvariant")
         self._need_qmul("MulRelinScaleInvariant")
         self._operands(op0, op1, opOut, True, "MulRelinInvariant")
         self.tensorScaleInvariant(op0, op1, True, opOut)
@@ -213,13 +231,13 @@ class Evaluator(rlwe.Evaluator):
 
     def MulScaleInvariantNew(self, op0, op1):
         """:849-857"""
-        opOut = self._new(2, op0)
+        opOut = self._new(op0.Degree() if self.encoder is not None and _is_values(op1) else 2, op0)
         self.MulScaleInvariant(op0, op1, opOut)
         return opOut
 
     def MulRelinScaleInvariantNew(self, op0, op1):
         """:960-972"""
-        opOut = self._new(1, op0)
+        opOut = self._new(op0.Degree() if self.encoder is not None and _is_values(op1) else 1, op0)
         self.MulRelinScaleInvariant(op0, op1, opOut)
         return opOut
 
@@ -234,6 +252,15 @@ class Evaluator(rlwe.Evaluator):
                                % (who, type(op1).__name__))
         if not (_is_int(op1) or isinstance(op1, Ciphertext)):
             raise RingHipError("cannot %s: invalid op1 of type %s, expected a Ciphertext or an int" % (who, type(op1).__name__))
+
+    def _slice_pt(self, op0, op1, scale):
+        """the plaintext of a slice operand: op0's metadata with the scale the method sets, encoded into the evaluator's buffer
+        (:245-259, :519-534, :804-818, :1213-1235)"""
+        level, npoly = op0.Level(), op0.Value[0].npoly
+        pt = Plaintext(self.buffer("bgv_pt", self.ringQ.AtLevel(level), npoly, level + 1), scale, is_ntt=op0.IsNTT,
+                       is_montgomery=getattr(op0, "IsMontgomery", False), is_batched=getattr(op0, "IsBatched", True))
+        self.encoder.Encode(op1, pt)
+        return pt
 
     def _same_level(self, who, *cts):
         for ct in cts:
@@ -287,6 +314,8 @@ class Evaluator(rlwe.Evaluator):
     # ---- Add / Sub :173-432 ------------------------------------------------------------------------------------------------------------
     def _add_sub(self, op0, op1, opOut, sub):
         who = "Sub" if sub else "Add"
+        if self.encoder is not None and _is_values(op1):
+            op1 = self._slice_pt(op0, op1, self._scale(op0))                         # the plaintext takes op0's metadata, scale included (:254)
         self._refuse_slice(op1, who)
         if _is_int(op1):                                                           # *big.Int (:197-227, :368-369: Sub adds the negation)
             level = self._same_level(who, op0, opOut)
@@ -427,6 +456,8 @@ class Evaluator(rlwe.Evaluator):
     def Mul(self, op0, op1, opOut):
         """:458-544: opOut (degree op0.Degree() + op1.Degree()) = op0 x op1 * T, scale op0.Scale * op1.Scale; op1 an int: every component
         times the scalar centred modulo T.  A scale-invariant evaluator sends ciphertexts and slices to MulScaleInvariant (:460-465)."""
+        if self.encoder is not None and _is_values(op1):                           # (:511-538; the scale-invariant form comes here too, :794-821)
+            return self.tensorStandard(op0, self._slice_pt(op0, op1, 1), False, opOut, "Mul")
         if self.ScaleInvariant and (isinstance(op1, Ciphertext) or _is_slice(op1)):
             return self.MulScaleInvariant(op0, op1, opOut)
         self._refuse_slice(op1, "Mul")
@@ -436,6 +467,8 @@ class Evaluator(rlwe.Evaluator):
 
     def MulRelin(self, op0, op1, opOut):
         """:602-629: the same, relinearised to degree 1"""
+        if self.encoder is not None and _is_values(op1):                           # (:901-930)
+            return self.tensorStandard(op0, self._slice_pt(op0, op1, 1), True, opOut, "MulRelin")
         if self.ScaleInvariant:
             return self.MulRelinScaleInvariant(op0, op1, opOut)
         self._refuse_slice(op1, "MulRelin")
@@ -445,6 +478,10 @@ class Evaluator(rlwe.Evaluator):
 
     def MulNew(self, op0, op1):
         """:564-581"""
+        if self.encoder is not None and _is_values(op1):
+            opOut = self._new(op0.Degree(), op0)
+            self.Mul(op0, op1, opOut)
+            return opOut
         if self.ScaleInvariant and (isinstance(op1, Ciphertext) or _is_slice(op1)):
             return self.MulScaleInvariantNew(op0, op1)
         self._refuse_slice(op1, "Mul")
@@ -454,6 +491,10 @@ class Evaluator(rlwe.Evaluator):
 
     def MulRelinNew(self, op0, op1):
         """:649-663"""
+        if self.encoder is not None and _is_values(op1):
+            opOut = self._new(op0.Degree(), op0)
+            self.MulRelin(op0, op1, opOut)
+            return opOut
         if self.ScaleInvariant:
             return self.MulRelinScaleInvariantNew(op0, op1)
         self._refuse_slice(op1, "MulRelin")
@@ -530,6 +571,9 @@ class Evaluator(rlwe.Evaluator):
     def MulThenAdd(self, op0, op1, opOut):
         """:1142-1246: opOut += op0 x op1 * T without relinearisation (opOut of degree 2 for two degree-1 operands); an opOut whose scale is
         not op0.Scale * op1.Scale has both sides matched first.  op1 an int: opOut += op0 * (op1 * opOut.Scale / op0.Scale)."""
+        if self.encoder is not None and _is_values(op1):                           # (:1202-1239): encoded at opOut.Scale / op0.Scale, or 1
+            s0, so = self._scale(op0), self._scale(opOut)
+            op1 = self._slice_pt(op0, op1, pow(s0, self.t - 2, self.t) * so % self.t if s0 != so else 1)
         self._refuse_slice(op1, "MulThenAdd")
         if _is_int(op1):                                                           # (:1162-1194)
             level = self._same_level("MulThenAdd", op0, opOut)
@@ -598,3 +642,290 @@ class Evaluator(rlwe.Evaluator):
                 else:
                     ringQ.MulScalar(el, r, el)                                     # (:1601-1603, :1608-1610)
             ct.Scale = self._scale(ct) * r % self.t                                # (:1606, :1613)
+
+
+# ---- bgv.Encoder, schemes/bgv/encoder.go, on standard rings -------------------------------------------------------------------------------
+def PlaintextRingDegree(N, t):
+    """bgv/params.go:110-121: min(N, order / 2) with order the largest power of two such that t = 1 modulo it"""
+    t = int(t)
+    order = 1 << t.bit_length()
+    while order and t & (order - 1) != 1:
+        order >>= 1
+    if order < 16:
+        raise RingHipError("provided plaintext modulus t has cyclotomic order < 16 (ring degree of minimum 8 is required by the backend)")
+    return min(int(N), order >> 1)
+
+
+def permuteMatrix(logN):
+    """encoder.go:98-121: slot i of the first row sits at bitrev((5^i mod 2N) >> 1), slot i of the second row mirrors it"""
+    N = 1 << logN
+    perm = np.zeros(N, dtype=np.uint64)
+    pow5, mask = 1, 2 * N - 1
+    for i in range(N >> 1):
+        pos = int(format(pow5 >> 1, "0%db" % logN)[::-1], 2)
+        perm[i], perm[i + (N >> 1)] = pos, N - pos - 1
+        pow5 = pow5 * 5 & mask
+    return perm
+
+
+class DeviceValues:
+    """(nvec, n) uint64 -- or int64 with signed=True -- on the device: the []uint64 / []int64 of a batch of vectors"""
+
+    def __init__(self, ring, nvec, n, signed=False):
+        self.ring, self.nvec, self.n, self.signed = ring, int(nvec), int(n), bool(signed)
+        self.words = self.nvec * self.n
+        p = C.c_void_p()
+        _check(lib().rh_dev_alloc(ring._h, max(self.words, 1), C.byref(p)))
+        self.ptr = int(p.value)
+
+    @classmethod
+    def from_numpy(cls, ring, arr):
+        arr = np.asarray(arr)
+        if arr.dtype not in (np.uint64, np.int64):
+            raise RingHipError("bgv.DeviceValues: values must be uint64 or int64, but are %s" % arr.dtype)
+        arr = np.ascontiguousarray(arr[None] if arr.ndim == 1 else arr)
+        assert arr.ndim == 2, arr.shape
+        v = cls(ring, arr.shape[0], arr.shape[1], arr.dtype == np.int64)
+        v.upload(arr)
+        return v
+
+    def upload(self, arr):
+        if self.words:
+            _check(lib().rh_dev_upload(self.ring._h, self.ptr, _p(np.ascontiguousarray(arr).view(np.uint64).reshape(-1)), self.words))
+
+    def numpy(self):
+        out = np.empty(self.words, dtype=np.uint64)
+        if self.words:
+            _check(lib().rh_dev_download(self.ring._h, _p(out), self.ptr, self.words))
+        return out.view(np.int64 if self.signed else np.uint64).reshape(self.nvec, self.n)
+
+    def free(self):
+        if self.ptr:
+            lib().rh_dev_free(None, self.ptr)
+            self.ptr = 0
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class Plaintext(Ciphertext):
+    """rlwe.Plaintext: one poly block (npoly vectors) with the MetaData the BGV encoder reads -- Scale (an int modulo T), IsNTT, IsBatched,
+    IsMontgomery.  A degree-0 Ciphertext to the evaluator."""
+
+    def __init__(self, poly, scale=1, is_ntt=True, is_montgomery=False, is_batched=True):
+        Ciphertext.__init__(self, [poly], is_ntt=is_ntt)
+        self.Scale = int(scale)
+        self.IsMontgomery, self.IsBatched = bool(is_montgomery), bool(is_batched)
+
+
+class Encoder:
+    """bgv.Encoder on device batches: Encode / Decode / EncodeRingT / DecodeRingT / Embed / EmbedScale / RingT2Q / RingQ2T of nvec vectors at
+    once (csrc/bgv_encoder.hip).  ringT is built here by the rule of bgv/params.go:110-121.  Refused by name: conjugate-invariant and 3N
+    rings, more values than slots, value types other than uint64 / int64, a scale that is zero or not invertible modulo T in Decode, and
+    EmbedScale(scaleUp=True) into a (Q, P) pair: the reference multiplies the limbs of P by T^-1 mod Q_levelP under the moduli of Q there
+    (:282, :384), which is a finding about the reference, not a behaviour to reproduce."""
+
+    def __init__(self, ringQ, t, ringP=None):
+        self.ringQ, self.ringP, self.t = ringQ, ringP, int(t)
+        self._h, self.ringT = None, None
+        for r in (ringQ, ringP):
+            if r is not None and r.kind == ConjugateInvariant:
+                raise RingHipError("cannot NewEncoder: conjugate-invariant rings are not supported (their one-row encoder stays with the reference)")
+            if r is not None and r.kind != Standard:
+                raise RingHipError("cannot NewEncoder: 3N rings are not supported (the BGV encoder is defined on power-of-two cyclotomics)")
+        if self.t <= 0:
+            raise RingHipError("invalid parameters: t = 0")
+        n = PlaintextRingDegree(ringQ.N, self.t)
+        try:
+            self.ringT = Ring(n, [self.t], device=ringQ.device)
+        except RingHipError as e:
+            raise RingHipError("provided plaintext modulus t is invalid: %s" % e) from None
+        h = C.c_void_p()
+        _check(lib().rh_bgv_encoder_create(C.byref(h), ringQ._h, self.ringT._h))
+        self._h = h
+        self.indexMatrix = permuteMatrix(n.bit_length() - 1)
+        self._tls = threading.local()      # per host thread: the blocks host values go through, kept so that no call frees device memory
+
+    def close(self):
+        if self._h:
+            lib().rh_bgv_encoder_destroy(self._h)
+            self._h = None
+        if self.ringT is not None:
+            self.ringT.close()
+            self.ringT = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def RingT(self):
+        return self.ringT
+
+    def MaxSlots(self):
+        """params.go:189-192: Rows * Cols = 2 * (n / 2)"""
+        return self.ringT.N
+
+    def LogMaxDimensions(self):
+        """params.go:176-185 on a standard ring: (Rows, Cols) = (1, log2(n) - 1) -- two rows of n / 2 slots"""
+        return (1, self.ringT.N.bit_length() - 2)
+
+    def reserve(self, nvec):
+        _check(lib().rh_bgv_encoder_reserve(self._h, int(nvec)))
+
+    def set_tuning(self, key, value):
+        _check(lib().rh_bgv_encoder_set_tuning(self._h, key.encode(), int(value)))
+
+    def NewPlaintext(self, level, scale=1, nvec=1, is_ntt=True, is_batched=True):
+        return Plaintext(self.ringQ.AtLevel(level).NewPoly(nvec), scale, is_ntt, False, is_batched)
+
+    # ---- values on their way to and from the device --------------------------------------------------------------------------------------
+    def _pooled(self, nvec, n, signed):
+        pool = self._tls.__dict__.setdefault("blocks", {})
+        dv = pool.get((nvec, n, signed))
+        if dv is None:
+            dv = pool[(nvec, n, signed)] = DeviceValues(self.ringQ, nvec, n, signed)
+        return dv
+
+    def _block(self, values, nvec, text):
+        """(nvec, nvals) block on the device from a slice (one vector, shared by the batch), a (nvec, nvals) array or a DeviceValues; text: the
+        reference's refusal of too many values, with %d for their number"""
+        slots = self.ringT.N
+        if isinstance(values, DeviceValues):
+            if values.nvec != nvec:
+                raise RingHipError("a device block of %d vectors given for a block of %d polys" % (values.nvec, nvec))
+            if values.n > slots:
+                raise RingHipError(text % values.n)
+            return values
+        a = np.asarray(values)
+        if a.dtype not in (np.uint64, np.int64) and not (isinstance(values, (list, tuple)) and a.size == 0):
+            raise RingHipError("cannot EncodeRingT: values.(type) must be either []uint64 or []int64 but is %s"
+                               % (a.dtype if isinstance(values, np.ndarray) else "%s of %s" % (type(values).__name__, a.dtype)))
+        if a.size == 0:
+            a = np.zeros((0,), dtype=np.uint64)
+        if a.ndim == 1:
+            a = np.broadcast_to(a, (nvec, a.shape[0]))
+        if a.ndim != 2 or a.shape[0] != nvec:
+            raise RingHipError("%d vectors given for a block of %d polys" % (a.shape[0] if a.ndim == 2 else -1, nvec))
+        if a.shape[1] > slots:
+            raise RingHipError(text % a.shape[1])
+        dv = self._pooled(nvec, a.shape[1], a.dtype == np.int64)
+        dv.upload(a)
+        return dv
+
+    def _out(self, values, nvec, who):
+        """where decoded values go: (device block, host array or None, signed)"""
+        if isinstance(values, DeviceValues):
+            if values.nvec != nvec or values.n > self.ringT.N:
+                raise RingHipError("cannot %s: a device block of values must be (%d, k) with k <= %d" % (who, nvec, self.ringT.N))
+            return values, None, values.signed
+        if not isinstance(values, np.ndarray) or values.dtype not in (np.uint64, np.int64):
+            raise RingHipError("cannot %s: values must be either []uint64 or []int64 but is %s"
+                               % (who, values.dtype if isinstance(values, np.ndarray) else type(values).__name__))
+        if not (values.ndim == 2 and values.shape[0] == nvec) and not (values.ndim == 1 and nvec == 1):
+            raise RingHipError("cannot %s: values of shape %s for a block of %d vectors: give (%d, k)" % (who, values.shape, nvec, nvec))
+        if values.shape[-1] > self.ringT.N:
+            raise RingHipError("cannot %s: len(values)=%d > slots=%d" % (who, values.shape[-1], self.ringT.N))
+        signed = values.dtype == np.int64
+        return self._pooled(nvec, values.shape[-1], signed), values, signed
+
+    @staticmethod
+    def _back(dv, host):
+        if host is None:
+            return dv
+        np.copyto(host, dv.numpy().reshape(host.shape))        # through the caller's own array, whatever its strides
+        return host
+
+    def _ring_of(self, poly, who):
+        for r in (self.ringQ, self.ringP):
+            if r is not None and poly.ring._h.value == r._h.value:
+                return r
+        raise RingHipError("cannot %s: the poly belongs to neither ringQ nor ringP of this encoder" % who)
+
+    # ---- Encode / Embed (:130-320) --------------------------------------------------------------------------------------------------------
+    def _encode(self, values, scale, batched, scaleUp, is_ntt, mont, poly, text, who):
+        ring = self._ring_of(poly, who)
+        dv = self._block(values, poly.npoly, text)
+        _check(lib().rh_bgv_encode(self._h, ring._h, poly.limbs - 1, int(scale) % (1 << 64), dv.ptr, dv.n, 1 if dv.signed else 0, poly.npoly,
+                                   poly.ptr, 1 if batched else 0, 1 if scaleUp else 0, 1 if is_ntt else 0, 1 if mont else 0))
+
+    def Encode(self, values, pt):
+        """:130-184: batched through EmbedScale(scaleUp=True); IsBatched = false puts the values on coefficients 0 .. len-1 of the plaintext ring"""
+        if pt.IsBatched:
+            return self.EmbedScale(values, True, pt, pt.Value[0])
+        self._encode(values, pt.Scale, False, True, pt.IsNTT, False, pt.Value[0],
+                     "cannot Encode (TimeDomain): len(values)=%%d > N=%d" % self.ringT.N, "Encode")
+
+    def EmbedScale(self, values, scaleUp, metadata, polyOut):
+        """:252-316: metadata is anything with Scale, IsNTT and IsMontgomery (a Plaintext, a Ciphertext given them); polyOut a DevicePoly of
+        ringQ (or of ringP), or a (Q, P) pair -- a tuple or an rlwe.PolyQP -- whose P may be None"""
+        pair = isinstance(polyOut, (tuple, list, rlwe.PolyQP))
+        Q, P = ((polyOut.Q, polyOut.P) if isinstance(polyOut, rlwe.PolyQP) else tuple(polyOut)) if pair else (polyOut, None)
+        if not isinstance(Q, DevicePoly) or not (P is None or isinstance(P, DevicePoly)):
+            raise RingHipError("cannot embed: invalid polyOut.(Type) must be ringqp.Poly or *ring.Poly")
+        if pair and scaleUp:
+            raise RingHipError("cannot EmbedScale: scaleUp into a ringqp.Poly is refused: the reference multiplies the limbs of P by T^-1 mod Q_levelP "
+                               "under the moduli of Q (bgv/encoder.go:282, :384)")
+        text = "cannot EncodeRingT (FrequencyDomain): len(values)=%%d > slots=%d" % self.ringT.N
+        scale, ntt, mont = getattr(metadata, "Scale", 1), metadata.IsNTT, getattr(metadata, "IsMontgomery", False)
+        self._encode(values, scale, True, scaleUp, ntt, mont, Q, text, "Embed")
+        if P is not None:
+            if self.ringP is None:
+                raise RingHipError("cannot embed into a ringqp.Poly: the encoder was built without ringP")
+            self._encode(values, scale, True, False, ntt, mont, P, text, "Embed")
+
+    def Embed(self, values, metadata, polyOut):
+        """:318-320"""
+        return self.EmbedScale(values, False, metadata, polyOut)
+
+    def EncodeRingT(self, values, scale, pT):
+        """:187-246; pT: a DevicePoly of RingT(), one limb"""
+        dv = self._block(values, pT.npoly, "cannot EncodeRingT (FrequencyDomain): len(values)=%%d > slots=%d" % self.ringT.N)
+        self._t_block(pT, "EncodeRingT")
+        _check(lib().rh_bgv_encode_ring_t(self._h, int(scale) % (1 << 64), dv.ptr, dv.n, 1 if dv.signed else 0, pT.npoly, pT.ptr))
+
+    # ---- Decode (:323-353, :442-487) --------------------------------------------------------------------------------------------------------
+    def _t_block(self, pT, who):
+        if pT.ring._h.value != self.ringT._h.value or pT.limbs != 1:
+            raise RingHipError("cannot %s: pT must be a one-limb poly block of RingT()" % who)
+
+    def _new_values(self, nvec, signed):
+        return np.zeros((nvec, self.ringT.N), dtype=np.int64 if signed else np.uint64)
+
+    def DecodeRingT(self, pT, scale, values=None, signed=False):
+        """:323-353: values None (a new (nvec, slots) array, int64 with signed), a numpy array of dtype uint64 or int64 -- (nvec, k), or (k,) for
+        a single vector -- or a DeviceValues; filled and returned"""
+        self._t_block(pT, "DecodeRingT")
+        dv, host, signed = self._out(self._new_values(pT.npoly, signed) if values is None else values, pT.npoly, "DecodeRingT")
+        _check(lib().rh_bgv_decode_ring_t(self._h, int(scale) % (1 << 64), pT.ptr, pT.npoly, dv.ptr, dv.n, 1 if signed else 0))
+        return self._back(dv, host)
+
+    def Decode(self, pt, values=None, signed=False):
+        """:442-487, values as for DecodeRingT; IsBatched = false: the coefficients of the plaintext ring in their order"""
+        p = pt.Value[0]
+        if self._ring_of(p, "Decode") is not self.ringQ:
+            raise RingHipError("cannot Decode: the plaintext must live in ringQ")
+        dv, host, signed = self._out(self._new_values(p.npoly, signed) if values is None else values, p.npoly, "Decode")
+        _check(lib().rh_bgv_decode(self._h, p.limbs - 1, int(getattr(pt, "Scale", 1)) % (1 << 64), p.ptr, p.npoly, dv.ptr, dv.n, 1 if signed else 0,
+                                   1 if getattr(pt, "IsBatched", True) else 0, 1 if pt.IsNTT else 0))
+        return self._back(dv, host)
+
+    # ---- the two conversions alone (:357-439) ------------------------------------------------------------------------------------------------
+    def RingT2Q(self, level, scaleUp, pT, pQ):
+        self._t_block(pT, "RingT2Q")
+        ring = self._ring_of(pQ, "RingT2Q")
+        if pQ.limbs != level + 1 or pQ.npoly != pT.npoly:
+            raise RingHipError("cannot RingT2Q: pQ must be a block of %d polys with level + 1 = %d limbs" % (pT.npoly, level + 1))
+        _check(lib().rh_bgv_ring_t2q(self._h, ring._h, int(level), 1 if scaleUp else 0, pT.ptr, pQ.ptr, pT.npoly))
+
+    def RingQ2T(self, level, scaleDown, pQ, pT):
+        self._t_block(pT, "RingQ2T")
+        if not scaleDown:
+            raise RingHipError("cannot RingQ2T: scaleDown = false is not built on the device (the encoder calls it with true only)")
+        if self._ring_of(pQ, "RingQ2T") is not self.ringQ or pQ.limbs != level + 1 or pQ.npoly != pT.npoly:
+            raise RingHipError("cannot RingQ2T: pQ must be a block of %d polys of ringQ with level + 1 = %d limbs" % (pT.npoly, level + 1))
+        _check(lib().rh_bgv_ring_q2t(self._h, int(level), pQ.ptr, pT.ptr, pT.npoly))

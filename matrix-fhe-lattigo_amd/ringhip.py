@@ -143,6 +143,11 @@ def lib():
         "rh_ckks_special_ifft": (i, [vp, vp, i, i]), "rh_ckks_special_fft": (i, [vp, vp, i, i]),
         "rh_ckks_encode": (i, [vp, i, i, C.c_double, vp, i, vp, i, i]), "rh_ckks_encode_coeffs": (i, [vp, i, C.c_double, vp, i, i, vp, i]),
         "rh_ckks_decode": (i, [vp, i, i, C.c_double, C.c_double, i, i, i, vp, i, vp]),
+        "rh_bgv_encoder_create": (i, [C.POINTER(vp), vp, vp]), "rh_bgv_encoder_destroy": (None, [vp]),
+        "rh_bgv_encoder_reserve": (i, [vp, i]), "rh_bgv_encoder_set_tuning": (i, [vp, C.c_char_p, C.c_long]),
+        "rh_bgv_encode": (i, [vp, vp, i, C.c_uint64, vp, i, i, i, vp, i, i, i, i]), "rh_bgv_decode": (i, [vp, i, C.c_uint64, vp, i, vp, i, i, i, i]),
+        "rh_bgv_encode_ring_t": (i, [vp, C.c_uint64, vp, i, i, i, vp]), "rh_bgv_decode_ring_t": (i, [vp, C.c_uint64, vp, i, vp, i, i]),
+        "rh_bgv_ring_t2q": (i, [vp, vp, i, i, vp, vp, i]), "rh_bgv_ring_q2t": (i, [vp, i, vp, vp, i]),
         "rh_kshard_create": (i, [C.POINTER(vp), vp, vp, U64P, i, U64P, i, C.POINTER(i), i, C.POINTER(i), i]),
         "rh_kshard_destroy": (None, [vp]), "rh_kshard_num_digits": (i, [vp]),
         "rh_kshard_digit_range": (i, [vp, i, C.POINTER(i), C.POINTER(i)]),

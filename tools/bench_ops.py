@@ -6,7 +6,9 @@ profiles/bfv_ops.json (or OUT.json); `bench_ops.py bgv [OUT.json]` the BGV group
 against the reference's sequence of ring calls) and writes profiles/bgv_ops.json; `bench_ops.py ckks [OUT.json]` the CKKS group
 (MulThenAdd, MulRelinThenAdd, scale-matched Add and scalar Mul at the config 5 ring, fused against composed) and writes profiles/ckks_ops.json;
 `bench_ops.py ckks_encoder [OUT.json]` the CKKS encoder (Encode, Decode and the two transforms at N = 2^16, 24 limbs, full slots, 64 vectors)
-against its algorithmic bytes, and writes profiles/ckks_encoder.json."""
+against its algorithmic bytes, and writes profiles/ckks_encoder.json; `bench_ops.py bgv_encoder [OUT.json]` the BGV encoder (Encode, Decode,
+the lift and Q to T alone, one kernel each against the reference's sequence of ring calls, at N = 2^16, 24 limbs, 64 vectors, T = 65537 for
+gap 2 and T = 786433 for gap 1) and writes profiles/bgv_encoder.json."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -314,6 +316,87 @@ def ckks_encoder_group(out_path):
     print(json.dumps(res, indent=1))
     enc.close()
     rq.close()
+
+
+def bgv_encoder_group(out_path):
+    """The BGV encoder (csrc/bgv_encoder.hip) at N = 2^16, 24 limbs of Qi60, nvec = 64, device-resident values and plaintexts, top level:
+    T = 65537 (n = 2^15, gap 2: Q to T is the exact-CRT branch, which has one form) and T = 786433 (n = 2^16, gap 1: the ModUpExact branch).
+    Every line is timed with "fused" = 1 and = 0 (the reference's sequence of ring and basis-extension calls) in the same process, in
+    alternating windows, and stands against its algorithmic bytes per vector: lift 8 n in + 8 L N out; Q to T 8 L n in + 8 n out; a Ring
+    transform 16 N per limb; the transform modulo T 16 n; slots 8 n in + 8 n out.  Medians of `rounds` windows of `reps` calls, device
+    events, 2 warm-up calls per window; the spread is the windows' max - min."""
+    import hashlib
+    import statistics
+    N, L, B, rounds, reps = 1 << 16, 24, 64, 7, 5
+    Q = QI60[:L]
+    rq = rh.Ring(N, Q); rq.set_stream(stream.cuda_stream)
+    rng = np.random.default_rng(0)
+    lines = []
+    for T in (65537, 786433):
+        enc = rh.bgv.Encoder(rq, T)
+        enc.reserve(B)
+        n = enc.MaxSlots()
+        host = rng.integers(0, T, (B, n), dtype=np.uint64)
+        vals = rh.bgv.DeviceValues.from_numpy(rq, host)
+        out = rh.bgv.DeviceValues(rq, B, n)
+        pt = enc.NewPlaintext(L - 1, 3, nvec=B)
+        pT = enc.RingT().NewPoly(B)
+        pt0 = rq.AtLevel(0).NewPoly(B)
+        pt_nb = rh.bgv.Plaintext(rq.AtLevel(0).NewPoly(B), 3, is_ntt=False, is_batched=False)      # the slot kernel has no entry of its own: its shortest caller
+        enc.Encode(vals, pt)
+        rq.AtLevel(0).CopyLvl(pt.Value[0], pt0)
+        enc.Decode(pt, out)
+        assert np.array_equal(out.numpy(), host), "Encode then Decode lost the values"
+        digest = {}
+        for fused in (1, 0):                              # both forms give the same bits at this size too
+            enc.set_tuning("fused", fused)
+            enc.Encode(vals, pt); enc.Decode(pt, out); enc.RingQ2T(L - 1, True, pt.Value[0], pT)
+            digest[fused] = [hashlib.sha256(a.numpy()).hexdigest() for a in (pt.Value[0], out, pT)]
+        assert digest[0] == digest[1], "fused and composed differ"
+        del digest
+        per_ntt, lift, q2t = 16.0 * N * L, 8.0 * n + 8.0 * L * N, 8.0 * L * n + 8.0 * n
+        cases = {
+            "Encode (slots, INTT mod T, lift, NTT)": (lambda: enc.Encode(vals, pt), 16.0 * n + 16.0 * n + lift + per_ntt),
+            "Decode (INTT, Q to T, NTT mod T, slots)": (lambda: enc.Decode(pt, out), per_ntt + q2t + 16.0 * n + 16.0 * n),
+            "EncodeRingT (slots, INTT mod T, MulScalar)": (lambda: enc.EncodeRingT(vals, 3, pT), 16.0 * n + 16.0 * n + 16.0 * n),
+            "lift alone (RingT2Q, scaleUp)": (lambda: enc.RingT2Q(L - 1, True, pT, pt.Value[0]), lift),
+            "Q to T alone (RingQ2T)": (lambda: enc.RingQ2T(L - 1, True, pt.Value[0], pT), q2t),
+            "Q to T alone at level 0": (lambda: enc.RingQ2T(0, True, pt0, pT), 16.0 * n),
+            "slots + one-limb lift (Encode, IsBatched = false, level 0, coefficient domain)": (lambda: enc.Encode(vals, pt_nb), 8.0 * n + 16.0 * n + 8.0 * N),
+        }
+        times = {(k, f): [] for k in cases for f in (1, 0)}
+        for _ in range(rounds):
+            for name, (fn, _) in cases.items():
+                for fused in (1, 0):
+                    enc.set_tuning("fused", fused)
+                    times[(name, fused)].append(timed(fn, reps=reps))
+        enc.set_tuning("fused", -1)
+        for name, (_, vec_bytes) in cases.items():
+            f, c = times[(name, 1)], times[(name, 0)]
+            ms, msc = statistics.median(f), statistics.median(c)
+            gbs = vec_bytes * B / (ms * 1e-3) / 1e9
+            lines.append({"T": T, "n": n, "gap": N // n, "op": name, "fused_ms_median": round(ms, 4), "fused_ms_min": round(min(f), 4),
+                          "fused_ms_max": round(max(f), 4), "composed_ms_median": round(msc, 4), "composed_ms_min": round(min(c), 4),
+                          "composed_ms_max": round(max(c), 4), "composed_spread_ms": round(max(c) - min(c), 4),
+                          "fused_wins_by_more_than_spread": bool(msc - ms > max(c) - min(c)),
+                          "vectors_per_s": round(B / (ms * 1e-3), 1), "algorithmic_bytes_per_vector": vec_bytes,
+                          "algorithmic_GBps": round(gbs, 1), "frac_of_8TBps": round(gbs / PEAK, 4)})
+        enc.close()
+    from bench import csrc_tree_hash
+    res = {"device": torch.cuda.get_device_name(0), "csrc_tree": csrc_tree_hash(), "shape": {"N": N, "limbs_Q": L, "nvec": B, "level": L - 1},
+           "method": "%d alternating windows of %d calls each per form, device events, 2 warm-up calls per window; clocks left to the driver's default governor"
+                     % (rounds, reps),
+           "results": lines}
+    with open(out_path, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(res, indent=1))
+    rq.close()
+
+
+if sys.argv[1:2] == ["bgv_encoder"]:
+    bgv_encoder_group(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "bgv_encoder.json"))
+    sys.exit(0)
 
 
 if sys.argv[1:2] == ["ckks_encoder"]:
