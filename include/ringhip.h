@@ -361,6 +361,37 @@ int rh_bext_gadget_product_hoisted_then_add(rh_bext* be, int levelQ, int levelP,
                                             const uint64_t* evkQ_dev, const uint64_t* evkP_dev, int beta_key, const uint64_t* add0_dev,
                                             const uint64_t* add1_dev, uint64_t* ct0_dev, uint64_t* ct1_dev, int npoly);
 
+/* ---- sums of rotations (core/rlwe/inner_sum.go).  Standard rings (RH_ERR_UNSUPPORTED for 3N and conjugate-invariant rings), NTT domain, dense
+ * blocks of npoly polys with levelQ+1 / levelP+1 limbs, canonical residues in and out; the Galois element is any odd number, taken modulo 2N,
+ * and the NTT-domain index map (ring/automorphism.go:12-35) is computed in the kernel.
+ *   rh_rlwe_rotate_accumulate_qp  the tail of AutomorphismHoistedLazy (core/rlwe/evaluator_automorphism.go:107-160: MulScalarBigint, Add and the four
+ *                                 AutomorphismNTTWithIndex passes over the Q and P parts) and the ringQP.Add that follows it in PartialTracesSum
+ *                                 (inner_sum.go:245-246), ONE launch over both components, the Q and the P rows and every poly:
+ *                                   acc_c[j] = [first ? 0 : acc_c[j]] + tmp_c[index(j)] + [c == 0, Q rows] (P mod q_i) * ct0[index(j)]
+ *                                 tmp: the output of rh_bext_gadget_product_hoisted_lazy; ct0: ctIn.Value[0]; first != 0: acc is written, not read
+ *                                 (the `copy` flag, inner_sum.go:236-240).  levelP >= 0.  No acc block may overlap a tmp block or ct0, and every block is
+ *                                 16-byte aligned (RH_ERR_ARG otherwise: the kernels move 16-byte pairs).
+ *   rh_rlwe_rotate_add_q          the two AutomorphismNTTWithIndex calls that end AutomorphismHoisted (evaluator_automorphism.go:90-95) and the
+ *                                 ringQ.Add pair that follows them (inner_sum.go:279-280; Trace :94-95), one launch: ct_c[j] = ct_c[j] + tmp_c[index(j)]
+ *                                 mod q_i, in place on ct; tmp may not overlap ct; 16-byte aligned blocks.
+ *   rh_rlwe_partial_traces_sum    the whole of Evaluator.PartialTracesSum (inner_sum.go:152-291): out = sum_{i < n} phi_{5^(i offset)}(in), by the
+ *                                 reference's binary reading of n -- log2(n) hoisted rotations, HW(n) - 1 lazy ones under one ModDown.  in / out:
+ *                                 both components in the domain is_ntt names (a coefficient-domain input is transformed on entry and the result
+ *                                 transformed back, :180-182, :285-288); out may be in (both components) and is otherwise another ciphertext.
+ *                                 keys: the caller's table of Galois keys, each laid out as rh_bext_gadget_product takes evkQ / evkP, `digits` rows;
+ *                                 every element the call needs is looked up BEFORE the first launch, a missing one is RH_ERR_ARG naming it.
+ *                                 levelP >= 1 (the hoisted product's own limit), n >= 1, offset != 0 (the reference's "partialtrace: invalid
+ *                                 parameter" otherwise).  fused != 0: the two kernels above; 0: the reference's own passes (rh_ring_automorphism_ntt,
+ *                                 rh_ring_vec_op) -- the same bits.  Scratch is the extender's (rh_bext_reserve); asynchronous. */
+typedef struct rh_galois_key { uint64_t galois_element; const uint64_t* evkQ_dev; const uint64_t* evkP_dev; int digits; } rh_galois_key;
+int rh_rlwe_rotate_accumulate_qp(rh_bext* be, int levelQ, int levelP, uint64_t gen, const uint64_t* ct0_dev, const uint64_t* tmpQ0_dev,
+                                 const uint64_t* tmpQ1_dev, const uint64_t* tmpP0_dev, const uint64_t* tmpP1_dev, uint64_t* accQ0_dev,
+                                 uint64_t* accQ1_dev, uint64_t* accP0_dev, uint64_t* accP1_dev, int npoly, int first);
+int rh_rlwe_rotate_add_q(rh_ring* r, int level, uint64_t gen, const uint64_t* tmp0_dev, const uint64_t* tmp1_dev, uint64_t* ct0_dev,
+                         uint64_t* ct1_dev, int npoly);
+int rh_rlwe_partial_traces_sum(rh_bext* be, int levelQ, int levelP, const uint64_t* in0_dev, const uint64_t* in1_dev, int is_ntt, int offset,
+                               int n, const rh_galois_key* keys, int nkeys, uint64_t* out0_dev, uint64_t* out1_dev, int npoly, int fused);
+
 /* ---- BFV ciphertext multiply: scale-invariant tensoring (schemes/bgv/evaluator.go, the scheme of schemes/bfv) ----------------------
  * rh_bfv pairs ringQ with ringQMul (bgv/params.go:98-108: ceil((bitlen(Q_max) + logN) / 61) NTT-friendly 61-bit primes, none shared
  * with Q) and a plaintext modulus T: newEvaluatorPrecomp (:46-78).  Standard rings of the same degree N >= 16.  RH_ERR_ARG for T = 0,

@@ -196,6 +196,10 @@ class Ring {
   }
   void AutomorphismNTT(const Poly& in, uint64_t gen, Poly& out) const { check(rh_ring_automorphism_ntt(h_.get(), level_, in.data(), gen, out.data(), in.npoly(), 0)); }
   void Automorphism(const Poly& in, uint64_t gen, Poly& out) const { check(rh_ring_automorphism(h_.get(), level_, in.data(), gen, out.data(), in.npoly())); }
+  // ct_c += phi_gen(tmp_c) modulo Q, both components in one launch: the end of AutomorphismHoisted + ringQ.Add (core/rlwe/inner_sum.go:279-280)
+  void RotateAddQ(uint64_t gen, const Poly& tmp0, const Poly& tmp1, Poly& ct0, Poly& ct1) const {
+    check(rh_rlwe_rotate_add_q(h_.get(), level_, gen, tmp0.data(), tmp1.data(), ct0.data(), ct1.data(), ct0.npoly()));
+  }
   // AutomorphismNTTWithIndex / ...ThenAddLazy (ring/automorphism.go:50-117): `index` = a 1-poly, 1-limb device block holding the lookup table
   void AutomorphismNTTWithIndex(const Poly& in, const Poly& index, Poly& out, bool thenAddLazy = false) const {
     check(rh_ring_automorphism_ntt_index(h_.get(), level_, in.data(), index.data(), out.data(), in.npoly(), thenAddLazy ? 1 : 0));
@@ -291,6 +295,18 @@ class BasisExtender {
   }
   void ModDownPair(int lq, int lp, const Poly& ctQ0, const Poly& ctQ1, const Poly& ctP0, const Poly& ctP1, Poly& ct0, Poly& ct1) const {
     check(rh_bext_moddown_qp_to_q_ntt_pair(h_.get(), lq, lp, ctQ0.data(), ctQ1.data(), ctP0.data(), ctP1.data(), ct0.data(), ct1.data(), ct0.npoly()));
+  }
+  // Evaluator.PartialTracesSum (core/rlwe/inner_sum.go:152-291) as one call: out = sum_{i < n} phi_{5^(i offset)}(in); keys: the caller's table of
+  // Galois keys (element, evkQ, evkP, digits); out may be in.  RotateAccumulateQP: the tail of AutomorphismHoistedLazy + ringQP.Add (:245-246)
+  void PartialTracesSum(int lq, int lp, const Poly& in0, const Poly& in1, bool isNTT, int offset, int n, const std::vector<rh_galois_key>& keys,
+                        Poly& out0, Poly& out1, bool fused = true) const {
+    check(rh_rlwe_partial_traces_sum(h_.get(), lq, lp, in0.data(), in1.data(), isNTT ? 1 : 0, offset, n, keys.data(), (int)keys.size(), out0.data(),
+                                     out1.data(), in0.npoly(), fused ? 1 : 0));
+  }
+  void RotateAccumulateQP(int lq, int lp, uint64_t galEl, const Poly& ct0, const Poly& tmpQ0, const Poly& tmpQ1, const Poly& tmpP0, const Poly& tmpP1,
+                          Poly& accQ0, Poly& accQ1, Poly& accP0, Poly& accP1, bool first) const {
+    check(rh_rlwe_rotate_accumulate_qp(h_.get(), lq, lp, galEl, ct0.data(), tmpQ0.data(), tmpQ1.data(), tmpP0.data(), tmpP1.data(), accQ0.data(),
+                                       accQ1.data(), accP0.data(), accP1.data(), ct0.npoly(), first ? 1 : 0));
   }
  private:
   std::shared_ptr<rh_bext> h_;

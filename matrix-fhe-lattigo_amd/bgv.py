@@ -643,6 +643,80 @@ class Evaluator(rlwe.Evaluator):
                     ringQ.MulScalar(el, r, el)                                     # (:1601-1603, :1608-1610)
             ct.Scale = self._scale(ct) * r % self.t                                # (:1606, :1613)
 
+    # ---- rotations :1465-1506, InnerSum / RotateAndAdd :1527-1586 (Replicate and Trace: rlwe.Evaluator's) -------------------------------
+    def GaloisElement(self, k):
+        """Parameters.GaloisElement: 5^k mod 2N"""
+        return rlwe.GaloisElement(self.ringQ.N, k)
+
+    def GaloisElementForRowRotation(self):
+        """GaloisElementOrderTwoOrthogonalSubgroup (core/rlwe/params.go:683-689): 2N - 1"""
+        return 2 * self.ringQ.N - 1
+
+    def _rotate(self, op0, galEl, opOut):
+        self.Automorphism(op0, galEl, opOut)
+        self._copy_metadata(op0, opOut)
+
+    def RotateColumns(self, op0, k, opOut):
+        """:1473-1475: both rows of the 2 x N/2 plaintext matrix rotated by k columns to the left"""
+        self._rotate(op0, self.GaloisElement(k), opOut)
+
+    def RotateColumnsNew(self, op0, k):
+        opOut = self._new(op0.Degree(), op0)
+        self.RotateColumns(op0, k, opOut)
+        return opOut
+
+    def RotateRows(self, op0, opOut):
+        """:1488-1490: the two rows swapped"""
+        self._rotate(op0, self.GaloisElementForRowRotation(), opOut)
+
+    def RotateRowsNew(self, op0):
+        opOut = self._new(op0.Degree(), op0)
+        self.RotateRows(op0, opOut)
+        return opOut
+
+    def RotateHoistedLazyNew(self, level, rotations, op0, c2DecompQP):
+        """:1494-1506: a dict rotation -> rlwe.ElementQP (modulo QP, not yet divided by P) for every rotation other than 0"""
+        if self.ringP is None:
+            raise RingHipError("cannot RotateHoistedLazyNew: the evaluator was built without ringP, which the key switch needs")
+        opOut = {}
+        for i in rotations:
+            if i != 0:
+                opOut[i] = rlwe.ElementQP.alloc(self.ringQ, self.ringP, op0.Value[0].npoly, level, self.ringP.L - 1)
+                self.AutomorphismHoistedLazy(level, op0, c2DecompQP, self.GaloisElement(i), opOut[i])
+        return opOut
+
+    def InnerSum(self, ctIn, batchSize, n, opOut, fused=None):
+        """:1527-1566: the sub-vectors of batchSize slots of each row added together in groups of n.  n batchSize = N sums over BOTH rows:
+        PartialTracesSum with n / 2, RotateRows, Add (:1541-1562).  fused: as rlwe.Evaluator.PartialTracesSum."""
+        N, l = self.ringQ.N, int(n) * int(batchSize)                                  # ctIn.Slots(): a 2 x N/2 matrix
+        if n <= 0 or batchSize <= 0:
+            raise RingHipError("innersum: invalid parameter (n <= 0 or batchSize <= 0)")
+        if l > N:
+            raise RingHipError("innersum: invalid parameters (n*batchSize=%d > #slots=%d)" % (l, N))
+        if l & (l - 1) != 0:
+            raise RingHipError("innersum: invalid parameters (n*batchSize=%d does not divide #slots=%d)" % (l, N))
+        if l != N:
+            return self.PartialTracesSum(ctIn, batchSize, n, opOut, fused=fused)
+        if n == 1:
+            if opOut is not ctIn:
+                ringQ = self.ringQ.AtLevel(self._sum_operands(ctIn, opOut, "InnerSum"))
+                for a, b in zip(ctIn.Value, opOut.Value):
+                    ringQ.CopyLvl(a, b)
+                self._copy_metadata(ctIn, opOut)
+            return
+        g = self.GaloisElementForRowRotation()
+        self._sum_keys([g], "InnerSum")                                               # before the first launch, like the keys of the partial sum
+        self.PartialTracesSum(ctIn, batchSize, n // 2, opOut, fused=fused)
+        level, npoly = opOut.Level(), opOut.Value[0].npoly
+        ringQ = self.ringQ.AtLevel(level)
+        ctTmp = Ciphertext([self.buffer("rowsQ%d" % c, ringQ, npoly, level + 1) for c in (0, 1)], is_ntt=True)
+        self.RotateRows(opOut, ctTmp)
+        self.Add(opOut, ctTmp, opOut)
+
+    def RotateAndAdd(self, ctIn, batchSize, n, opOut, fused=None):
+        """:1583-1586"""
+        self.PartialTracesSum(ctIn, batchSize, n, opOut, fused=fused)
+
 
 # ---- bgv.Encoder, schemes/bgv/encoder.go, on standard rings -------------------------------------------------------------------------------
 def PlaintextRingDegree(N, t):

@@ -735,6 +735,77 @@ class Evaluator:
         self.RotateHoisted(ctIn, rotations, opOut)
         return opOut
 
+    def RotateHoistedLazyNew(self, level, rotations, ct, c2DecompQP):
+        """:1257-1269: a dict rotation -> rlwe.ElementQP (modulo QP, scaled by P: not yet divided by it) for every rotation other than 0"""
+        ks = self._sum_evaluator("RotateHoistedLazyNew")
+        cOut = {}
+        for i in rotations:
+            if i != 0:
+                cOut[i] = rlwe.ElementQP.alloc(self.ringQ, self.ringP, ct.Value[0].npoly, level, self.ringP.L - 1)
+                try:
+                    ks.AutomorphismHoistedLazy(level, ct, c2DecompQP, self.GaloisElement(i), cOut[i])
+                except RingHipError as e:
+                    raise RingHipError("cannot RotateHoistedLazyNew: %s" % e) from None
+        return cOut
+
+    # ---- InnerSum / RotateAndAdd :1271-1317, Replicate (core/rlwe/inner_sum.go:477-479), Trace / Average (linear_transformation.go:13-52) ------------
+    def _sum_evaluator(self, who):
+        if self.ks is None:
+            raise RingHipError("cannot %s: the evaluator was built without ringP, which the key switch needs" % who)
+        return self.ks
+
+    def _slots(self, ct):
+        """ct.Slots(): 2^LogDimensions, the ring's N / 2 slots when the ciphertext does not say"""
+        return 1 << int(getattr(ct, "LogDimensions", self.ringQ.N.bit_length() - 2))
+
+    def InnerSum(self, ctIn, batchSize, n, opOut, fused=None):
+        """:1284-1299: the sub-vectors of batchSize slots added together in groups of n; n batchSize must be a power of two and at most the slot
+        count (RotateAndAdd takes any).  The scale is ctIn's.  fused: as rlwe.Evaluator.PartialTracesSum."""
+        N, l = self._slots(ctIn), int(n) * int(batchSize)
+        if n <= 0 or batchSize <= 0:
+            raise RingHipError("innersum: invalid parameter (n <= 0 or batchSize <= 0)")
+        if l > N:
+            raise RingHipError("innersum: invalid parameters (n*batchSize=%d > #slots=%d)" % (l, N))
+        if l & (l - 1) != 0:
+            raise RingHipError("innersum: invalid parameters (n*batchSize=%d does not divide #slots=%d)" % (l, N))
+        self._sum_evaluator("InnerSum").PartialTracesSum(ctIn, batchSize, n, opOut, fused=fused)
+
+    def RotateAndAdd(self, ctIn, batchSize, n, opOut, fused=None):
+        """:1314-1317: the sum of ctIn rotated by i batchSize slots, 0 <= i < n"""
+        self._sum_evaluator("RotateAndAdd").PartialTracesSum(ctIn, batchSize, n, opOut, fused=fused)
+
+    def Replicate(self, ctIn, batchSize, n, opOut, fused=None):
+        self._sum_evaluator("Replicate").Replicate(ctIn, batchSize, n, opOut, fused=fused)
+
+    def Trace(self, ctIn, logSlots, opOut, fused=None):
+        self._sum_evaluator("Trace").Trace(ctIn, logSlots, opOut, fused=fused)
+
+    def TraceNew(self, ctIn, logSlots, fused=None):
+        """linear_transformation.go:13-16"""
+        opOut = self._new(1, ctIn)
+        self.Trace(ctIn, logSlots, opOut, fused=fused)
+        return opOut
+
+    def Average(self, ctIn, logBatchSize, opOut, fused=None):
+        """linear_transformation.go:24-52: every sub-vector of 2^logBatchSize slots replaced by the average of all of them -- a multiplication by
+        n^-1 mod q_i, n = slots / 2^logBatchSize, then InnerSum(2^logBatchSize, n) in place on opOut"""
+        if ctIn.Degree() != 1 or opOut.Degree() != 1:
+            raise RingHipError("cannot Average: ctIn.Degree() != 1 or opOut.Degree() != 1")
+        logSlots = int(getattr(ctIn, "LogDimensions", self.ringQ.N.bit_length() - 2))
+        if logBatchSize > logSlots:
+            raise RingHipError("cannot Average: batchSize must be smaller or equal to the number of slots")
+        level = min(ctIn.Level(), opOut.Level())
+        rlwe.Evaluator._rows(level, *ctIn.Value, *opOut.Value)
+        rq = self.ringQ.AtLevel(level)
+        n = 1 << (logSlots - logBatchSize)
+        Q = 1
+        for q in self._qs(level):
+            Q *= q
+        for c in (0, 1):
+            rq.MulScalarBigint(ctIn.Value[c], pow(n, -1, Q), opOut.Value[c])      # MulScalarMontgomery by MForm(n^-1 mod q_i) (:41-49)
+        rlwe.Evaluator._copy_metadata(ctIn, opOut)
+        self.InnerSum(opOut, 1 << logBatchSize, n, opOut, fused=fused)
+
 
 # ---- ckks.Encoder, schemes/ckks/encoder.go: the float64 path (prec <= 53) on standard rings -------------------------------------------------
 def GetRootsComplex128(NthRoot):

@@ -166,7 +166,7 @@ bext_sign_copy_kernel(const u64* in, int in_rows, int src_limb, u64 qd, int ntgt
 struct rh_bext {
   rh_ring* Q = nullptr; rh_ring* P = nullptr;
   std::map<std::array<int, 5>, BextPlan> plans;
-  u64* buf[9] = {}; size_t buf_words[9] = {};      // 0,1: ModDownNTT buffers; 2..8: gadget product (keyswitch.hip)
+  u64* buf[11] = {}; size_t buf_words[11] = {};    // 0,1: ModDownNTT buffers; 2..8: gadget product (keyswitch.hip); 6, 9, 10: inner sums (inner_sum.hip)
   std::recursive_mutex mu;
 };
 
@@ -234,7 +234,7 @@ extern "C" void rh_bext_destroy(rh_bext* be) {
     void* ptrs[] = {p.d_S, p.d_T, p.d_coef, p.d_vt, p.d_sign};
     for (void* q : ptrs) if (q) (void)hipFree(q);
   }
-  for (int i = 0; i < 9; ++i) if (be->buf[i]) (void)hipFree(be->buf[i]);
+  for (int i = 0; i < 11; ++i) if (be->buf[i]) (void)hipFree(be->buf[i]);
   delete be;
 }
 
@@ -255,8 +255,8 @@ extern "C" int rh_bext_reserve(rh_bext* be, int npoly) {
   (void)hipSetDevice(be->Q->device);
   const size_t N = be->Q->N, wq = (size_t)npoly * be->Q->L * N, wp = be->P ? (size_t)npoly * be->P->L * N : 0;
   const size_t beta = be->P ? (size_t)(be->Q->L + be->P->L - 1) / be->P->L : 1;
-  const size_t need[9] = {2 * wq, 2 * wp, wq, beta * wq, beta * wp, 2 * wp, 0, wq, wq};
-  for (int i = 0; i < 9; ++i) if (need[i]) if (int rc = ensure_buf(be, i, need[i])) return rc;
+  const size_t need[11] = {2 * wq, 2 * wp, wq, beta * wq, beta * wp, 2 * wp, be->P ? 2 * wq : 0, wq, wq, be->P ? 2 * (wq + wp) : 0, be->P ? 2 * (wq + wp) : 0};
+  for (int i = 0; i < 11; ++i) if (need[i]) if (int rc = ensure_buf(be, i, need[i])) return rc;
   return RH_OK;
 }
 rh_ring* rh_bext_ringQ(rh_bext* be) { return be->Q; }

@@ -12,6 +12,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 U64P = C.POINTER(C.c_uint64)
 # rh_allgather_fn (ringhip.h): (ctx, send_dev, recv_dev, send_words, hip_stream) -> 0 on success
+class GaloisKeyEntry(C.Structure):
+    """rh_galois_key (ringhip.h): one row of the key table rh_rlwe_partial_traces_sum takes"""
+    _fields_ = [("galois_element", C.c_uint64), ("evkQ_dev", C.c_void_p), ("evkP_dev", C.c_void_p), ("digits", C.c_int)]
+
+
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
 Standard = 0   # ring.Standard (ring/ring.go Type)
@@ -130,6 +135,9 @@ def lib():
         "rh_bext_gadget_product_hoisted_lazy": (i, [vp, i, i, vp, vp, vp, vp, i, vp, vp, vp, vp, i]),
         "rh_bext_moddown_qp_to_q_ntt_pair": (i, [vp, i, i, vp, vp, vp, vp, vp, vp, i]),
         "rh_bext_gadget_product_hoisted_then_add": (i, [vp, i, i, vp, vp, vp, vp, i, vp, vp, vp, vp, i]),
+        "rh_rlwe_rotate_accumulate_qp": (i, [vp, i, i, C.c_uint64] + [vp] * 9 + [i, i]),
+        "rh_rlwe_rotate_add_q": (i, [vp, i, C.c_uint64, vp, vp, vp, vp, i]),
+        "rh_rlwe_partial_traces_sum": (i, [vp, i, i, vp, vp, i, i, i, C.POINTER(GaloisKeyEntry), i, vp, vp, i, i]),
         "rh_bfv_create": (i, [C.POINTER(vp), vp, vp, C.c_uint64]), "rh_bfv_destroy": (None, [vp]), "rh_bfv_level_qmul": (i, [vp, i]),
         "rh_bfv_reserve": (i, [vp, i]), "rh_bfv_set_tuning": (i, [vp, C.c_char_p, C.c_long]), "rh_bfv_quantize_path": (i, [vp, i]),
         "rh_bfv_tensor_lazy": (i, [vp, i] + [vp] * 14 + [i, i]), "rh_bfv_quantize": (i, [vp, i, vp, vp, vp, i]),

@@ -9,11 +9,78 @@ the HIP library; no key generation, no encoders (those stay with the reference).
 
 GadgetProduct covers both branches of GadgetProductLazy (:102-121): gadgetProductMultiplePLazy (levelP >= 1) and
 gadgetProductSinglePAndBitDecompLazy (levelP <= 0, optional BaseTwoDecomposition), for NTT- and coefficient-domain ciphertexts.
-The hoisted forms and the automorphism / relinearisation callers take NTT-domain ciphertexts and levelP >= 1."""
+The hoisted forms and the automorphism / relinearisation callers take NTT-domain ciphertexts and levelP >= 1.
+
+  PartialTracesSum       core/rlwe/inner_sum.go:152-291     Trace  :36-121     InnerFunction  :316-440     Replicate  :477-479
+  GaloisElementsForInnerSum  :444-468     GaloisElementsForReplicate  :483-485     GaloisElementsForTrace  :125-146
+
+The sums of rotations take NTT- and coefficient-domain ciphertexts on standard rings, keys with levelP >= 1 and no power-of-two decomposition."""
 import numpy as np
 
-from .ringhip import BasisExtender, DevicePoly, RingHipError, _check, lib
+from .ringhip import BasisExtender, DevicePoly, GaloisKeyEntry, RingHipError, Standard, _check, lib
 from .schemes import Ciphertext
+
+GaloisGen = 5                                                          # ring.GaloisGen (ring/ring.go:17-19)
+METADATA = ("Scale", "LogDimensions", "IsMontgomery", "IsBatched")     # what the scheme layers hang on a Ciphertext besides IsNTT
+
+
+def GaloisElement(N, k, NthRoot=None):
+    """Parameters.GaloisElement (core/rlwe/params.go:671-675): GaloisGen^k mod NthRoot (2N on a standard ring), a negative k taken modulo NthRoot"""
+    NthRoot = 2 * int(N) if NthRoot is None else int(NthRoot)
+    return pow(GaloisGen, int(k) % NthRoot, NthRoot)
+
+
+def GaloisElementsForInnerSum(N, batch, n):
+    """(:444-468): the Galois elements of the rotations i batch and (n - (n & (2i - 1))) batch for i = 1, 2, 4 ... < n, sorted.  A superset of what
+    PartialTracesSum(batch, n) applies: the reference lists the rotation by 0 (element 1) when it occurs and the last power of two too."""
+    rot = set()
+    i = 1
+    while i < n:
+        rot.add(i * batch)
+        rot.add((n - (n & ((i << 1) - 1))) * batch)
+        i <<= 1
+    return sorted({GaloisElement(N, k) for k in rot})
+
+
+def GaloisElementsForReplicate(N, batch, n):
+    """(:483-485)"""
+    return GaloisElementsForInnerSum(N, -batch, n)
+
+
+def GaloisElementsForTrace(N, logN, kind=Standard):
+    """(:125-146): 5^(2^i) for logN <= i < log2(N) - 1, and 2N - 1 for the full trace (logN = 0) of a standard ring"""
+    if kind != Standard:
+        raise RingHipError("cannot GaloisElementsForTrace: standard rings only on the device path")
+    top = int(N).bit_length() - 1
+    out = [GaloisElement(N, 1 << i) for i in range(logN, top - 1)]
+    if logN == 0:
+        out.append(2 * int(N) - 1)                                    # GaloisElementOrderTwoOrthogonalSubgroup
+    return out
+
+
+LAZY, CLOSE, DOUBLE = "lazy", "close", "double"
+
+
+def partial_traces_plan(N, offset, n):
+    """The binary reading of n in PartialTracesSum (:216-282) as a list of steps (kind, Galois element, decompose):
+    LAZY accQP (+)= AutomorphismHoistedLazy(ctInNTT, g); CLOSE opOut = ModDown(accQP) + ctInNTT, or ctInNTT when n is a power of two;
+    DOUBLE ctInNTT += AutomorphismHoisted(ctInNTT, g).  decompose: the step is the first of its iteration to read DecomposeNTT(ctInNTT[1]) --
+    the reference decomposes at the top of EVERY iteration, the last one for nothing (nothing reads it after CLOSE)."""
+    plan, state, i, j = [], False, 0, n
+    while j > 0:
+        fresh = True
+        if j & 1:
+            k = (n - (n & ((2 << i) - 1))) * offset
+            if k != 0:
+                plan.append((LAZY, GaloisElement(N, k), fresh))
+                fresh = False
+            else:
+                state = True
+                plan.append((CLOSE, 0, False))
+        if not state:
+            plan.append((DOUBLE, GaloisElement(N, (1 << i) * offset), fresh))
+        i, j = i + 1, j >> 1
+    return plan
 
 
 class GadgetCiphertext:
@@ -324,3 +391,241 @@ class Evaluator:
         ringQ.MulScalarBigintThenAdd(ctIn.Value[0], P, tmp.Value[0].Q)                    # + ctIn[0] * P (:138-142 as one pass: same canonical values)
         autQ(tmp.Value[0].Q, galEl, ctQP.Value[0].Q)                                      # (:144 / :155)
         autP(tmp.Value[0].P, galEl, ctQP.Value[0].P)
+
+    # ---- core/rlwe/inner_sum.go ------------------------------------------------------------------------------------------------------
+    # Which of the two fused kernels (csrc/inner_sum_kernels.hip.hpp) a call uses when it is not told (fused=None): the measured choice -- a kernel is
+    # the default where the run shows it no slower than its composed form, alone and in the whole call (profiles/inner_sum.json).
+    # fused=True / False selects both / neither; the bits are the same.
+    FUSED_INNER_SUM = {"accumulate": True, "rotate_add": True}
+
+    def _fused_inner_sum(self, fused):
+        return dict(self.FUSED_INNER_SUM) if fused is None else {k: bool(fused) for k in self.FUSED_INNER_SUM}
+
+    def RotateAccumulateQP(self, levelQ, galEl, ct0, tmpQP, accQP, first):
+        """accQP (=|+=) phi_galEl(tmpQP + (P ct0, 0)) modulo QP in one launch: the tail of AutomorphismHoistedLazy (evaluator_automorphism.go:107-160)
+        and ringQP.Add (inner_sum.go:245-246).  tmpQP: the output of GadgetProductHoistedLazy; first: accQP is written, not added to."""
+        levelP = tmpQP.LevelP()
+        q, p = [v.Q for v in tmpQP.Value + accQP.Value], [v.P for v in tmpQP.Value + accQP.Value]
+        self._rows(levelQ, ct0, *q)
+        self._rows(levelP, *p)
+        _check(lib().rh_rlwe_rotate_accumulate_qp(self.be._h, levelQ, levelP, int(galEl), ct0.ptr, q[0].ptr, q[1].ptr, p[0].ptr, p[1].ptr,
+                                                  q[2].ptr, q[3].ptr, p[2].ptr, p[3].ptr, ct0.npoly, 1 if first else 0))
+
+    def RotateAddQ(self, level, galEl, tmp, ct):
+        """ct += phi_galEl(tmp) modulo Q, both components in one launch, in place on ct: the AutomorphismNTT pair that ends AutomorphismHoisted
+        (evaluator_automorphism.go:90-95) and the ringQ.Add pair that follows it (inner_sum.go:279-280)"""
+        self._rows(level, *tmp.Value, *ct.Value)
+        _check(lib().rh_rlwe_rotate_add_q(self.ringQ._h, level, int(galEl), tmp.Value[0].ptr, tmp.Value[1].ptr, ct.Value[0].ptr, ct.Value[1].ptr,
+                                          ct.Value[0].npoly))
+
+    def _sum_operands(self, ctIn, opOut, who):
+        if ctIn.Degree() != 1 or opOut.Degree() != 1:
+            raise RingHipError("cannot %s: ctIn.Degree() != 1 or opOut.Degree() != 1" % who)
+        if self.ringQ.kind != Standard:
+            raise RingHipError("cannot %s: 3N and conjugate-invariant rings are not supported by the device path" % who)
+        if self.ringP is None:
+            raise RingHipError("cannot %s: the evaluator was built without ringP, which the key switch needs" % who)
+        level = ctIn.Level()
+        self._rows(level, *ctIn.Value, *opOut.Value)
+        if opOut.Value[0].npoly != ctIn.Value[0].npoly:
+            raise RingHipError("cannot %s: ctIn and opOut hold different numbers of ciphertexts" % who)
+        return level
+
+    def _sum_keys(self, galEls, who):
+        """every key a sum of rotations needs, looked up before the first launch (CheckAndGetGaloisKey for each element)"""
+        keys = {}
+        for g in galEls:
+            if g not in self.galois_keys:
+                raise RingHipError("cannot apply %s: GaloisKey[%d] is missing" % (who, g))
+            evk = keys[g] = self.galois_keys[g]
+            if evk.BaseTwoDecomposition != 0:
+                raise RingHipError("cannot apply %s: method is unsupported for BaseTwoDecomposition != 0" % who)   # gadgetProductMultiplePLazyHoisted's own text
+            if evk.LevelP() < 1:
+                raise RingHipError("cannot apply %s: GaloisKey[%d] has one P modulus, which the hoisted product of the device path does not take (levelP >= 1)" % (who, g))
+        return keys
+
+    @staticmethod
+    def _copy_metadata(ctIn, opOut):
+        for name in METADATA:                                            # *opOut.MetaData = *ctIn.MetaData
+            if hasattr(ctIn, name):
+                setattr(opOut, name, getattr(ctIn, name))
+        opOut.IsNTT = ctIn.IsNTT
+
+    def _sum_buffers(self, levelQ, levelP, npoly):
+        """ctInNTT (BuffCt), accQP (BuffQP[2:4]), cQP (BuffQP[4:6]) and BuffDecompQP, evaluator-owned"""
+        rq, rp = self.ringQ.AtLevel(levelQ), self.ringP.AtLevel(levelP)
+        beta = self.BaseRNSDecompositionVectorSize(levelQ, levelP)
+        qp = lambda t: ElementQP([PolyQP(self.buffer(t + "Q%d" % c, rq, npoly, levelQ + 1), self.buffer(t + "P%d" % c, rp, npoly, levelP + 1)) for c in (0, 1)])
+        ct = Ciphertext([self.buffer("BuffCt%d" % c, rq, npoly, levelQ + 1) for c in (0, 1)], is_ntt=True)
+        dec = (self.buffer("BuffDecompQ", rq, beta * npoly, levelQ + 1), self.buffer("BuffDecompP", rp, beta * npoly, levelP + 1))
+        return ct, qp("sumAcc"), qp("sumC"), dec
+
+    def PartialTracesSum(self, ctIn, offset, n, opOut, fused=None):
+        """(:152-291): opOut = sum_{i < n} phi_{5^(i offset)}(ctIn) with log2(n) hoisted and HW(n) - 1 lazy rotations under one ModDown, by the
+        reference's binary reading of n.  opOut may be ctIn.  A coefficient-domain ctIn is transformed on entry and the result transformed back
+        (:180-182, :285-288 -- for n = 1 too, where the reference copies and then applies INTT to the copy: kept).  The keys are used at
+        ctIn.Level(); every one is looked up before the first launch.  fused: the kernels of csrc/inner_sum.hip (True), the composition of
+        DecomposeNTT / AutomorphismHoisted(Lazy) / Add / ModDown (False), FUSED_INNER_SUM per kernel (None) -- the same bits."""
+        n, offset = int(n), int(offset)
+        if n <= 0 or offset == 0:
+            raise RingHipError("partialtrace: invalid parameter (n = 0 or batchSize = 0)")
+        levelQ = self._sum_operands(ctIn, opOut, "PartialTracesSum")
+        levelP = self.ringP.L - 1
+        use = self._fused_inner_sum(fused)
+        plan = partial_traces_plan(self.ringQ.N, offset, n) if n > 1 else []
+        keys = self._sum_keys([g for kind, g, _ in plan if kind == LAZY or (kind == DOUBLE and g != 1)], "PartialTracesSum")
+        rq, rp = self.ringQ.AtLevel(levelQ), self.ringP.AtLevel(levelP)
+        npoly = ctIn.Value[0].npoly
+        ct, acc, cqp, dec = self._sum_buffers(levelQ, levelP, npoly)
+        cq = Ciphertext([cqp.Value[0].Q, cqp.Value[1].Q], is_ntt=True)
+        in_ntt = ctIn.IsNTT
+        for c in (0, 1):                                                 # ctInNTT (:180-186)
+            (rq.CopyLvl if in_ntt else rq.NTT)(ctIn.Value[c], ct.Value[c])
+        if n == 1 and opOut is not ctIn:                                 # (:188-192)
+            for c in (0, 1):
+                rq.CopyLvl(ctIn.Value[c], opOut.Value[c])
+        add_q = lambda a, b: [rq.vec_op("ADD", a.Value[c], b.Value[c], a.Value[c]) for c in (0, 1)]
+        first = True
+        for kind, g, decompose in plan:
+            if decompose:
+                self.DecomposeNTT(levelQ, levelP, ct.Value[1], True, dec)                        # (:222)
+            if kind == LAZY and use["accumulate"]:                                               # (:236-247), the tail in one launch
+                self.GadgetProductHoistedLazy(levelQ, dec, keys[g], cqp)
+                self.RotateAccumulateQP(levelQ, g, ct.Value[0], cqp, acc, first)
+                first = False
+            elif kind == LAZY:
+                self.AutomorphismHoistedLazy(levelQ, ct, dec, g, acc if first else cqp)
+                if not first:
+                    for c in (0, 1):
+                        rq.vec_op("ADD", acc.Value[c].Q, cqp.Value[c].Q, acc.Value[c].Q)        # ringQP.Add (:245-246)
+                        rp.vec_op("ADD", acc.Value[c].P, cqp.Value[c].P, acc.Value[c].P)
+                first = False
+            elif kind == CLOSE and n & (n - 1):                                                  # opOut = accQP / P + ctInNTT (:258-262)
+                view = Ciphertext(opOut.Value, is_ntt=True)                                      # opOut's flag is the caller's until the call has succeeded
+                self.ModDown(levelQ, levelP, acc, view)
+                add_q(opOut, ct)
+            elif kind == CLOSE:                                                                  # (:265-266)
+                for c in (0, 1):
+                    rq.CopyLvl(ct.Value[c], opOut.Value[c])
+            elif g == 1:                                                                         # AutomorphismHoisted of the identity copies (:68-73)
+                add_q(ct, ct)
+            elif use["rotate_add"]:                                                              # (:276-280), the tail in one launch
+                evk = keys[g]
+                _check(lib().rh_bext_gadget_product_hoisted_then_add(self.be._h, levelQ, evk.LevelP(), dec[0].ptr, dec[1].ptr, evk.Q.ptr, evk.P.ptr, evk.digits,
+                                                                     ct.Value[0].ptr, None, cq.Value[0].ptr, cq.Value[1].ptr, npoly))
+                self.RotateAddQ(levelQ, g, cq, ct)
+            else:
+                self.AutomorphismHoisted(levelQ, ct, dec, g, cq)
+                add_q(ct, cq)
+        if not in_ntt:                                                   # (:285-288)
+            for c in (0, 1):
+                rq.INTT(opOut.Value[c], opOut.Value[c])
+        self._copy_metadata(ctIn, opOut)
+
+    def PartialTracesSumC(self, ctIn, offset, n, opOut, fused=None):
+        """PartialTracesSum as ONE call into the library (rh_rlwe_partial_traces_sum): what a compiled host uses.  fused: both kernels or neither."""
+        n, offset = int(n), int(offset)
+        if n <= 0 or offset == 0:
+            raise RingHipError("partialtrace: invalid parameter (n = 0 or batchSize = 0)")
+        levelQ = self._sum_operands(ctIn, opOut, "PartialTracesSum")
+        plan = partial_traces_plan(self.ringQ.N, offset, n) if n > 1 else []
+        keys = self._sum_keys([g for kind, g, _ in plan if kind == LAZY or (kind == DOUBLE and g != 1)], "PartialTracesSum")
+        table = (GaloisKeyEntry * max(len(keys), 1))()
+        for i, (g, evk) in enumerate(keys.items()):
+            table[i] = GaloisKeyEntry(g, evk.Q.ptr, evk.P.ptr, evk.digits)
+        use = self._fused_inner_sum(fused)
+        _check(lib().rh_rlwe_partial_traces_sum(self.be._h, levelQ, self.ringP.L - 1, ctIn.Value[0].ptr, ctIn.Value[1].ptr, 1 if ctIn.IsNTT else 0, offset, n,
+                                                table, len(keys), opOut.Value[0].ptr, opOut.Value[1].ptr, ctIn.Value[0].npoly,
+                                                1 if all(use.values()) else 0))
+        self._copy_metadata(ctIn, opOut)
+
+    def Replicate(self, ctIn, batchSize, n, opOut, fused=None):
+        """(:477-479): the inverse of an inner sum, PartialTracesSum by -batchSize"""
+        self.PartialTracesSum(ctIn, -int(batchSize), n, opOut, fused=fused)
+
+    def Trace(self, ctIn, logN, opOut, fused=None):
+        """(:36-121): X -> sum of the automorphisms 5^(2^i), logN <= i < log2(N) - 1 (and 2N - 1 when logN = 0), pre-multiplied by (N / 2^logN)^-1:
+        monomials X^k with N / 2^logN not dividing k vanish, the others are kept.  opOut may be ctIn."""
+        level = self._sum_operands(ctIn, opOut, "Trace")
+        N, top = self.ringQ.N, self.ringQ.N.bit_length() - 1
+        gap = 1 << (top - logN - 1)
+        if logN == 0:
+            gap <<= 1
+        rq = self.ringQ.AtLevel(level)
+        if gap <= 1:
+            if opOut is not ctIn:
+                for c in (0, 1):
+                    rq.CopyLvl(ctIn.Value[c], opOut.Value[c])
+            self._copy_metadata(ctIn, opOut)
+            return
+        galEls = GaloisElementsForTrace(N, logN)
+        keys = self._sum_keys(galEls, "Trace")
+        use = self._fused_inner_sum(fused)
+        in_ntt = ctIn.IsNTT
+        Q = 1
+        for q in self.ringQ.moduli[:level + 1]:
+            Q *= int(q)
+        NInv = pow(gap, -1, Q)
+        npoly = ctIn.Value[0].npoly
+        buff = Ciphertext([self.buffer("traceQ%d" % c, rq, npoly, level + 1) for c in (0, 1)], is_ntt=True)
+        for c in (0, 1):
+            rq.MulScalarBigint(ctIn.Value[c], NInv, opOut.Value[c])      # pre-multiplication by (N/n)^-1 (:69-70)
+            if not in_ntt:
+                rq.NTT(opOut.Value[c], opOut.Value[c])
+        view = Ciphertext(opOut.Value, is_ntt=True)                      # opOut's flag is the caller's until the call has succeeded
+        for g in galEls:                                                 # (:88-106)
+            if use["rotate_add"]:                                        # Automorphism's product + Add (:42-44), then its index maps and the Adds in one launch
+                self.GadgetProductThenAdd(level, opOut.Value[1], keys[g], opOut.Value[0], None, buff)
+                self.RotateAddQ(level, g, buff, opOut)
+            else:
+                self.Automorphism(view, g, buff)
+                for c in (0, 1):
+                    rq.vec_op("ADD", opOut.Value[c], buff.Value[c], opOut.Value[c])
+        if not in_ntt:
+            for c in (0, 1):
+                rq.INTT(opOut.Value[c], opOut.Value[c])
+        self._copy_metadata(ctIn, opOut)
+
+    def InnerFunction(self, ctIn, batchSize, n, f, opOut):
+        """(:316-440): the tree of PartialTracesSum with a caller's f(a, b, c) -- a Python callable on device ciphertexts, c = f(a, b) -- in place
+        of the additions, and plain (not hoisted) automorphisms.  f = Add gives the inner sum."""
+        n, batchSize = int(n), int(batchSize)
+        levelQ = self._sum_operands(ctIn, opOut, "InnerFunction")
+        rq = self.ringQ.AtLevel(levelQ)
+        npoly = ctIn.Value[0].npoly
+        plan = partial_traces_plan(self.ringQ.N, batchSize, n) if n > 1 else []
+        self._sum_keys([g for kind, g, _ in plan if kind != CLOSE and g != 1], "InnerFunction")
+        new = lambda: Ciphertext([rq.NewPoly(npoly), rq.NewPoly(npoly)], is_ntt=True)
+        ct, accQ, cQ = new(), new(), new()
+        for x in (ct, accQ, cQ):
+            self._copy_metadata(ctIn, x)
+            x.IsNTT = True
+        in_ntt = ctIn.IsNTT
+        copy = lambda a, b: [rq.CopyLvl(a.Value[c], b.Value[c]) for c in (0, 1)]
+        for c in (0, 1):
+            (rq.CopyLvl if in_ntt else rq.NTT)(ctIn.Value[c], ct.Value[c])
+        if n == 1 and opOut is not ctIn:
+            copy(ctIn, opOut)
+        self._copy_metadata(ctIn, opOut)
+        opOut.IsNTT = True                                               # f sees NTT-domain operands; the caller's flag comes back whatever happens
+        try:
+            first = True
+            for kind, g, _ in plan:
+                if kind == LAZY:
+                    self.Automorphism(ct, g, accQ if first else cQ)
+                    if not first:
+                        f(accQ, cQ, accQ)
+                    first = False
+                elif kind == CLOSE and n & (n - 1):
+                    copy(accQ, opOut)
+                    f(opOut, ct, opOut)
+                elif kind == CLOSE:
+                    copy(ct, opOut)
+                else:
+                    self.Automorphism(ct, g, cQ)
+                    f(ct, cQ, ct)
+            if not in_ntt:
+                for c in (0, 1):
+                    rq.INTT(opOut.Value[c], opOut.Value[c])
+        finally:
+            opOut.IsNTT = in_ntt

@@ -8,7 +8,9 @@ against the reference's sequence of ring calls) and writes profiles/bgv_ops.json
 `bench_ops.py ckks_encoder [OUT.json]` the CKKS encoder (Encode, Decode and the two transforms at N = 2^16, 24 limbs, full slots, 64 vectors)
 against its algorithmic bytes, and writes profiles/ckks_encoder.json; `bench_ops.py bgv_encoder [OUT.json]` the BGV encoder (Encode, Decode,
 the lift and Q to T alone, one kernel each against the reference's sequence of ring calls, at N = 2^16, 24 limbs, 64 vectors, T = 65537 for
-gap 2 and T = 786433 for gap 1) and writes profiles/bgv_encoder.json."""
+gap 2 and T = 786433 for gap 1) and writes profiles/bgv_encoder.json; `bench_ops.py inner_sum [OUT.json]` the sums of rotations
+(PartialTracesSum for n = 7 and n = 8 at the config 5 ring, fused against composed, and each of the two kernels of csrc/inner_sum.hip against the
+passes it replaces) and writes profiles/inner_sum.json."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -392,6 +394,102 @@ def bgv_encoder_group(out_path):
         fh.write("\n")
     print(json.dumps(res, indent=1))
     rq.close()
+
+
+def inner_sum_group(out_path):
+    """The config 5 ring of ckks_group: N = 2^16, 24 limbs of Qi60, 6 of Pi60, batch 64.  rlwe.Evaluator.PartialTracesSum(offset 1) for n = 7 (three
+    decompositions, two lazy rotations accumulated modulo QP, two hoisted ones, one ModDown) and n = 8 (three hoisted rotations), with fused=True
+    (csrc/inner_sum.hip) against fused=False, the same sequence composed from DecomposeNTT / AutomorphismHoisted(Lazy) / Add / ModDown; and each
+    kernel alone against the passes it replaces.  Both paths are timed HERE, in alternating windows, as in ckks_group; `fused_default` is the rule
+    rlwe.Evaluator.FUSED_INNER_SUM follows: the fused median within the composed windows' max - min of the composed median, or below it.
+    Whole-row passes (row-words moved per coefficient set): the accumulate tail 13 against 23, the rotate-add tail 6 against 10."""
+    import statistics
+    N, LQ, LP, B, rounds, reps = 1 << 16, 24, 6, 64, 7, 10
+    Q, P = QI60[:LQ], PI60[:LP]
+    rq, rp = rh.Ring(N, Q), rh.Ring(N, P); rq.set_stream(stream.cuda_stream); rp.set_stream(stream.cuda_stream)
+    digits = (LQ + LP - 1) // LP
+    level, levelP = LQ - 1, LP - 1
+
+    def key():
+        k = rh.rlwe.GadgetCiphertext.__new__(rh.rlwe.GadgetCiphertext)
+        k.digits, k.levelQ, k.levelP, k.BaseTwoDecomposition, k.digits_per_limb = digits, level, levelP, 0, None
+        k.Q, k.P = rh.DevicePoly.from_torch(rq, rand_block(2 * digits, Q, N)), rh.DevicePoly.from_torch(rp, rand_block(2 * digits, P, N))
+        return k
+    galEls = sorted({g for n in (7, 8) for kind, g, _ in rh.rlwe.partial_traces_plan(N, 1, n) if kind != rh.rlwe.CLOSE})
+    ev = rh.rlwe.Evaluator(rq, rp, galois_keys={g: key() for g in galEls})
+    mkq = lambda: rh.DevicePoly.from_torch(rq, rand_block(B, Q, N))
+    mkp = lambda: rh.DevicePoly.from_torch(rp, rand_block(B, P, N))
+    ct, out = rh.Ciphertext([mkq(), mkq()], is_ntt=True), rh.Ciphertext([mkq(), mkq()], is_ntt=True)
+    qp = lambda: rh.rlwe.ElementQP([rh.rlwe.PolyQP(mkq(), mkp()), rh.rlwe.PolyQP(mkq(), mkp())])
+    tmp, acc, rot = qp(), qp(), qp()
+    g = galEls[-1]
+    Pbig = 1
+    for p in P:
+        Pbig *= int(p)
+
+    def tail_composed():                              # AutomorphismHoistedLazy after its product, then ringQP.Add: 1 + 4 + 4 passes
+        rq.MulScalarBigintThenAdd(ct.Value[0], Pbig, tmp.Value[0].Q)
+        for c in (1, 0):
+            rq.AutomorphismNTT(tmp.Value[c].Q, g, rot.Value[c].Q); rp.AutomorphismNTT(tmp.Value[c].P, g, rot.Value[c].P)
+        for c in (0, 1):
+            rq.vec_op("ADD", acc.Value[c].Q, rot.Value[c].Q, acc.Value[c].Q); rp.vec_op("ADD", acc.Value[c].P, rot.Value[c].P, acc.Value[c].P)
+
+    def rotate_add_composed():                        # the end of AutomorphismHoisted, then ringQ.Add: 2 + 2 passes
+        for c in (0, 1):
+            rq.AutomorphismNTT(tmp.Value[c].Q, g, rot.Value[c].Q)
+        for c in (0, 1):
+            rq.vec_op("ADD", out.Value[c], rot.Value[c].Q, out.Value[c])
+    tq = rh.Ciphertext([tmp.Value[0].Q, tmp.Value[1].Q], is_ntt=True)
+    cases = {
+        "PartialTracesSum n = 7": (lambda f: ev.PartialTracesSum(ct, 1, 7, out, fused=f), None, None),
+        "PartialTracesSum n = 8": (lambda f: ev.PartialTracesSum(ct, 1, 8, out, fused=f), None, None),
+        "rotate and accumulate modulo QP, the kernel alone": (lambda f: ev.RotateAccumulateQP(level, g, ct.Value[0], tmp, acc, False) if f else tail_composed(), 13, 23),
+        "rotate and add modulo Q, the kernel alone": (lambda f: ev.RotateAddQ(level, g, tq, out) if f else rotate_add_composed(), 6, 10),
+    }
+    res = []
+    for fused in (True, False):                       # same bits first, at the timed shape
+        ev.PartialTracesSum(ct, 1, 7, out, fused=fused)
+        res.append([v.numpy() for v in out.Value])
+    assert all(np.array_equal(x, y) for x, y in zip(*res)), "fused and composed PartialTracesSum differ"
+    del res
+    stat = lambda v: {"ms_median": round(statistics.median(v), 4), "ms_min": round(min(v), 4), "ms_max": round(max(v), 4)}
+    results = []
+    row_bytes = 8.0 * N * B                           # one row-word per coefficient set: (LQ + LP) rows modulo QP, LQ modulo Q
+    for name, (fn, pf, pc) in cases.items():
+        tf, tc = [], []
+        for _ in range(rounds):
+            tf.append(timed(lambda: fn(True), reps=reps)); tc.append(timed(lambda: fn(False), reps=reps))
+        f, c = stat(tf), stat(tc)
+        spread = round(c["ms_max"] - c["ms_min"], 4)
+        entry_ = {"op": name, "fused": f, "composed": c, "ratio_composed_over_fused": round(c["ms_median"] / f["ms_median"], 3),
+                  "composed_run_to_run_spread_ms": spread, "fused_default": bool(f["ms_median"] <= c["ms_median"] + spread)}
+        if pf == 13:                                  # per coefficient set: 2 (acc in, out) + 1 (tmp) per Q and P row and component, + ct0 on the Q rows of one = 13 / 23 words
+            words = lambda per_qp, extra_q: (per_qp * 2 * (LQ + LP) + extra_q * LQ) * row_bytes
+            f["algorithmic_GBps"] = round(words(3, 1) / (f["ms_median"] * 1e-3) / 1e9, 1)
+            c["algorithmic_GBps"] = round(words(5, 3) / (c["ms_median"] * 1e-3) / 1e9, 1)
+        elif pf == 6:
+            f["algorithmic_GBps"] = round(6 * LQ * row_bytes / (f["ms_median"] * 1e-3) / 1e9, 1)
+            c["algorithmic_GBps"] = round(10 * LQ * row_bytes / (c["ms_median"] * 1e-3) / 1e9, 1)
+        if pf:
+            entry_["row_words_fused"], entry_["row_words_composed"] = pf, pc
+            f["frac_of_8TBps"] = round(f["algorithmic_GBps"] / PEAK, 3)
+        results.append(entry_)
+    from bench import csrc_tree_hash
+    res = {"device": torch.cuda.get_device_name(0), "csrc_tree": csrc_tree_hash(), "shape": {"N": N, "limbs_Q": LQ, "limbs_P": LP, "batch": B, "offset": 1},
+           "method": "%d alternating windows of %d calls each, device events, 2 warm-up calls per window; clocks left to the driver's default governor"
+                     % (rounds, reps),
+           "results": results}
+    with open(out_path, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(res, indent=1))
+    ev.close()
+    rq.close(); rp.close()
+
+
+if sys.argv[1:2] == ["inner_sum"]:
+    inner_sum_group(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "inner_sum.json"))
+    sys.exit(0)
 
 
 if sys.argv[1:2] == ["bgv_encoder"]:
