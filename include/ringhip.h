@@ -392,6 +392,44 @@ int rh_rlwe_rotate_add_q(rh_ring* r, int level, uint64_t gen, const uint64_t* tm
 int rh_rlwe_partial_traces_sum(rh_bext* be, int levelQ, int levelP, const uint64_t* in0_dev, const uint64_t* in1_dev, int is_ntt, int offset,
                                int n, const rh_galois_key* keys, int nkeys, uint64_t* out0_dev, uint64_t* out1_dev, int npoly, int fused);
 
+/* ---- ring packing (core/rlwe/ring_packing.go).  Standard rings (RH_ERR_UNSUPPORTED otherwise), dense blocks of level+1 limbs per poly, canonical
+ * residues in and out, both components of a batch of ciphertexts in one launch; the NTT-domain index map of the Galois element (any odd number,
+ * taken modulo 2N) is computed in the kernel.  Every block is 16-byte aligned and no written block may overlap a read one (RH_ERR_ARG).
+ *   rh_rlwe_expand_step      one level of Expand for the live prefix ct[0 .. cnt) of a batch of at least 2 cnt polys (ring_packing.go:555-575: the two
+ *                            AutomorphismNTT that end Automorphism, the CopyNew, and the Add, Sub and MulCoeffsMontgomery pairs):
+ *                              ct[p][j] = ct[p][j] + t,  ct[cnt + p][j] = (ct[p][j] - t) * xpow[l][j],  t = tmp[p][index(j)]
+ *                            tmp: the un-permuted output of the key switch (cnt polys per component); xpow: X^(-2^i), one poly, NTT domain,
+ *                            Montgomery form.  Levels without a second output are rh_rlwe_rotate_add_q.
+ *   rh_rlwe_pack_combine     one level of Pack before its key switch (ring_packing.go:726-745, :762, :781).  The level's plan is a table of K int32
+ *                            triples (mode, slot_a, slot_b) over the nslots polys of the batch, on the device for the kernel and on the host for the
+ *                            check (out of range, or a slot named twice: RH_ERR_ARG).  With bx = b * xpow:
+ *                              mode 2 (a and b): u[k] = a - bx, a = a + bx in place;  mode 1 (b alone): b = bx in place, u[k] = bx;  mode 0 (a alone): u[k] = a
+ *                            u: the contiguous batch of K polys per component that the level's one key switch reads.
+ *   rh_rlwe_rotate_addsub_q  one level of Pack after its key switch (ring_packing.go:768-769, :786-787), same table:
+ *                              slot[j] = slot[j] +- tmp[k][index(j)],  slot = slot_b and minus for mode 1, slot_a and plus otherwise
+ *   rh_rlwe_ring_split       X -> Y = X^gap on COEFFICIENT-domain rows, gap = 2^logGap (SwitchCiphertextRingDegree, core/rlwe/element.go:293-312, and the
+ *                            middle of SwitchCiphertextRingDegreeNTT, :256-268): even[i] = in[i gap] and, when odd0 / odd1 are given, odd[i] = in[i gap + 1],
+ *                            as rows of the ring of degree N / gap.  With gap = 2 the two halves of Split; the odd half replaces the multiplication
+ *                            by X^-1 and the second inverse transform of ring_packing.go:239-241 (the same canonical residues).
+ *   rh_rlwe_ring_merge       Y = X^gap -> X in the NTT domain (MapSmallDimensionToLargerDimensionNTT, ring/operations.go:380-392) and, with odd0 / odd1 and
+ *                            the table xpow = X^1 of the large ring, Merge's sum (ring_packing.go:429-434): out[i gap + w] = even[i] + odd[i] * xpow[l][i gap + w]
+ *   rh_rlwe_expand           the whole of Expand (ring_packing.go:475-594) on NTT-domain inputs: ct0 / ct1 hold nin << (logN - logGap) polys, the nin inputs
+ *                            first; on return the ciphertext of coefficient m 2^logGap of input b is poly m nin + b.  xinvpow: logN polys of xrows limbs,
+ *                            X^(-2^i) (GenXPow2NTT, :795-833).  keys: the caller's table, every element N / 2^i + 1 looked up BEFORE the first launch
+ *                            (a missing one is RH_ERR_ARG naming it).  levelP >= 1.  Scratch is the extender's; asynchronous. */
+int rh_rlwe_expand_step(rh_ring* r, int level, uint64_t gen, const uint64_t* tmp0_dev, const uint64_t* tmp1_dev, uint64_t* ct0_dev, uint64_t* ct1_dev,
+                        const uint64_t* xpow_dev, int cnt);
+int rh_rlwe_pack_combine(rh_ring* r, int level, uint64_t* ct0_dev, uint64_t* ct1_dev, int nslots, const int32_t* table_dev, const int32_t* table_host,
+                         int K, const uint64_t* xpow_dev, uint64_t* u0_dev, uint64_t* u1_dev);
+int rh_rlwe_rotate_addsub_q(rh_ring* r, int level, uint64_t gen, const uint64_t* tmp0_dev, const uint64_t* tmp1_dev, uint64_t* ct0_dev, uint64_t* ct1_dev,
+                            int nslots, const int32_t* table_dev, const int32_t* table_host, int K);
+int rh_rlwe_ring_split(rh_ring* r, int level, const uint64_t* in0_dev, const uint64_t* in1_dev, uint64_t* even0_dev, uint64_t* even1_dev,
+                       uint64_t* odd0_dev, uint64_t* odd1_dev, int logGap, int npoly);
+int rh_rlwe_ring_merge(rh_ring* r, int level, const uint64_t* even0_dev, const uint64_t* even1_dev, const uint64_t* odd0_dev, const uint64_t* odd1_dev,
+                       const uint64_t* xpow_dev, uint64_t* out0_dev, uint64_t* out1_dev, int logGap, int npoly);
+int rh_rlwe_expand(rh_bext* be, int levelQ, int levelP, uint64_t* ct0_dev, uint64_t* ct1_dev, int nin, int logGap, const uint64_t* xinvpow_dev,
+                   int xrows, const rh_galois_key* keys, int nkeys);
+
 /* ---- BFV ciphertext multiply: scale-invariant tensoring (schemes/bgv/evaluator.go, the scheme of schemes/bfv) ----------------------
  * rh_bfv pairs ringQ with ringQMul (bgv/params.go:98-108: ceil((bitlen(Q_max) + logN) / 61) NTT-friendly 61-bit primes, none shared
  * with Q) and a plaintext modulus T: newEvaluatorPrecomp (:46-78).  Standard rings of the same degree N >= 16.  RH_ERR_ARG for T = 0,

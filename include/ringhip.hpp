@@ -200,6 +200,24 @@ class Ring {
   void RotateAddQ(uint64_t gen, const Poly& tmp0, const Poly& tmp1, Poly& ct0, Poly& ct1) const {
     check(rh_rlwe_rotate_add_q(h_.get(), level_, gen, tmp0.data(), tmp1.data(), ct0.data(), ct1.data(), ct0.npoly()));
   }
+  // core/rlwe/ring_packing.go, one level at a time over a batch (see ringhip.h): ExpandStep (:555-575), PackCombine / RotateAddSubQ (:726-787) with the
+  // level's table of (mode, slot_a, slot_b) on the device and on the host, RingSplit / RingMerge (element.go:250-312, ring/operations.go:380-392)
+  void ExpandStep(uint64_t gen, const Poly& tmp0, const Poly& tmp1, Poly& ct0, Poly& ct1, const Poly& xpow, int cnt) const {
+    check(rh_rlwe_expand_step(h_.get(), level_, gen, tmp0.data(), tmp1.data(), ct0.data(), ct1.data(), xpow.data(), cnt));
+  }
+  void PackCombine(Poly& ct0, Poly& ct1, const int32_t* table_dev, const std::vector<int32_t>& table, const Poly& xpow, Poly& u0, Poly& u1) const {
+    check(rh_rlwe_pack_combine(h_.get(), level_, ct0.data(), ct1.data(), ct0.npoly(), table_dev, table.data(), (int)(table.size() / 3), xpow.data(), u0.data(), u1.data()));
+  }
+  void RotateAddSubQ(uint64_t gen, const Poly& tmp0, const Poly& tmp1, Poly& ct0, Poly& ct1, const int32_t* table_dev, const std::vector<int32_t>& table) const {
+    check(rh_rlwe_rotate_addsub_q(h_.get(), level_, gen, tmp0.data(), tmp1.data(), ct0.data(), ct1.data(), ct0.npoly(), table_dev, table.data(), (int)(table.size() / 3)));
+  }
+  void RingSplit(const Poly& in0, const Poly& in1, Poly& even0, Poly& even1, Poly* odd0, Poly* odd1, int logGap = 1) const {
+    check(rh_rlwe_ring_split(h_.get(), level_, in0.data(), in1.data(), even0.data(), even1.data(), odd0 ? odd0->data() : nullptr, odd1 ? odd1->data() : nullptr, logGap, in0.npoly()));
+  }
+  void RingMerge(const Poly& even0, const Poly& even1, const Poly* odd0, const Poly* odd1, const Poly* xpow, Poly& out0, Poly& out1, int logGap = 1) const {
+    check(rh_rlwe_ring_merge(h_.get(), level_, even0.data(), even1.data(), odd0 ? odd0->data() : nullptr, odd1 ? odd1->data() : nullptr, xpow ? xpow->data() : nullptr,
+                             out0.data(), out1.data(), logGap, out0.npoly()));
+  }
   // AutomorphismNTTWithIndex / ...ThenAddLazy (ring/automorphism.go:50-117): `index` = a 1-poly, 1-limb device block holding the lookup table
   void AutomorphismNTTWithIndex(const Poly& in, const Poly& index, Poly& out, bool thenAddLazy = false) const {
     check(rh_ring_automorphism_ntt_index(h_.get(), level_, in.data(), index.data(), out.data(), in.npoly(), thenAddLazy ? 1 : 0));
@@ -302,6 +320,10 @@ class BasisExtender {
                         Poly& out0, Poly& out1, bool fused = true) const {
     check(rh_rlwe_partial_traces_sum(h_.get(), lq, lp, in0.data(), in1.data(), isNTT ? 1 : 0, offset, n, keys.data(), (int)keys.size(), out0.data(),
                                      out1.data(), in0.npoly(), fused ? 1 : 0));
+  }
+  // RingPackingEvaluator.Expand (core/rlwe/ring_packing.go:475-594) as one call: ct0 / ct1 hold nin << (logN - logGap) polys, the nin inputs first
+  void Expand(int lq, int lp, Poly& ct0, Poly& ct1, int nin, int logGap, const Poly& xinvpow, const std::vector<rh_galois_key>& keys) const {
+    check(rh_rlwe_expand(h_.get(), lq, lp, ct0.data(), ct1.data(), nin, logGap, xinvpow.data(), xinvpow.limbs(), keys.data(), (int)keys.size()));
   }
   void RotateAccumulateQP(int lq, int lp, uint64_t galEl, const Poly& ct0, const Poly& tmpQ0, const Poly& tmpQ1, const Poly& tmpP0, const Poly& tmpP1,
                           Poly& accQ0, Poly& accQ1, Poly& accP0, Poly& accP1, bool first) const {

@@ -84,6 +84,20 @@ inline RhStreamGrid rh_stream_begin(const rh_ring* r, unsigned rows) {   // ... 
   (void)hipGetLastError();
   return rh_stream_grid(r, rows);
 }
+// Blocks [p, p + words) as byte ranges: no written block may overlap a permuted (gathered) one, and every block moves as 16-byte pairs
+struct IsBlock { const void* p; size_t words; };
+inline bool is_overlap(const IsBlock& a, const IsBlock& b) {
+  const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
+  return a0 < b0 + b.words * 8 && b0 < a0 + a.words * 8;
+}
+inline int is_blocks(const IsBlock* written, int nw, const IsBlock* read, int nr, const char* who, const char* text) {
+  for (int i = 0; i < nw; ++i) {
+    if ((uintptr_t)written[i].p & 15) return rh_fail(RH_ERR_ARG, "%s: every block must be 16-byte aligned", who);
+    for (int j = 0; j < nr; ++j) if (is_overlap(written[i], read[j])) return rh_fail(RH_ERR_ARG, "%s: %s", who, text);
+  }
+  for (int j = 0; j < nr; ++j) if ((uintptr_t)read[j].p & 15) return rh_fail(RH_ERR_ARG, "%s: every block must be 16-byte aligned", who);
+  return RH_OK;
+}
 // Argument checks of the scheme-level entry points (bgv.hip, ckks.hip): kinds: a mask of 1 << RH_RING_* admitted (the refusal names the scheme
 // the mask belongs to); N a multiple of n_multiple
 int rh_scheme_args(const rh_ring* r, int level, int npoly, unsigned kinds, int n_multiple, const char* who);

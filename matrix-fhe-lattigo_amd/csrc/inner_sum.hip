@@ -30,21 +30,6 @@ static int is_gen(const rh_ring* r, uint64_t gen, const char* who, u32* out) {
   return RH_OK;
 }
 
-// Blocks [p, p + words) as byte ranges: no written block may overlap a permuted (gathered) one, and every block moves as 16-byte pairs
-struct IsBlock { const void* p; size_t words; };
-static bool is_overlap(const IsBlock& a, const IsBlock& b) {
-  const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
-  return a0 < b0 + b.words * 8 && b0 < a0 + a.words * 8;
-}
-static int is_blocks(const IsBlock* written, int nw, const IsBlock* read, int nr, const char* who, const char* text) {
-  for (int i = 0; i < nw; ++i) {
-    if ((uintptr_t)written[i].p & 15) return rh_fail(RH_ERR_ARG, "%s: every block must be 16-byte aligned", who);
-    for (int j = 0; j < nr; ++j) if (is_overlap(written[i], read[j])) return rh_fail(RH_ERR_ARG, "%s: %s", who, text);
-  }
-  for (int j = 0; j < nr; ++j) if ((uintptr_t)read[j].p & 15) return rh_fail(RH_ERR_ARG, "%s: every block must be 16-byte aligned", who);
-  return RH_OK;
-}
-
 // ringP.ModulusAtLevel[levelP] mod q_i in Montgomery form, per limb of Q (the scalar of MulScalarBigint, evaluator_automorphism.go:138-142)
 static RhPmodQ is_pmodq(const rh_ring* RQ, const rh_ring* RP, int LQ, int LP) {
   RhPmodQ pq; memset(&pq, 0, sizeof(pq));

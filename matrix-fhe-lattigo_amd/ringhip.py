@@ -138,6 +138,12 @@ def lib():
         "rh_rlwe_rotate_accumulate_qp": (i, [vp, i, i, C.c_uint64] + [vp] * 9 + [i, i]),
         "rh_rlwe_rotate_add_q": (i, [vp, i, C.c_uint64, vp, vp, vp, vp, i]),
         "rh_rlwe_partial_traces_sum": (i, [vp, i, i, vp, vp, i, i, i, C.POINTER(GaloisKeyEntry), i, vp, vp, i, i]),
+        "rh_rlwe_expand_step": (i, [vp, i, C.c_uint64, vp, vp, vp, vp, vp, i]),
+        "rh_rlwe_pack_combine": (i, [vp, i, vp, vp, i, vp, C.POINTER(C.c_int32), i, vp, vp, vp]),
+        "rh_rlwe_rotate_addsub_q": (i, [vp, i, C.c_uint64, vp, vp, vp, vp, i, vp, C.POINTER(C.c_int32), i]),
+        "rh_rlwe_ring_split": (i, [vp, i, vp, vp, vp, vp, vp, vp, i, i]),
+        "rh_rlwe_ring_merge": (i, [vp, i, vp, vp, vp, vp, vp, vp, vp, i, i]),
+        "rh_rlwe_expand": (i, [vp, i, i, vp, vp, i, i, vp, i, C.POINTER(GaloisKeyEntry), i]),
         "rh_bfv_create": (i, [C.POINTER(vp), vp, vp, C.c_uint64]), "rh_bfv_destroy": (None, [vp]), "rh_bfv_level_qmul": (i, [vp, i]),
         "rh_bfv_reserve": (i, [vp, i]), "rh_bfv_set_tuning": (i, [vp, C.c_char_p, C.c_long]), "rh_bfv_quantize_path": (i, [vp, i]),
         "rh_bfv_tensor_lazy": (i, [vp, i] + [vp] * 14 + [i, i]), "rh_bfv_quantize": (i, [vp, i, vp, vp, vp, i]),

@@ -14,10 +14,17 @@ The hoisted forms and the automorphism / relinearisation callers take NTT-domain
   PartialTracesSum       core/rlwe/inner_sum.go:152-291     Trace  :36-121     InnerFunction  :316-440     Replicate  :477-479
   GaloisElementsForInnerSum  :444-468     GaloisElementsForReplicate  :483-485     GaloisElementsForTrace  :125-146
 
-The sums of rotations take NTT- and coefficient-domain ciphertexts on standard rings, keys with levelP >= 1 and no power-of-two decomposition."""
+The sums of rotations take NTT- and coefficient-domain ciphertexts on standard rings, keys with levelP >= 1 and no power-of-two decomposition.
+
+  RingPackingEvaluator   core/rlwe/ring_packing.go: Expand :475-594, Pack :623-793, Split :193-258, Merge :396-464, Extract :70-189, Repack :260-392
+  GenXPow2NTT  :795-833     GaloisElementsForExpand / ForPack  core/rlwe/ring_packing_keys.go:143-180
+  SwitchCiphertextRingDegreeNTT  core/rlwe/element.go:250-287     SwitchCiphertextRingDegree  :293-312 (to the smaller degree)
+
+Ring packing takes standard rings and every key GadgetProduct takes; Expand and Pack take NTT- and coefficient-domain ciphertexts, Split and Merge
+NTT-domain ones."""
 import numpy as np
 
-from .ringhip import BasisExtender, DevicePoly, GaloisKeyEntry, RingHipError, Standard, _check, lib
+from .ringhip import BasisExtender, DevicePoly, GaloisKeyEntry, RingHipError, Standard, U64P, _check, lib
 from .schemes import Ciphertext
 
 GaloisGen = 5                                                          # ring.GaloisGen (ring/ring.go:17-19)
@@ -629,3 +636,637 @@ class Evaluator:
                     rq.INTT(opOut.Value[c], opOut.Value[c])
         finally:
             opOut.IsNTT = in_ntt
+
+
+# ---- core/rlwe/ring_packing.go, ring_packing_keys.go ----------------------------------------------------------------------------------------
+def GaloisElementsForExpand(N, logN):
+    """(ring_packing_keys.go:143-153): NthRoot / 2^(i+1) + 1 = N / 2^i + 1 for 0 <= i < logN"""
+    return [2 * int(N) // (2 << i) + 1 for i in range(logN)]
+
+
+def GaloisElementsForPack(N, logGap):
+    """(ring_packing_keys.go:156-180), standard rings: 5^(2^i) for 0 <= i < logGap, and 2N - 1 when logGap = logN"""
+    logN = int(N).bit_length() - 1
+    if logGap > logN or logGap < 0:
+        raise RingHipError("cannot GaloisElementsForPack: logGap > logN || logGap < 0")
+    out = [GaloisElement(N, 1 << i) for i in range(logGap)]
+    if logGap == logN:
+        out.append(2 * int(N) - 1)
+    return out
+
+
+def _view(p, first, count, ring=None):
+    """polys [first, first + count) of a batch as a batch of their own"""
+    ring = p.ring if ring is None else ring
+    return DevicePoly(ring, count, p.limbs, ptr=p.ptr + first * p.limbs * p.ring.N * 8, owner=p)
+
+
+def GenXPow2NTT(ring, logN, div):
+    """(ring_packing.go:795-833): [X^(+-2^i) for 0 <= i < logN] in the NTT domain and in Montgomery form, at the level of `ring`, built on the device with
+    the ring's own calls: MForm(1) at coefficient 1 (N - 1 for div) transformed, then squared logN - 1 times; for div the first entry is negated
+    (X^(N-1) = -X^-1).  Returns views of ONE block of logN polys (what rh_rlwe_expand takes as its table)."""
+    L, N = ring.level + 1, ring.N
+    first = np.zeros((1, L, N), dtype=np.uint64)
+    first[0, :, N - 1 if div else 1] = [(1 << 64) % int(q) for q in ring.moduli[:L]]
+    block = DevicePoly(ring, max(logN, 1), L)
+    x = [_view(block, i, 1) for i in range(logN)]
+    if logN:
+        _check(lib().rh_dev_upload(ring._h, block.ptr, first.ctypes.data_as(U64P), first.size))
+        ring.NTT(x[0], x[0])
+        for i in range(1, logN):
+            ring.MulCoeffsMontgomery(x[i - 1], x[i - 1], x[i])
+        if div:
+            ring.Neg(x[0], x[0])
+    return x
+
+
+def _log_n(ct):
+    return ct.Value[0].ring.N.bit_length() - 1
+
+
+def _small_ntt(ring, p):
+    # The reference transforms the rows of the small ring with ring.NTTStandard and the LARGE ring's table of roots (core/rlwe/element.go:273):
+    # entry i < N/2 of that table is psi_N^bitrev(i, logN) = (psi_N^2)^bitrev(i, logN - 1).  Both rings derive psi from the same smallest
+    # primitive root g of q, psi_N = g^((q-1)/2N), so psi_(N/2) = g^((q-1)/N) = psi_N^2: the small ring's own transform is that very transform.
+    ring.NTT(p, p)
+
+
+def SwitchCiphertextRingDegreeNTT(ctIn, ringQLargeDim, opOut):
+    """(core/rlwe/element.go:250-287): Y^(N/n) -> X^N or back, NTT domain in and out; ringQLargeDim: the ring of the larger degree (its level is not
+    read: the ciphertexts' is).  Down: an inverse transform at the large degree, every gap-th coefficient, the small ring's transform.  Up: every
+    NTT coefficient gap times (ring.MapSmallDimensionToLargerDimensionNTT, ring/operations.go:380-392).  ctIn is left alone."""
+    NIn, NOut = ctIn.Value[0].ring.N, opOut.Value[0].ring.N
+    level = min(ctIn.Level(), opOut.Level())
+    npoly = ctIn.Value[0].npoly
+    if ringQLargeDim.N != max(NIn, NOut) or NIn == NOut:
+        raise RingHipError("SwitchCiphertextRingDegreeNTT: ringQLargeDim must be the ring of the larger of two different degrees")
+    big = ringQLargeDim.AtLevel(level)
+    lg = abs(NIn.bit_length() - NOut.bit_length())
+    Evaluator._rows(level, *ctIn.Value, *opOut.Value)
+    if NIn > NOut:
+        buff = [DevicePoly(big, npoly, level + 1) for _ in (0, 1)]
+        for c in (0, 1):
+            big.INTT(ctIn.Value[c], buff[c])
+        _check(lib().rh_rlwe_ring_split(big._h, level, buff[0].ptr, buff[1].ptr, opOut.Value[0].ptr, opOut.Value[1].ptr, None, None, lg, npoly))
+        for c in (0, 1):
+            _small_ntt(opOut.Value[c].ring.AtLevel(level), opOut.Value[c])
+    else:
+        _check(lib().rh_rlwe_ring_merge(big._h, level, ctIn.Value[0].ptr, ctIn.Value[1].ptr, None, None, None, opOut.Value[0].ptr, opOut.Value[1].ptr, lg, npoly))
+    Evaluator._copy_metadata(ctIn, opOut)
+
+
+def SwitchCiphertextRingDegree(ctIn, opOut):
+    """(core/rlwe/element.go:293-312), to the SMALLER degree: opOut[w] = ctIn[w gap], whatever the domain flag says (the reference does not read it).
+    The other direction writes every gap-th word of opOut and leaves the rest: not built on the device path."""
+    NIn, NOut = ctIn.Value[0].ring.N, opOut.Value[0].ring.N
+    if NIn <= NOut:
+        raise RingHipError("SwitchCiphertextRingDegree: only the map to a smaller ring degree is built on the device path")
+    level = min(ctIn.Level(), opOut.Level())
+    Evaluator._rows(level, *ctIn.Value, *opOut.Value)
+    big = ctIn.Value[0].ring
+    _check(lib().rh_rlwe_ring_split(big._h, level, ctIn.Value[0].ptr, ctIn.Value[1].ptr, opOut.Value[0].ptr, opOut.Value[1].ptr, None, None,
+                                    NIn.bit_length() - NOut.bit_length(), ctIn.Value[0].npoly))
+    Evaluator._copy_metadata(ctIn, opOut)
+
+
+def getMinimumGap(keys):
+    """(ring_packing.go:835-868) -> (gap, logGap): the odd part and the 2-adic valuation of the smallest difference of a sorted list"""
+    gap, logGap = 0x7fffffffffffffff, 0
+    for a, b in zip(keys, keys[1:]):
+        if a > b:
+            raise RingHipError("getMinimumGap: invalid index list: element must be sorted from smallest to largest")
+        if a == b:
+            raise RingHipError("getMinimumGap: invalid index list: contains duplicated elements")
+        gap = min(gap, b - a)
+        if gap == 1:
+            break
+    while gap & 1 == 0:
+        logGap += 1
+        gap >>= 1
+    return gap, logGap
+
+
+MODE_A, MODE_B, MODE_AB = 0, 1, 2
+
+
+def pack_plan(N, keys, inputLogGap, zeroGarbageSlots):
+    """The loops of Pack (ring_packing.go:660-790) on the sorted index list alone -> (logStart, logEnd, levels, slot): `levels` holds, per level that
+    has work, (Galois element, position of X^(N/2^(i+1)) in XPow2NTT, [(mode, slot_a, slot_b)]), a slot being the position of a ciphertext in
+    `keys`; `slot` is where cts[0] ends (None: the reference returns a nil ciphertext).  MODE_AB: both halves of a pair are there, MODE_B: only the
+    upper one (it takes the lower one's place in the map, not in memory), MODE_A: only the lower one."""
+    N = int(N)
+    logN = N.bit_length() - 1
+    if len(keys) > 1:
+        gap, logGap = getMinimumGap(keys)
+    else:
+        gap, logGap = N, logN
+    logStart, logEnd = logN - inputLogGap, logN
+    if not zeroGarbageSlots and gap > 0:
+        logEnd -= logGap
+    if logStart >= logEnd:
+        raise RingHipError("gaps between ciphertexts is smaller than inputLogGap > N")
+    pos = {k: s for s, k in enumerate(keys)}
+    levels = []
+    for i in range(logStart, logEnd):
+        t = 1 << (logN - 1 - i)
+        entries = []
+        for jx in sorted({k % t for k in pos if 0 <= k < 2 * t}):
+            a, b = pos.get(jx), pos.get(jx + t)
+            if b is not None:
+                entries.append((MODE_AB, a, b) if a is not None else (MODE_B, b, b))
+                if a is None:
+                    pos[jx] = b
+                del pos[jx + t]
+            else:
+                entries.append((MODE_A, a, a))
+        if entries:
+            galEl = 2 * N - 1 if i == 0 else GaloisElement(N, 1 << (i - 1))
+            levels.append((galEl, logN - i - 1, entries))
+    return logStart, logEnd, levels, pos.get(0)
+
+
+class RingPackingEvaluator:
+    """rlwe.RingPackingEvaluator (core/rlwe/ring_packing.go) on device batches.  parameters: {logN: (ringQ, ringP)}, rings over the same moduli;
+    RingSwitchingKeys[logNIn][logNOut], RepackKeys[logN][galEl], ExtractKeys[logN][galEl]: GadgetCiphertexts (RingPackingEvaluationKey,
+    ring_packing_keys.go:14-32), every key setting GadgetProduct takes.  Standard rings, NTT-friendly chains.
+
+    Where the reference walks maps of single ciphertexts and issues one key switch per ciphertext, a level of Expand or Pack is here ONE launch
+    sequence over all the ciphertexts of the level: they share the Galois element."""
+
+    # Which fused kernels (csrc/ring_packing_kernels.hip.hpp) a call uses when it is not told (fused=None): the measured choice, a kernel being the
+    # default where the run shows it no slower than its composed form, alone and in the whole call (profiles/ring_packing.json, DESIGN.md section 6).
+    # fused=True / False selects all / none; the bits are the same.
+    FUSED_RING_PACKING = {"expand_step": True, "rotate_add": True, "pack_combine": True, "pack_finish": True}
+
+    def __init__(self, parameters, RingSwitchingKeys=None, RepackKeys=None, ExtractKeys=None):
+        self.parameters = dict(parameters)
+        if not self.parameters:
+            raise RingHipError("RingPackingEvaluator: no parameters")
+        self.RingSwitchingKeys, self.RepackKeys, self.ExtractKeys = RingSwitchingKeys, RepackKeys, ExtractKeys
+        levelQ = self.parameters[self.MinLogN()][0].L - 1                # (:35)
+        self.Evaluators, self.XPow2NTT, self.XInvPow2NTT = {}, {}, {}
+        for logN, (ringQ, ringP) in self.parameters.items():
+            if ringQ.N != 1 << logN:
+                raise RingHipError("RingPackingEvaluator: parameters[%d] has a ring of degree %d" % (logN, ringQ.N))
+            self.Evaluators[logN] = Evaluator(ringQ, ringP)
+            if ringQ.kind == Standard:
+                self.XPow2NTT[logN] = GenXPow2NTT(ringQ.AtLevel(levelQ), logN, False)
+                self.XInvPow2NTT[logN] = GenXPow2NTT(ringQ.AtLevel(levelQ), logN, True)
+        self._xrep = {}
+
+    def close(self):
+        for ev in self.Evaluators.values():
+            ev.close()
+
+    def MinLogN(self):
+        return min(self.parameters)
+
+    def MaxLogN(self):
+        return max(self.parameters)
+
+    def _use(self, fused):
+        return dict(self.FUSED_RING_PACKING) if fused is None else {k: bool(fused) for k in self.FUSED_RING_PACKING}
+
+    @staticmethod
+    def _key_switch(ev, level, c0, c1, evk, out0, out1):
+        """(c0 + KS(c1)_0, KS(c1)_1) (applyEvaluationKey, evaluator_evaluationkey.go:105-112) into out0 / out1, other buffers than c0 / c1"""
+        out = Ciphertext([out0, out1], is_ntt=True)
+        if evk.LevelP() >= 1:
+            ev.GadgetProductThenAdd(level, c1, evk, c0, None, out)
+        else:
+            ev.GadgetProduct(level, c1, evk, out)
+            ev.ringQ.AtLevel(level).vec_op("ADD", out0, c0, out0)
+
+    def _galois_keys(self, keyset, galEls):
+        """CheckAndGetGaloisKey for every element, before the first launch"""
+        for g in galEls:
+            if g not in keyset:
+                raise RingHipError("cannot apply Automorphism: GaloisKey[%d] is missing" % g)
+        return {g: keyset[g] for g in galEls}
+
+    def _replicated(self, x, cnt, rq, level):
+        """the composed forms multiply a batch by a table poly: the table `cnt` times, built once per (table, level, cnt)"""
+        key = (x.ptr, level, cnt)
+        rep = self._xrep.get(key)
+        if rep is None:
+            rep = self._xrep[key] = DevicePoly(rq, cnt, level + 1)
+            for p in range(cnt):
+                rq.CopyLvl(x, _view(rep, p, 1))
+        return rep
+
+    # ---- Expand (:475-594) ----------------------------------------------------------------------------------------------------------------
+    def _expand_checks(self, ct, logGap):
+        if ct.Degree() != 1:
+            raise RingHipError("ct.Degree() != 1")                                                      # (:477-479)
+        logN = _log_n(ct)
+        if logN not in self.parameters:
+            raise RingHipError("eval.Parameters[%d] is nil" % logN)                                     # (:485-486)
+        if self.ExtractKeys is None:
+            raise RingHipError("eval.ExtractKeys is nil")                                               # (:491-493)
+        if logN not in self.ExtractKeys:
+            raise RingHipError("eval.ExtractKeys[%d] is nil" % logN)                                    # (:496-497)
+        ev = self.Evaluators[logN]
+        if ev.ringQ.kind != Standard:                                                                   # (:509-511)
+            raise RingHipError("method is only supported for ring.Type = ring.Standard (X^{-2^{i}} does not exist in the sub-ring Z[X + X^{-1}])")
+        if not 0 <= logGap <= logN:
+            raise RingHipError("Expand: need 0 <= logGap <= logN")
+        N = 1 << logN
+        keys = self._galois_keys(self.ExtractKeys[logN], [N // (1 << i) + 1 for i in range(logN)])
+        return logN, ev, keys
+
+    def _expand_head(self, ct, logN, logGap, ev, scale=True):
+        """the output batch with the NTT-domain inputs, scaled by 2^-logN, in its first B polys (:513-528)"""
+        level, B = ct.Level(), ct.Value[0].npoly
+        ev._rows(level, *ct.Value)
+        rq = ev.ringQ.AtLevel(level)
+        out = Ciphertext([DevicePoly(rq, B << (logN - logGap), level + 1) for _ in (0, 1)], is_ntt=True)
+        Q = 1
+        for q in ev.ringQ.moduli[:level + 1]:
+            Q *= int(q)
+        NInv = pow(1 << logN, -1, Q)
+        for c in (0, 1):
+            head = _view(out.Value[c], 0, B)
+            (rq.CopyLvl if ct.IsNTT else rq.NTT)(ct.Value[c], head)
+            if scale:
+                rq.MulScalarBigint(head, NInv, head)
+        return out, rq, level, B
+
+    def _expand_done(self, ct, out, logN, logGap):
+        Evaluator._copy_metadata(ct, out)
+        out.IsNTT = True                       # (:517-521): the flag is set on entry, so the closing INTT loop (:586-592) never fires
+        out.LogDimensions = 0                  # (:515): Rows = Cols = 0; every output descends from cts[0]
+        return out, [m << logGap for m in range(1 << (logN - logGap))]
+
+    def Expand(self, ct, logGap, fused=None):
+        """(:475-594) on a batch of B ciphertexts -> (one batch of B N / 2^logGap ciphertexts, the index list): the ciphertext of coefficient
+        m 2^logGap of input b is poly m B + b, so the live set of every level is a contiguous prefix, which doubles with every level that has a
+        second output.  The outputs are in the NTT domain with IsNTT set, whatever the input's domain (:517-521, :586-592).  ct is left alone."""
+        logN, ev, keys = self._expand_checks(ct, logGap)
+        use = self._use(fused)
+        out, rq, level, B = self._expand_head(ct, logN, logGap, ev)
+        N, gap = 1 << logN, 1 << logGap
+        half = max(B, (B << (logN - logGap)) // 2)
+        tmp = [ev.buffer("rpTmp%d" % c, rq, half, level + 1) for c in (0, 1)]
+        xinv = self.XInvPow2NTT[logN]
+        for i in range(logN):
+            n = 1 << i
+            galEl = N // n + 1
+            cnt = (n // gap) * B if n >= gap else B
+            c = [_view(out.Value[k], 0, cnt) for k in (0, 1)]
+            t = [_view(tmp[k], 0, cnt) for k in (0, 1)]
+            self._key_switch(ev, level, c[0], c[1], keys[galEl], t[0], t[1])                               # Automorphism's product + Add (:555)
+            if n >= gap and use["expand_step"]:                                                           # (:555-575) in one launch
+                _check(lib().rh_rlwe_expand_step(rq._h, level, galEl, t[0].ptr, t[1].ptr, out.Value[0].ptr, out.Value[1].ptr, xinv[i].ptr, cnt))
+            elif n >= gap:
+                rot = ev.buffer("rpRot", rq, half, level + 1)
+                x = self._replicated(xinv[i], cnt, rq, level)
+                for k in (0, 1):
+                    r, hi = _view(rot, 0, cnt), _view(out.Value[k], cnt, cnt)
+                    rq.AutomorphismNTT(t[k], galEl, r)
+                    rq.Sub(c[k], r, hi)
+                    rq.Add(c[k], r, c[k])
+                    rq.MulCoeffsMontgomery(hi, x, hi)
+            elif use["rotate_add"]:                                                                       # (:580-581)
+                ev.RotateAddQ(level, galEl, Ciphertext(t, is_ntt=True), Ciphertext(c, is_ntt=True))
+            else:
+                rot = ev.buffer("rpRot", rq, half, level + 1)
+                for k in (0, 1):
+                    r = _view(rot, 0, cnt)
+                    rq.AutomorphismNTT(t[k], galEl, r)
+                    rq.Add(c[k], r, c[k])
+        return self._expand_done(ct, out, logN, logGap)
+
+    def ExpandC(self, ct, logGap):
+        """Expand as ONE call into the library (rh_rlwe_expand): what a compiled host uses.  Keys with more than one P modulus."""
+        logN, ev, keys = self._expand_checks(ct, logGap)
+        for g, evk in keys.items():
+            if evk.LevelP() < 1 or evk.BaseTwoDecomposition:
+                raise RingHipError("ExpandC: GaloisKey[%d] must have more than one P modulus and no power-of-two decomposition" % g)
+        out, rq, level, B = self._expand_head(ct, logN, logGap, ev, scale=False)       # the call scales by 2^-logN itself
+        table = (GaloisKeyEntry * max(len(keys), 1))()
+        for i, (g, evk) in enumerate(keys.items()):
+            table[i] = GaloisKeyEntry(g, evk.Q.ptr, evk.P.ptr, evk.digits)
+        x = self.XInvPow2NTT[logN]
+        _check(lib().rh_rlwe_expand(ev.be._h, level, ev.ringP.L - 1, out.Value[0].ptr, out.Value[1].ptr, B, logGap, x[0].ptr, x[0].limbs, table, len(keys)))
+        return self._expand_done(ct, out, logN, logGap)
+
+    # ---- Pack (:623-793) ------------------------------------------------------------------------------------------------------------------
+    def Pack(self, cts, keys, inputLogGap, zeroGarbageSlots, fused=None):
+        """(:623-793): cts is ONE batch, keys the sorted index of each of its ciphertexts.  A host plan (pack_plan) lists per level the Galois
+        element and the (mode, slot_a, slot_b) entries; it is uploaded once, and sparse and dense index sets take the same path: one key switch
+        per level over all its pairs.  Returns the ciphertext where index 0 ends, a view into cts (None where the reference returns nil).
+        cts is CONSUMED, as in the reference: transformed to the NTT domain on entry (:699-703), scaled by 2^-(logEnd - logStart) (:705-706),
+        and b X^k written over b (:726-727)."""
+        keys = [int(k) for k in keys]
+        if len(keys) == 0:
+            raise RingHipError("len(cts) = 0")                                                          # (:625-627)
+        if cts.Value[0].npoly != len(keys):
+            raise RingHipError("Pack: the batch holds %d ciphertexts for %d keys" % (cts.Value[0].npoly, len(keys)))
+        getMinimumGap(keys)
+        logN = _log_n(cts)
+        if logN not in self.parameters:
+            raise RingHipError("eval.Parameters[%d] is nil" % logN)                                     # (:635-636)
+        if self.RepackKeys is None:
+            raise RingHipError("eval.RepackKeys is nil")                                                # (:641-643)
+        if logN not in self.RepackKeys:
+            raise RingHipError("eval.RepackKeys[%d] is nil" % logN)                                     # (:646-647)
+        ev = self.Evaluators[logN]
+        if ev.ringQ.kind != Standard:                                                                   # (:656-658)
+            raise RingHipError("procedure is only supported for ring.Type = ring.Standard (X^{2^{i}} does not exist in the sub-ring Z[X + X^{-1}])")
+        N = 1 << logN
+        logStart, logEnd, levels, slot = pack_plan(N, keys, inputLogGap, zeroGarbageSlots)              # (:684-686)
+        if cts.Degree() != 1:
+            raise RingHipError("cts[%d].Degree() != 1" % keys[0])                                       # (:695-697)
+        gk = self._galois_keys(self.RepackKeys[logN], [g for g, _, _ in levels])
+        use = self._use(fused)
+        level, nslots = cts.Level(), len(keys)
+        ev._rows(level, *cts.Value)
+        rq = ev.ringQ.AtLevel(level)
+        Q = 1
+        for q in ev.ringQ.moduli[:level + 1]:
+            Q *= int(q)
+        NInv = pow(1 << (logEnd - logStart), -1, Q)
+        for c in (0, 1):
+            if not cts.IsNTT:
+                rq.NTT(cts.Value[c], cts.Value[c])
+            rq.MulScalarBigint(cts.Value[c], NInv, cts.Value[c])
+        cts.IsNTT = True
+        Kmax = max([len(e) for _, _, e in levels] + [1])
+        u = [ev.buffer("rpU%d" % c, rq, Kmax, level + 1) for c in (0, 1)]
+        tmp = [ev.buffer("rpTmp%d" % c, rq, Kmax, level + 1) for c in (0, 1)]
+        # the whole plan as one table of int32 triples, every level's part starting on an 8-byte word; uploaded once
+        import ctypes as C
+        host, offs = [], []
+        for _, _, entries in levels:
+            offs.append(len(host))
+            host += [v for e in entries for v in e]
+            host += [0] * (len(host) & 1)
+        arr = np.ascontiguousarray(np.array(host + [0, 0], dtype=np.int32))
+        dev = DevicePoly(rq, (arr.size // 2 + rq.N - 1) // rq.N, 1)
+        _check(lib().rh_dev_upload(rq._h, dev.ptr, arr.view(np.uint64).ctypes.data_as(U64P), arr.size // 2))
+        xpow = self.XPow2NTT[logN]
+        for (galEl, xi, entries), off in zip(levels, offs):
+            K = len(entries)
+            tdev = dev.ptr + 4 * off
+            thost = arr[off:off + 3 * K].ctypes.data_as(C.POINTER(C.c_int32))
+            uk, tk = [_view(u[c], 0, K) for c in (0, 1)], [_view(tmp[c], 0, K) for c in (0, 1)]
+            if use["pack_combine"]:                                                                     # (:726-745) over the level
+                _check(lib().rh_rlwe_pack_combine(rq._h, level, cts.Value[0].ptr, cts.Value[1].ptr, nslots, tdev, thost, K, xpow[xi].ptr, uk[0].ptr, uk[1].ptr))
+            else:
+                for k, (mode, sa, sb) in enumerate(entries):
+                    for c in (0, 1):
+                        a, b, uu = _view(cts.Value[c], sa, 1), _view(cts.Value[c], sb, 1), _view(u[c], k, 1)
+                        if mode == MODE_A:
+                            rq.CopyLvl(a, uu)
+                            continue
+                        rq.MulCoeffsMontgomery(b, xpow[xi], b)
+                        if mode == MODE_B:
+                            rq.CopyLvl(b, uu)
+                        else:
+                            rq.Sub(a, b, uu)
+                            rq.Add(a, b, a)
+            self._key_switch(ev, level, uk[0], uk[1], gk[galEl], tk[0], tk[1])                           # the level's ONE key switch (:758-763, :781)
+            if use["pack_finish"]:                                                                      # (:768-769, :786-787) over the level
+                _check(lib().rh_rlwe_rotate_addsub_q(rq._h, level, galEl, tk[0].ptr, tk[1].ptr, cts.Value[0].ptr, cts.Value[1].ptr, nslots, tdev, thost, K))
+            else:
+                for c in (0, 1):
+                    rq.AutomorphismNTT(tk[c], galEl, uk[c])
+                    for k, (mode, sa, sb) in enumerate(entries):
+                        dst, r = _view(cts.Value[c], sb if mode == MODE_B else sa, 1), _view(u[c], k, 1)
+                        (rq.Sub if mode == MODE_B else rq.Add)(dst, r, dst)
+        rq.sync()                                                        # the plan's device copy is released with this frame
+        if slot is None:
+            return None
+        res = Ciphertext([_view(cts.Value[c], slot, 1) for c in (0, 1)], is_ntt=True)
+        Evaluator._copy_metadata(cts, res)
+        return res
+
+    # ---- Split (:193-258), Merge (:396-464) -----------------------------------------------------------------------------------------------
+    def _two_degrees(self):
+        if self.MinLogN() == self.MaxLogN():
+            raise RingHipError("method is not supported when eval.MinLogN() == eval.MaxLogN()")         # (:195-197, :251-253, :398-400, :450-452)
+
+    def _switching_key(self, a, b):
+        try:
+            return self.RingSwitchingKeys[a][b]
+        except (KeyError, TypeError):
+            raise RingHipError("eval.RingSwitchingKeys[%d][%d] is nil" % (a, b))
+
+    def Split(self, ctN, ctEvenNHalf, ctOddNHalf):
+        """(:193-246): ctN[X] = ctEvenNHalf[Y] + X ctOddNHalf[Y], Y = X^2: ONE key switch to the small secret, one inverse transform pair at N, the
+        split kernel for both halves, the small ring's transform.  ctOddNHalf may be None.  The metadata is ctN's with LogDimensions one less
+        (:227-229, :238-242).  NTT domain only: the device ApplyEvaluationKey takes no coefficient-domain ciphertext."""
+        self._two_degrees()
+        LogN = _log_n(ctN)
+        if LogN <= self.MinLogN():
+            raise RingHipError("ctN.Log() must be greater than eval.MinLogN()")                         # (:199-201)
+        if ctEvenNHalf is None:
+            raise RingHipError("ctEvenNHalf cannot be nil")                                             # (:203-205)
+        if _log_n(ctEvenNHalf) != LogN - 1:
+            raise RingHipError("ctEvenNHalf.LogN() must be equal to ctN.LogN()-1")                      # (:207-209)
+        if ctOddNHalf is not None and _log_n(ctOddNHalf) != LogN - 1:
+            raise RingHipError("ctOddNHalf.LogN() must be equal to ctN.LogN()-1")                       # (:234-236)
+        if not ctN.IsNTT:
+            raise RingHipError("Split: coefficient-domain ciphertexts are not supported by the device path")
+        ev, evk = self.Evaluators[LogN], self._switching_key(LogN, LogN - 1)
+        level, npoly = ctN.Level(), ctN.Value[0].npoly
+        outs = [ctEvenNHalf] + ([ctOddNHalf] if ctOddNHalf is not None else [])
+        ev._rows(level, *ctN.Value)
+        for o in outs:
+            ev._rows(level, *o.Value)
+            if o.Value[0].npoly != npoly:
+                raise RingHipError("Split: the halves hold another number of ciphertexts than ctN")
+        rq = ev.ringQ.AtLevel(level)
+        tmp = [ev.buffer("rpSw%d" % c, rq, npoly, level + 1) for c in (0, 1)]
+        self._key_switch(ev, level, ctN.Value[0], ctN.Value[1], evk, tmp[0], tmp[1])                   # SkN -> SkNHalf (:219)
+        for c in (0, 1):
+            rq.INTT(tmp[c], tmp[c])
+        odd = ctOddNHalf.Value if ctOddNHalf is not None else (None, None)
+        _check(lib().rh_rlwe_ring_split(rq._h, level, tmp[0].ptr, tmp[1].ptr, ctEvenNHalf.Value[0].ptr, ctEvenNHalf.Value[1].ptr,
+                                        odd[0].ptr if odd[0] is not None else None, odd[1].ptr if odd[1] is not None else None, 1, npoly))
+        for o in outs:
+            for c in (0, 1):
+                _small_ntt(o.Value[c].ring.AtLevel(level), o.Value[c])
+            Evaluator._copy_metadata(ctN, o)
+            if hasattr(o, "LogDimensions"):
+                o.LogDimensions -= 1
+
+    def _new(self, logN, level, npoly):
+        rq = self.parameters[logN][0].AtLevel(level)
+        return Ciphertext([DevicePoly(rq, npoly, level + 1) for _ in (0, 1)], is_ntt=True)
+
+    def SplitNew(self, ctN):
+        """(:250-258)"""
+        self._two_degrees()
+        LogN = _log_n(ctN)
+        if LogN - 1 not in self.parameters:
+            raise RingHipError("ctN.Log() must be greater than eval.MinLogN()")
+        even, odd = self._new(LogN - 1, ctN.Level(), ctN.Value[0].npoly), self._new(LogN - 1, ctN.Level(), ctN.Value[0].npoly)
+        self.Split(ctN, even, odd)
+        return even, odd
+
+    def Merge(self, ctEvenNHalf, ctOddNHalf, ctN):
+        """(:396-444): ctN[X] = ctEvenNHalf[Y] + X ctOddNHalf[Y]: the merge kernel (replication, and the product with X and the sum when there is an
+        odd half), then ONE key switch to the large secret.  The metadata is ctEvenNHalf's with LogDimensions one more (:428, :442).  NTT domain only."""
+        self._two_degrees()
+        if ctEvenNHalf is None:
+            raise RingHipError("ctEvenNHalf cannot be nil")                                             # (:402-404)
+        if _log_n(ctEvenNHalf) >= self.MaxLogN():
+            raise RingHipError("ctEvenNHalf.LogN() must be smaller than eval.MaxLogN()")                # (:406-408)
+        if _log_n(ctN) != _log_n(ctEvenNHalf) + 1:
+            raise RingHipError("ctN.LogN() must be equal to ctEvenNHalf.LogN()+1")                      # (:410-412)
+        if ctOddNHalf is not None and _log_n(ctEvenNHalf) != _log_n(ctOddNHalf):
+            raise RingHipError("ctEvenNHalf.LogN() and ctOddNHalf.LogN() must be equal")                # (:414-418)
+        if not ctEvenNHalf.IsNTT or (ctOddNHalf is not None and not ctOddNHalf.IsNTT):
+            raise RingHipError("Merge: coefficient-domain ciphertexts are not supported by the device path")
+        LogN = _log_n(ctN)
+        ev, evk = self.Evaluators[LogN], self._switching_key(LogN - 1, LogN)
+        level, npoly = ctN.Level(), ctN.Value[0].npoly
+        ev._rows(level, *ctN.Value, *ctEvenNHalf.Value, *(ctOddNHalf.Value if ctOddNHalf is not None else ()))
+        if ctEvenNHalf.Value[0].npoly != npoly or (ctOddNHalf is not None and ctOddNHalf.Value[0].npoly != npoly):
+            raise RingHipError("Merge: the halves hold another number of ciphertexts than ctN")
+        rq = ev.ringQ.AtLevel(level)
+        tmp = [ev.buffer("rpSw%d" % c, rq, npoly, level + 1) for c in (0, 1)]
+        odd = ctOddNHalf.Value if ctOddNHalf is not None else (None, None)
+        _check(lib().rh_rlwe_ring_merge(rq._h, level, ctEvenNHalf.Value[0].ptr, ctEvenNHalf.Value[1].ptr, odd[0].ptr if odd[0] is not None else None,
+                                        odd[1].ptr if odd[1] is not None else None, self.XPow2NTT[LogN][0].ptr, tmp[0].ptr, tmp[1].ptr, 1, npoly))
+        self._key_switch(ev, level, tmp[0], tmp[1], evk, ctN.Value[0], ctN.Value[1])                   # SkNHalf -> SkN (:438)
+        Evaluator._copy_metadata(ctEvenNHalf, ctN)
+        ctN.IsNTT = True
+        if hasattr(ctN, "LogDimensions"):
+            ctN.LogDimensions += 1
+
+    def MergeNew(self, ctEvenNHalf, ctOddNHalf):
+        """(:448-464)"""
+        self._two_degrees()
+        if ctEvenNHalf is None:
+            raise RingHipError("ctEvenNHalf cannot be nil")
+        if _log_n(ctEvenNHalf) >= self.MaxLogN():
+            raise RingHipError("ctEvenNHalf.LogN() must be smaller than eval.MaxLogN()")
+        ctN = self._new(_log_n(ctEvenNHalf) + 1, ctEvenNHalf.Level(), ctEvenNHalf.Value[0].npoly)
+        self.Merge(ctEvenNHalf, ctOddNHalf, ctN)
+        return ctN
+
+    # ---- Extract (:70-189), Repack (:260-392) ---------------------------------------------------------------------------------------------
+    def Extract(self, ct, idx):
+        return self._extract(ct, idx, False)
+
+    def ExtractNaive(self, ct, idx):
+        return self._extract(ct, idx, True)
+
+    def _extract(self, ct, idx, naive):
+        """extract (:90-189) on ONE ciphertext -> {index: ciphertext of degree 2^MinLogN}, views into one batch per bucket.  With one index
+        getMinimumGap returns logGap = 0 (:101), so everything is expanded."""
+        if ct.Value[0].npoly != 1:
+            raise RingHipError("Extract: one ciphertext at a time (Expand takes batches)")
+        logNMax, logNMin, level = _log_n(ct), self.MinLogN(), ct.Level()
+        logNFactor = logNMax - logNMin
+        NFactor = 1 << logNFactor
+        keys = sorted(int(i) for i in idx)
+        _, logGap = getMinimumGap(keys)
+        tmpCts = {0: ct}
+        for i in range(logNFactor):
+            t = 1 << i
+            logGap = max(0, logGap - 1)
+            for j in range(t):
+                if tmpCts.get(j) is not None:
+                    tmpCts[j], tmpCts[j + t] = self.SplitNew(tmpCts[j])
+        buckets = {}
+        for i in keys:
+            buckets.setdefault(i & (NFactor - 1), []).append(i // NFactor)
+        out = {}
+        for i, want in buckets.items():
+            src = tmpCts[i]
+            if naive:
+                rq = self.parameters[logNMin][0].AtLevel(level)
+                xinv = self.XInvPow2NTT[logNMin]
+                batch = self._new(logNMin, level, len(want))
+                for s, j in enumerate(want):
+                    for c in (0, 1):
+                        dst = _view(batch.Value[c], s, 1)
+                        rq.CopyLvl(src.Value[c], dst)
+                        for b in range(logNMin):
+                            if (j >> b) & 1:
+                                rq.MulCoeffsMontgomery(dst, xinv[b], dst)                              # (:162-170)
+                where = {j: s for s, j in enumerate(want)}
+            else:
+                batch, index = self.Expand(src, logGap)
+                where = {j: s for s, j in enumerate(index)}
+            for j in want:
+                if j not in where:
+                    raise RingHipError("invalid ciphertexts map: index i+j*(NFactor*gap)=%d is nil" % (i + j * (NFactor << logGap)))
+                one = Ciphertext([_view(batch.Value[c], where[j], 1) for c in (0, 1)], is_ntt=True)
+                Evaluator._copy_metadata(src if naive else batch, one)
+                one.IsNTT = True
+                out[i + j * NFactor] = one
+        return out
+
+    def Repack(self, cts):
+        return self._repack(cts, False)
+
+    def RepackNaive(self, cts):
+        return self._repack(cts, True)
+
+    def _repack(self, cts, naive):
+        """repack (:291-392) on {index: ciphertext}: the ciphertexts of a bucket are gathered into one batch and packed by ONE Pack; the buckets are
+        merged in the reference's tree.  Its merge loop tests ctsLargeN[j+1], not ctsLargeN[j+t] (:377): a node without an even half therefore
+        fails with Merge's "ctEvenNHalf cannot be nil" or, when [j+1] is empty too, is dropped -- kept."""
+        keys = sorted(cts)
+        first = cts[keys[0]]
+        logNMin, logNMax, level = _log_n(first), self.MaxLogN(), first.Level()
+        logNFactor = logNMax - logNMin
+        NFactor = 1 << logNFactor
+        rq = self.parameters[logNMin][0].AtLevel(level)
+        small = [dict() for _ in range(NFactor)]
+        for i in keys:
+            small[i & (NFactor - 1)][i // NFactor] = cts[i]
+        large = {}
+        for i in range(NFactor):
+            ks = sorted(small[i])
+            if not ks:
+                if naive:
+                    large[i] = None
+                continue
+            batch = self._new(logNMin, level, len(ks))
+            for s, k in enumerate(ks):
+                for c in (0, 1):
+                    rq.CopyLvl(small[i][k].Value[c], _view(batch.Value[c], s, 1))
+            Evaluator._copy_metadata(small[i][ks[0]], batch)
+            batch.IsNTT = small[i][ks[0]].IsNTT
+            if naive:
+                large[i] = self._pack_naive(batch, ks, logNMin, rq)
+            else:
+                large[i] = self.Pack(batch, ks, logNMin, True)
+        for i in range(logNFactor - 1, -1, -1):
+            t = 1 << i
+            for j in range(t):
+                if large.get(j) is not None or large.get(j + 1) is not None:
+                    large[j] = self.MergeNew(large.get(j), large.get(j + t))
+                    large[j + t] = None
+        return large.get(0)
+
+    def _pack_naive(self, batch, keys, logN, rq):
+        """the naive branch of repack (:322-360): b X^(N/2^(l+1)) added to a, no key switch, no zeroing"""
+        xpow = self.XPow2NTT[logN]
+        pos = {k: s for s, k in enumerate(keys)}
+        for l in range(logN):
+            t = 1 << (logN - 1 - l)
+            for jx in range(t):
+                a, b = pos.get(jx), pos.get(jx + t)
+                if b is None:
+                    continue
+                for c in (0, 1):
+                    vb = _view(batch.Value[c], b, 1)
+                    rq.MulCoeffsMontgomery(vb, xpow[len(xpow) - l - 1], vb)
+                    if a is not None:
+                        va = _view(batch.Value[c], a, 1)
+                        rq.Add(va, vb, va)
+                if a is None:
+                    pos[jx] = b
+                del pos[jx + t]
+        slot = pos.get(0)
+        if slot is None:
+            return None
+        res = Ciphertext([_view(batch.Value[c], slot, 1) for c in (0, 1)], is_ntt=True)
+        Evaluator._copy_metadata(batch, res)
+        return res

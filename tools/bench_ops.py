@@ -10,7 +10,8 @@ against its algorithmic bytes, and writes profiles/ckks_encoder.json; `bench_ops
 the lift and Q to T alone, one kernel each against the reference's sequence of ring calls, at N = 2^16, 24 limbs, 64 vectors, T = 65537 for
 gap 2 and T = 786433 for gap 1) and writes profiles/bgv_encoder.json; `bench_ops.py inner_sum [OUT.json]` the sums of rotations
 (PartialTracesSum for n = 7 and n = 8 at the config 5 ring, fused against composed, and each of the two kernels of csrc/inner_sum.hip against the
-passes it replaces) and writes profiles/inner_sum.json."""
+passes it replaces) and writes profiles/inner_sum.json; `bench_ops.py ring_packing [OUT.json]` the ring-packing evaluator (Expand, Pack, Split, Merge at the
+config 5 ring and at N = 2^12, fused against composed, batched against per-ciphertext) and writes profiles/ring_packing.json."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -485,6 +486,193 @@ def inner_sum_group(out_path):
     print(json.dumps(res, indent=1))
     ev.close()
     rq.close(); rp.close()
+
+
+def ring_packing_group(out_path):
+    """rlwe.RingPackingEvaluator at the config 5 ring of ckks_group (N = 2^16, 24 limbs of Qi60, 6 of Pi60) and at a small ring (N = 2^12, 4 | 2 limbs):
+    Expand to 64 outputs (logGap = 10) and the small ring's full expansion (4096 outputs), Pack of the same counts, Split and Merge of 64 ciphertexts;
+    fused=True (csrc/ring_packing.hip) against fused=False, the same sequence composed from AutomorphismNTT and vec_op passes; each kernel alone
+    against the passes it replaces; and the batched level sequence against one launch sequence per ciphertext, what a port of the reference's loop
+    would issue.  Alternating windows as in inner_sum_group; `fused_default` is the rule RingPackingEvaluator.FUSED_RING_PACKING follows.  The keys
+    are random words (one block serves every Galois element): the timing does not read them."""
+    import statistics
+    from bench import csrc_tree_hash
+    stat = lambda v: {"ms_median": round(statistics.median(v), 4), "ms_min": round(min(v), 4), "ms_max": round(max(v), 4)}
+
+    def compare(name, fn, rounds, reps, extra=None, labels=("fused", "composed")):
+        tf, tc = [], []
+        for _ in range(rounds):
+            tf.append(timed(lambda: fn(True), reps=reps, warm=1)); tc.append(timed(lambda: fn(False), reps=reps, warm=1))
+        f, c = stat(tf), stat(tc)
+        spread = round(c["ms_max"] - c["ms_min"], 4)
+        e = {"op": name, labels[0]: f, labels[1]: c, "ratio_%s_over_%s" % (labels[1], labels[0]): round(c["ms_median"] / f["ms_median"], 3),
+             "%s_run_to_run_spread_ms" % labels[1]: spread, "windows": rounds, "calls_per_window": reps}
+        if labels[0] == "fused":
+            e["fused_default"] = bool(f["ms_median"] <= c["ms_median"] + spread)
+        e.update(extra or {})
+        print(json.dumps(e), flush=True)
+        return e
+
+    def setup(logN, LQ, LP, two_degrees):
+        N = 1 << logN
+        Q, P = QI60[:LQ], PI60[:LP]
+        rings = {}
+        for lg in ((logN - 1, logN) if two_degrees else (logN,)):
+            rq, rp = rh.Ring(1 << lg, Q), rh.Ring(1 << lg, P)
+            rq.set_stream(stream.cuda_stream); rp.set_stream(stream.cuda_stream)
+            rings[lg] = (rq, rp)
+        rq, rp = rings[logN]
+        digits = (LQ + LP - 1) // LP
+        k = rh.rlwe.GadgetCiphertext.__new__(rh.rlwe.GadgetCiphertext)
+        k.digits, k.levelQ, k.levelP, k.BaseTwoDecomposition, k.digits_per_limb = digits, LQ - 1, LP - 1, 0, None
+        k.Q, k.P = rh.DevicePoly.from_torch(rq, rand_block(2 * digits, Q, N)), rh.DevicePoly.from_torch(rp, rand_block(2 * digits, P, N))
+        gal = {g: k for g in set(rh.rlwe.GaloisElementsForExpand(N, logN) + rh.rlwe.GaloisElementsForPack(N, logN))}
+        sw = {logN: {logN - 1: k}, logN - 1: {logN: k}} if two_degrees else None
+        ev = rh.rlwe.RingPackingEvaluator(rings, RingSwitchingKeys=sw, RepackKeys={logN: gal}, ExtractKeys={logN: gal})
+        mk = lambda lg, B: rh.Ciphertext([rh.DevicePoly.from_torch(rings[lg][0], rand_block(B, Q, 1 << lg)) for _ in (0, 1)], is_ntt=True)
+        return N, Q, rings, ev, mk, k
+
+    def expand_per_ciphertext(ev, ct, logGap):
+        """the reference's loop (ring_packing.go:549-583) with the fused kernel: one key switch and one launch per ciphertext of every level.  Timing only:
+        a level's second outputs land next to their sources, not where Expand puts them."""
+        logN, e, keys = ev._expand_checks(ct, logGap)
+        out, rq, level, B = ev._expand_head(ct, logN, logGap, e)
+        N, gap = 1 << logN, 1 << logGap
+        tmp = [e.buffer("rpOne%d" % c, rq, 1, level + 1) for c in (0, 1)]
+        L = rh.lib()
+        for i in range(logN):
+            n = 1 << i
+            g = N // n + 1
+            for p in range(max(n // gap, 1)):
+                c = [rh.rlwe._view(out.Value[k], 2 * p if n >= gap else p, 1) for k in (0, 1)]
+                ev._key_switch(e, level, c[0], c[1], keys[g], tmp[0], tmp[1])
+                if n >= gap:
+                    rh.rlwe._check(L.rh_rlwe_expand_step(rq._h, level, g, tmp[0].ptr, tmp[1].ptr, c[0].ptr, c[1].ptr, ev.XInvPow2NTT[logN][i].ptr, 1))
+                else:
+                    e.RotateAddQ(level, g, rh.Ciphertext(tmp, is_ntt=True), rh.Ciphertext(c, is_ntt=True))
+        return out
+
+    results, shapes = [], {}
+    # ---- the config 5 ring ----
+    logN, LQ, LP, nout = 16, 24, 6, 64
+    N, Q, rings, ev, mk, key = setup(logN, LQ, LP, True)
+    shapes["config5"] = {"N": N, "limbs_Q": LQ, "limbs_P": LP, "outputs": nout, "logGap": logN - 6}
+    rq = rings[logN][0]
+    level = LQ - 1
+    ct = mk(logN, 1)
+    res = [[v.numpy() for v in ev.Expand(ct, logN - 6, fused=f)[0].Value] for f in (True, False)]      # same bits first, at the timed shape
+    assert all(np.array_equal(x, y) for x, y in zip(*res)), "fused and composed Expand differ"
+    del res
+    results.append(compare("Expand to 64 outputs, config 5", lambda f: ev.Expand(ct, logN - 6, fused=f), 5, 4))
+    results.append(compare("Expand to 64 outputs, config 5: batched levels against one launch sequence per ciphertext",
+                           lambda f: ev.Expand(ct, logN - 6, fused=True) if f else expand_per_ciphertext(ev, ct, logN - 6), 5, 4, labels=("batched", "per_ciphertext")))
+    keys64 = [m << (logN - 6) for m in range(nout)]
+    batch = mk(logN, nout)
+    results.append(compare("Pack of 64 ciphertexts, config 5", lambda f: ev.Pack(batch, keys64, logN, True, fused=f), 5, 3))
+    # the kernels alone, 32 ciphertexts (the last level of the expansion): row moves per component 5 against 13, 5 + 3 against 14
+    cnt = 32
+    e = ev.Evaluators[logN]
+    big, tmp, rot = mk(logN, 2 * cnt), mk(logN, cnt), mk(logN, cnt)
+    xi, xp = ev.XInvPow2NTT[logN][15], ev.XPow2NTT[logN][0]
+    g = N // (1 << 15) + 1
+    L = rh.lib()
+    lo = [rh.rlwe._view(big.Value[c], 0, cnt) for c in (0, 1)]
+    hi = [rh.rlwe._view(big.Value[c], cnt, cnt) for c in (0, 1)]
+    xrep = ev._replicated(xi, cnt, rq.AtLevel(level), level)
+
+    def step(f):
+        if f:
+            rh.rlwe._check(L.rh_rlwe_expand_step(rq._h, level, g, tmp.Value[0].ptr, tmp.Value[1].ptr, big.Value[0].ptr, big.Value[1].ptr, xi.ptr, cnt))
+            return
+        for c in (0, 1):
+            rq.AutomorphismNTT(tmp.Value[c], g, rot.Value[c]); rq.Sub(lo[c], rot.Value[c], hi[c]); rq.Add(lo[c], rot.Value[c], lo[c])
+            rq.MulCoeffsMontgomery(hi[c], xrep, hi[c])
+    row = 8.0 * N * cnt * LQ * 2
+    ent = compare("expand step, the kernel alone (32 ciphertexts)", step, 7, 10, {"row_moves_fused": 5, "row_moves_composed": 11,
+                  "note": "composed: AutomorphismNTT 2, Sub 3, Add 3, MulCoeffsMontgomery 3 row moves = 11; the reference's own sequence adds the CopyNew (2): 13"})
+    ent["fused"]["algorithmic_GBps"] = round(5 * row / (ent["fused"]["ms_median"] * 1e-3) / 1e9, 1)
+    ent["fused"]["frac_of_8TBps"] = round(ent["fused"]["algorithmic_GBps"] / PEAK, 3)
+    results.append(ent)
+    entries = [(rh.rlwe.MODE_AB, p, cnt + p) for p in range(cnt)]
+    arr = np.array([v for en in entries for v in en] + [0, 0], dtype=np.int32)
+    dt = rh.DevicePoly(rq, 1, 1)
+    rh.rlwe._check(L.rh_dev_upload(rq._h, dt.ptr, arr.view(np.uint64).ctypes.data_as(rh.ringhip.U64P), arr.size // 2))
+    import ctypes as C
+    th = arr.ctypes.data_as(C.POINTER(C.c_int32))
+    u = mk(logN, cnt)
+    xprep = ev._replicated(xp, cnt, rq.AtLevel(level), level)
+
+    def combine(f):
+        if f:
+            rh.rlwe._check(L.rh_rlwe_pack_combine(rq._h, level, big.Value[0].ptr, big.Value[1].ptr, 2 * cnt, dt.ptr, th, cnt, xp.ptr, u.Value[0].ptr, u.Value[1].ptr))
+            return
+        for c in (0, 1):
+            rq.MulCoeffsMontgomery(hi[c], xprep, hi[c]); rq.Sub(lo[c], hi[c], u.Value[c]); rq.Add(lo[c], hi[c], lo[c])
+
+    def finish(f):
+        if f:
+            rh.rlwe._check(L.rh_rlwe_rotate_addsub_q(rq._h, level, g, tmp.Value[0].ptr, tmp.Value[1].ptr, big.Value[0].ptr, big.Value[1].ptr, 2 * cnt, dt.ptr, th, cnt))
+            return
+        for c in (0, 1):
+            rq.AutomorphismNTT(tmp.Value[c], g, rot.Value[c]); rq.Add(lo[c], rot.Value[c], lo[c])
+    results.append(compare("pack combine, the kernel alone (32 pairs, batched passes)", combine, 7, 10, {"row_moves_fused": 5, "row_moves_composed": 9}))
+    results.append(compare("pack finish, the kernel alone (32 ciphertexts)", finish, 7, 10, {"row_moves_fused": 3, "row_moves_composed": 5}))
+    # Split and Merge of 64 ciphertexts
+    B = 64
+    ctN, even, odd = mk(logN, B), mk(logN - 1, B), mk(logN - 1, B)
+    results.append({"op": "Split of 64 ciphertexts, config 5", "ms": stat([timed(lambda: ev.Split(ctN, even, odd), reps=5, warm=1) for _ in range(5)])})
+    results.append({"op": "Merge of 64 ciphertexts, config 5", "ms": stat([timed(lambda: ev.Merge(even, odd, ctN), reps=5, warm=1) for _ in range(5)])})
+    print(json.dumps(results[-2:]), flush=True)
+    t0, t1 = mk(logN, B), mk(logN, B)
+    xinv0, x0 = ev._replicated(ev.XInvPow2NTT[logN][0], B, rq.AtLevel(level), level), ev._replicated(xp, B, rq.AtLevel(level), level)
+
+    def split_kernel(f):
+        if f:
+            rh.rlwe._check(L.rh_rlwe_ring_split(rq._h, level, t0.Value[0].ptr, t0.Value[1].ptr, even.Value[0].ptr, even.Value[1].ptr, odd.Value[0].ptr, odd.Value[1].ptr, 1, B))
+            return
+        # the reference's route to the odd half (:239-241): times X^-1, a second inverse transform; then both strided copies
+        for c in (0, 1):
+            rq.MulCoeffsMontgomery(t0.Value[c], xinv0, t1.Value[c]); rq.INTT(t1.Value[c], t1.Value[c])
+        rh.rlwe._check(L.rh_rlwe_ring_split(rq._h, level, t0.Value[0].ptr, t0.Value[1].ptr, even.Value[0].ptr, even.Value[1].ptr, None, None, 1, B))
+        rh.rlwe._check(L.rh_rlwe_ring_split(rq._h, level, t1.Value[0].ptr, t1.Value[1].ptr, odd.Value[0].ptr, odd.Value[1].ptr, None, None, 1, B))
+
+    def merge_kernel(f):
+        o = odd.Value if f else (None, None)
+        rh.rlwe._check(L.rh_rlwe_ring_merge(rq._h, level, even.Value[0].ptr, even.Value[1].ptr, o[0].ptr if f else None, o[1].ptr if f else None, xp.ptr if f else None,
+                                            t0.Value[0].ptr, t0.Value[1].ptr, 1, B))
+        if not f:                                     # (:429-434): two replications, MulCoeffsMontgomeryThenAdd
+            rh.rlwe._check(L.rh_rlwe_ring_merge(rq._h, level, odd.Value[0].ptr, odd.Value[1].ptr, None, None, None, t1.Value[0].ptr, t1.Value[1].ptr, 1, B))
+            for c in (0, 1):
+                rq.MulCoeffsMontgomeryThenAdd(t1.Value[c], x0, t0.Value[c])
+    results.append(compare("ring split, the kernel alone (64 ciphertexts) against X^-1, a second INTT and two strided copies", split_kernel, 5, 5))
+    results.append(compare("ring merge, the kernel alone (64 ciphertexts) against two replications and MulCoeffsMontgomeryThenAdd", merge_kernel, 5, 5))
+    del big, tmp, rot, u, batch, ctN, even, odd, t0, t1, xrep, xprep, xinv0, x0, lo, hi
+    ev._xrep.clear()
+    ev.close()
+    # ---- a small ring, full expansion ----
+    logN, LQ, LP = 12, 4, 2
+    N, Q, rings, ev, mk, key = setup(logN, LQ, LP, False)
+    shapes["small"] = {"N": N, "limbs_Q": LQ, "limbs_P": LP, "outputs": N, "logGap": 0}
+    ct = mk(logN, 1)
+    results.append(compare("Expand, full expansion to 4096 outputs, N = 2^12", lambda f: ev.Expand(ct, 0, fused=f), 5, 3))
+    results.append(compare("Expand, full expansion, N = 2^12: batched levels against one launch sequence per ciphertext",
+                           lambda f: ev.Expand(ct, 0, fused=True) if f else expand_per_ciphertext(ev, ct, 0), 3, 1, labels=("batched", "per_ciphertext")))
+    batch = mk(logN, N)
+    results.append(compare("Pack of 4096 ciphertexts, N = 2^12", lambda f: ev.Pack(batch, list(range(N)), logN, True, fused=f), 3, 1,
+                           {"note": "composed: one launch per ciphertext and pass around the level's one key switch, as the reference's loop issues them"}))
+    ev.close()
+    res = {"device": torch.cuda.get_device_name(0), "csrc_tree": csrc_tree_hash(), "shapes": shapes,
+           "method": "alternating windows (counts per entry), device events, 1 warm-up call per window; clocks left to the driver's default governor",
+           "results": results}
+    with open(out_path, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(res, indent=1))
+
+
+if sys.argv[1:2] == ["ring_packing"]:
+    ring_packing_group(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "ring_packing.json"))
+    sys.exit(0)
 
 
 if sys.argv[1:2] == ["inner_sum"]:
