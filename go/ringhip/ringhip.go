@@ -343,6 +343,23 @@ func (d *DeviceRing) TensorDegree1(a0, a1, b0, b1, c0, c1, c2 *DevPoly) {
 	d.must(C.rh_ring_tensor_degree1(d.h, a0.ptr, a1.ptr, b0.ptr, b1.ptr, c0.ptr, c1.ptr, c2.ptr, C.int(a0.npoly), C.int(a0.limbs-1), 1))
 }
 
+// LinearCombination runs a baby step of the polynomial evaluator (circuits/common/polynomial/polynomial_evaluator.go:342-355) as one kernel
+// (rh_ckks_linear_combination): x holds three device blocks per term, rows the limbs per poly of each term's blocks, table the caller's device scratch.
+func (d *DeviceRing) LinearCombination(level int, x []*C.uint64_t, rows []C.int, s0, s1, c0, c1 []uint64, out [3]*C.uint64_t, npoly int, table *C.uint64_t, tableWords int) {
+	p := func(s []uint64) *C.uint64_t {
+		if len(s) == 0 {
+			return nil
+		}
+		return (*C.uint64_t)(unsafe.Pointer(&s[0]))
+	}
+	var xp **C.uint64_t
+	var rp *C.int
+	if len(rows) > 0 {
+		xp, rp = &x[0], &rows[0]
+	}
+	d.must(C.rh_ckks_linear_combination(d.h, C.int(level), C.int(len(rows)), xp, rp, p(s0), p(s1), p(c0), p(c1), out[0], out[1], out[2], C.int(npoly), table, C.size_t(tableWords)))
+}
+
 // AutomorphismNTT mirrors ring.Ring.AutomorphismNTT (ring/automorphism.go:52-73).
 func (d *DeviceRing) AutomorphismNTT(in *DevPoly, galEl uint64, out *DevPoly) {
 	d.must(C.rh_ring_automorphism_ntt(d.h, C.int(in.limbs-1), in.ptr, C.uint64_t(galEl), out.ptr, C.int(in.npoly), 0))

@@ -512,7 +512,21 @@ int rh_bgv_axpby(rh_ring* r, int level, const uint64_t* a_dev, const uint64_t* b
  *                           else a) times ratio[i] = ratioInt mod q_i as Mul(ct, ratioInt, tmp) does it (ratio NULL: equal scales, nothing is
  *                           scaled), Add (sub != 0: Sub) on the components both operands have, the components only one has copied (:422-430)
  *                           and, for b's under Sub, negated with ring.Neg (:173-177: q_i - x, so 0 gives q_i as in the reference).  out has
- *                           the components of the larger operand. */
+ *                           the components of the larger operand.
+ *   rh_ckks_linear_combination  a baby step of the polynomial evaluator (circuits/common/polynomial/polynomial_evaluator.go:342-355), Add of a
+ *                           constant and nterms calls of MulThenAdd(X[k], c_k, res), in ONE launch: for the components j the outputs name,
+ *                           out_j = [j == 0] c + sum_k s_k X_k,j mod q_i, the canonical residue -- the bits of the sequence, whose every step
+ *                           ends in CRed(acc + MRed(x, MForm(s))).  x: a HOST array of 3 nterms device blocks (term k's component j at
+ *                           x[3 k + j]; entries past the last output's component are not read), x_rows[k] >= level + 1 the limbs per poly of
+ *                           term k's blocks (a power at a higher level is read as its AtLevel view); s0 / s1: host scalars, nterms rows of
+ *                           level + 1 words, as rh_ckks_scalar takes them; c0 / c1: the constant's (both NULL: none; nterms = 0 with a
+ *                           constant is allowed).  table_dev: device scratch of the CALLER, at least
+ *                           rh_ckks_linear_combination_table_words(nterms, level) words, which carries the terms to the kernel: the call keeps
+ *                           nothing in the handle, and concurrent callers bring a table each.  The table may be reused by the next call on
+ *                           the same stream.  Unlike its neighbours this entry is NOT in place: an output that overlaps a term (or the
+ *                           table) is refused.  Moduli must be below 2^61: the products are summed in 128 bits and reduced once per
+ *                           rh_ckks_linear_combination_chunk() = 56 terms, the most that bound allows (csrc/ckks.hip derives it);
+ *                           rh_ckks_linear_combination_width() terms have their loads in flight together. */
 enum rh_ckks_scalar_op { RH_CKKS_ADD_SCALAR = 0, RH_CKKS_SUB_SCALAR = 1, RH_CKKS_MUL_SCALAR = 2, RH_CKKS_MUL_SCALAR_THEN_ADD = 3 };
 int rh_ckks_tensor(rh_ring* r, int level, const uint64_t* a0_dev, const uint64_t* a1_dev, const uint64_t* b0_dev, const uint64_t* b1_dev,
                    uint64_t* c0_dev, uint64_t* c1_dev, uint64_t* c2_dev, int npoly, int accumulate, int square);
@@ -523,6 +537,12 @@ int rh_ckks_scalar(rh_ring* r, int level, int op, const uint64_t* in0_dev, const
 int rh_ckks_scale_then_add(rh_ring* r, int level, const uint64_t* a0_dev, const uint64_t* a1_dev, const uint64_t* a2_dev, const uint64_t* b0_dev,
                            const uint64_t* b1_dev, const uint64_t* b2_dev, uint64_t* out0_dev, uint64_t* out1_dev, uint64_t* out2_dev, int npoly,
                            const uint64_t* ratio, int sub, int scaled_is_b);
+int rh_ckks_linear_combination(rh_ring* r, int level, int nterms, const uint64_t* const* x_dev, const int* x_rows, const uint64_t* s0,
+                               const uint64_t* s1, const uint64_t* c0, const uint64_t* c1, uint64_t* out0_dev, uint64_t* out1_dev,
+                               uint64_t* out2_dev, int npoly, uint64_t* table_dev, size_t table_words);
+size_t rh_ckks_linear_combination_table_words(int nterms, int level);
+int rh_ckks_linear_combination_chunk(void);
+int rh_ckks_linear_combination_width(void);
 
 /* ---- CKKS encoder: the float64 path of schemes/ckks/encoder.go on device batches of nvec vectors ------------------------------------
  * A handle on a STANDARD ring.  Refused by name (RH_ERR_UNSUPPORTED): conjugate-invariant rings, 3N rings, prec > 53 (the *big.Float /

@@ -180,6 +180,22 @@ class Ring {
   void TensorDegree1(const Poly& a0, const Poly& a1, const Poly& b0, const Poly& b1, Poly& c0, Poly& c1, Poly& c2, bool mformFirst = true) const {
     check(rh_ring_tensor_degree1(h_.get(), a0.data(), a1.data(), b0.data(), b1.data(), c0.data(), c1.data(), c2.data(), a0.npoly(), level_, mformFirst ? 1 : 0));
   }
+  // CKKS: a baby step of the polynomial evaluator as one kernel (rh_ckks_linear_combination): out_j = [j == 0] c + sum_k s_k X_k,j.  terms[k]: the
+  // components of X_k (each term as many as `out`), s0 / s1: terms.size() rows of level + 1 scalars, c0 / c1: the constant's or null; table: device
+  // scratch of the caller of at least LinearCombinationTableWords(terms.size()) words
+  size_t LinearCombinationTableWords(size_t nterms) const { return rh_ckks_linear_combination_table_words((int)nterms, level_); }
+  void LinearCombination(const std::vector<std::vector<const Poly*>>& terms, const uint64_t* s0, const uint64_t* s1, const uint64_t* c0, const uint64_t* c1,
+                         const std::vector<Poly*>& out, uint64_t* table, size_t tableWords) const {
+    if (out.empty() || out.size() > 3) throw std::invalid_argument("LinearCombination: one to three output components");
+    std::vector<const uint64_t*> x(3 * terms.size(), nullptr); std::vector<int> rows(terms.size(), 0);
+    for (size_t k = 0; k < terms.size(); ++k) {
+      if (terms[k].size() != out.size()) throw std::invalid_argument("LinearCombination: every term has the output's components");
+      for (size_t j = 0; j < out.size(); ++j) x[3 * k + j] = terms[k][j]->data();
+      rows[k] = terms[k][0]->limbs();
+    }
+    check(rh_ckks_linear_combination(h_.get(), level_, (int)terms.size(), x.data(), rows.data(), s0, s1, c0, c1, out[0]->data(), out.size() > 1 ? out[1]->data() : nullptr,
+                                     out.size() > 2 ? out[2]->data() : nullptr, out[0]->npoly(), table, tableWords));
+  }
   // BGV (schemes/bgv/evaluator.go): tensorStandard / mulRelinThenAdd ct x ct as one kernel, k[i] = T r0 2^128 mod q_i; b0 / b1 null: squaring;
   // accumulate 0 / 1 / 2 and r1 (null or MForm(r1) per limb) as rh_bgv_tensor takes them.  BgvAxpby: out = r0 a +- r1 b (an operand and its scalar may be null)
   void BgvTensor(const Poly& a0, const Poly& a1, const Poly* b0, const Poly* b1, Poly& c0, Poly& c1, Poly& c2, const uint64_t* k, const uint64_t* r1 = nullptr,

@@ -12,3 +12,4 @@ from . import rlwe  # noqa: F401,E402
 from . import ckks  # noqa: F401,E402
 from . import rgsw  # noqa: F401,E402
 from . import bgv  # noqa: F401,E402
+from . import polynomial  # noqa: F401,E402

@@ -97,14 +97,37 @@ def _is_slice(op):
     return isinstance(op, (list, tuple, np.ndarray))
 
 
+class Complex:
+    """bignum.Complex (utils/bignum/complex.go:13-16): two big.Floats, held as exact rationals -- the scalar operand type that carries more
+    than a complex128 does (the coefficients of a polynomial, polynomial.py)"""
+    __slots__ = ("re", "im")
+
+    def __init__(self, re_=0, im_=0):
+        self.re, self.im = Fraction(re_), Fraction(im_)
+
+    def __eq__(self, other):
+        return isinstance(other, Complex) and (self.re, self.im) == (other.re, other.im)
+
+    def __hash__(self):
+        return hash((self.re, self.im))
+
+    def __complex__(self):
+        return complex(float(self.re), float(self.im))
+
+    def __repr__(self):
+        return "Complex(%s, %s)" % (self.re, self.im)
+
+
 def _is_scalar(op):
-    return isinstance(op, (int, float, complex, Fraction, np.integer, np.floating, np.complexfloating)) and not isinstance(op, bool)
+    return isinstance(op, (int, float, complex, Fraction, Complex, np.integer, np.floating, np.complexfloating)) and not isinstance(op, bool)
 
 
 def to_complex(value, prec):
     """bignum.ToComplex (utils/bignum/complex.go:22-55): both parts as big.Floats of `prec` bits -- ints and big.Floats (Fractions here) are
     ROUNDED to prec bits like floats.  Returns two Fractions."""
-    if isinstance(value, (complex, np.complexfloating)):
+    if isinstance(value, Complex):
+        re_, im_ = value.re, value.im
+    elif isinstance(value, (complex, np.complexfloating)):
         re_, im_ = Fraction(float(value.real)), Fraction(float(value.imag))
     elif isinstance(value, (float, np.floating)):
         re_, im_ = Fraction(float(value)), Fraction(0)
@@ -131,7 +154,9 @@ class Evaluator:
     the same bits; None (default) what FUSED_DEFAULT says per kernel, the measured choice.  encoding_precision:
     Parameters.EncodingPrecision(), max(53, floor(log2 DefaultScale)) (schemes/ckks/params.go:187-195)."""
 
-    FUSED_DEFAULT = {"tensor": True, "mul_plain": True, "scalar": False, "scale_then_add": True}   # profiles/ckks_ops.json: the scalar kernel is not faster than the four half-row launches
+    # profiles/ckks_ops.json: the scalar kernel is not faster than the four half-row launches; profiles/ckks_polynomial.json: the one-launch baby step
+    # (polynomial.py) is 4 to 7 % slower than the composed calls at batch 64 through this layer, whose per-term host work the composed launches overlap
+    FUSED_DEFAULT = {"tensor": True, "mul_plain": True, "scalar": False, "scale_then_add": True, "linear_combination": False}
 
     def __init__(self, ringQ, ringP=None, rlk=None, levels_consumed_per_rescaling=1, galois_keys=None, fused=None, encoding_precision=53, encoder=None):
         self.ringQ, self.ringP, self.rlk = ringQ, ringP, rlk
@@ -143,6 +168,7 @@ class Evaluator:
         self.ks = rlwe.Evaluator(ringQ, ringP, galois_keys=galois_keys) if ringP is not None else None
         self._pool = {}
         self._roots1 = None
+        self._scalars = {}                 # _rns_scalar's results by (level, scale, constant): host big-integer work, about a millisecond each at 16 limbs
 
     def close(self):
         self._pool.clear()
@@ -217,6 +243,12 @@ class Evaluator:
     def _rns_scalar(self, level, scale, cmplx):
         """bigComplexToRNSScalar (scaling.go:10-43) followed by the scalar half of evaluateWithScalar (:439-442): the RNS scalars for
         coefficients [0, N/2) and [N/2, N).  cmplx: the two Fractions of to_complex."""
+        key = (level, Scale(scale).Value, cmplx[0], cmplx[1])                                  # a circuit asks for the same few scalars call after call
+        hit = self._scalars.get(key)
+        if hit is not None:
+            return hit
+        if len(self._scalars) >= 4096:
+            self._scalars.clear()
         qs = self._qs(level)
         real = scaled_int(cmplx[0], Scale(scale).Value, self.encoding_precision)
         imag = scaled_int(cmplx[1], Scale(scale).Value, self.encoding_precision)
@@ -229,7 +261,8 @@ class Evaluator:
                 im_ = im_ * self._roots1[i] * pow(1 << 64, -1, q) % q                            # MRed(RNSImag[i], RootsForward[1]) (:440)
             s0.append((re_ + im_) % q)                                                           # (:441)
             s1.append((re_ + q - im_) % q)
-        return s0, s1
+        self._scalars[key] = (tuple(s0), tuple(s1))
+        return self._scalars[key]
 
     def _use(self, kind):
         return self.fused[kind]

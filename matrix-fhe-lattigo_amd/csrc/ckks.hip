@@ -12,8 +12,12 @@
 //                               [0, N/2) and one for [N/2, N), on every component given.
 //   ckks_scale_then_add_kernel  the scale-matching Add / Sub of evaluateInPlace (:246-431): Mul(ct, ratioInt, tmp) of the operand with the smaller
 //                               scale, Add / Sub on the shared components, the rest copied (:422-430) and negated under Sub (:173-177).
+//   ckks_linear_combination_kernel  a baby step of the polynomial evaluator (circuits/common/polynomial/polynomial_evaluator.go:342-355): an Add of
+//                               a constant and K calls of MulThenAdd(X[k], c_k, res), out_j = [j == 0] const + sum_k MRed(X_k,j, MForm(s_k)), as ONE pass:
+//                               K + 1 rows of traffic per component where the sequence moves 3 K, the products summed in 128 bits and reduced once
+//                               per LC_CHUNK terms.  Its terms are AtLevel views of blocks at higher levels; its outputs may alias no input.
 //
-// Each thread reads all of its operands before it writes, so any output may be any input.  Bandwidth-bound, no LDS; 16-byte loads and
+// Each thread reads all of its operands before it writes, so any output may be any input (the linear combination excepted).  Bandwidth-bound, no LDS; 16-byte loads and
 // stores, rows (one limb of one poly) on blockIdx.x so the per-limb constants are wave-uniform, non-temporal beyond the Infinity Cache: the
 // scaffold of stream_kernels.hip.hpp, as the BGV kernels (bgv.hip).
 #include <hip/hip_runtime.h>
@@ -147,6 +151,80 @@ ckks_scale_then_add_kernel(CkksComps p, unsigned n, const LimbConsts* __restrict
   }
 }
 
+// ---- linear combination ---------------------------------------------------------------------------------------------------------------
+// Every step of the reference's sequence ends in CRed(acc + MRed(x, s')), s' = MForm(s): the result is the canonical residue of
+// const + sum_k x_k s'_k 2^-64, whatever the order of the reductions.  Here T = sum x_k s'_k is kept in 128 bits and reduced by one Montgomery
+// step, (T - (T_lo qinv mod 2^64) q) / 2^64 = T_hi - H with H < q, and one Barrett step on the 64-bit word T_hi - H + q.
+// The chunk bound: q < 2^61 gives x s' <= (q - 1)^2 < 2^122, so after C terms T < C 2^122 (no carry out of 128 bits for C <= 64) and
+// T_hi - H + q <= T_hi + q < C 2^58 + 2^61 = (C + 8) 2^58, which stays a 64-bit word for C <= 56.
+#define LC_CHUNK 56            // terms summed between two reductions
+#define LC_WIDTH 4             // terms whose loads are in flight together
+#define LC_MODULUS_BITS 61     // the bound holds for q < 2^61 (checked per call)
+static_assert(LC_CHUNK <= 64 && (unsigned __int128)(LC_CHUNK + 8) << (2 * LC_MODULUS_BITS - 64) <= (unsigned __int128)1 << 64, "LC_CHUNK terms of q < 2^61 pass 64 bits after the Montgomery step");
+static_assert(LC_CHUNK % LC_WIDTH == 0, "a chunk is a whole number of load groups");
+// The device table of a call, in words: the constant's scalars a[L], b[L] (coefficients [0, N/2), [N/2, N)), then per term
+// { block of component 0, 1, 2; limbs per poly of the blocks; a[L]; b[L] }, the scalars in Montgomery form.
+#define LC_TERM_HEAD 4
+static inline size_t lc_table_words(int nterms, int L) { return 2 * (size_t)L + (size_t)nterms * (LC_TERM_HEAD + 2 * (size_t)L); }
+
+RH_DEV u64 lc_reduce(u128 t, const LimbConsts& c) {
+  const u64 lo = (u64)t, hi = (u64)(t >> 64);
+  return bred_add(hi - mulhi64(lo * c.qinv, c.q) + c.q, c.q, c.bred0);
+}
+
+// a block address out of the table: global memory, which the compiler cannot know of a word it loaded (it would emit flat loads)
+RH_DEV const u64* lc_block(u64 addr) { return (const u64*)reinterpret_cast<const __attribute__((address_space(1))) u64*>(addr); }
+
+// grid: (npoly * L, chunks).  The term loops run on kernel arguments and table words alone: wave-uniform.
+template <int NC>
+__global__ void __launch_bounds__(256)
+ckks_linear_combination_kernel(CkksComps p, const u64* __restrict__ table, int nterms, int has_const, unsigned n, const LimbConsts* __restrict__ consts,
+                               int L, int nt) {
+  const StreamRow row(consts, L, n);
+  const LimbConsts& c = row.c;
+  const unsigned half = n >> 2;
+  const size_t stride = LC_TERM_HEAD + 2 * (size_t)L;
+  const u64* terms = table + 2 * (size_t)L;
+  RH_FOR_EACH_PAIR(i, 0, n >> 1) {
+    const bool lower = i < half;
+    ulonglong2 res[NC];
+#pragma unroll
+    for (int j = 0; j < NC; ++j) res[j] = make_ulonglong2(0, 0);
+    if (has_const) { const u64 ca = table[row.limb], cb = table[L + row.limb]; res[0].x = res[0].y = lower ? ca : cb; }
+    for (int k0 = 0; k0 < nterms; k0 += LC_CHUNK) {
+      const int k1 = min(k0 + LC_CHUNK, nterms);
+      u128 acc[NC][2];
+#pragma unroll
+      for (int j = 0; j < NC; ++j) acc[j][0] = acc[j][1] = 0;
+      for (int k = k0; k < k1; k += LC_WIDTH) {
+        ulonglong2 x[LC_WIDTH][NC];
+        u64 sc[LC_WIDTH];
+#pragma unroll
+        for (int w = 0; w < LC_WIDTH; ++w) {
+          if (k + w >= k1) break;
+          const u64* t = terms + (size_t)(k + w) * stride;
+          const size_t o = row.at((int)t[3], n) + 2 * (size_t)i;
+#pragma unroll
+          for (int j = 0; j < NC; ++j) x[w][j] = rh_ld2(lc_block(t[j]) + o, nt);
+          const u64 sa = t[LC_TERM_HEAD + row.limb], sb = t[LC_TERM_HEAD + L + row.limb];
+          sc[w] = lower ? sa : sb;
+        }
+#pragma unroll
+        for (int w = 0; w < LC_WIDTH; ++w) {
+          if (k + w >= k1) break;
+#pragma unroll
+          for (int j = 0; j < NC; ++j) { acc[j][0] += (u128)x[w][j].x * sc[w]; acc[j][1] += (u128)x[w][j].y * sc[w]; }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < NC; ++j) { res[j].x = cred(res[j].x + lc_reduce(acc[j][0], c), c.q); res[j].y = cred(res[j].y + lc_reduce(acc[j][1], c), c.q); }
+    }
+    const size_t o = row.ro + 2 * (size_t)i;
+#pragma unroll
+    for (int j = 0; j < NC; ++j) rh_st2(p.out[j] + o, res[j], nt);
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
@@ -250,4 +328,80 @@ extern "C" int rh_ckks_scale_then_add(rh_ring* r, int level, const uint64_t* a0,
   const CkksComps p{{a0, a1, a2}, {b0, b1, b2}, {out0, out1, out2}};
   ckks_scale_then_add_kernel<<<g.grid, 256, 0, rh_stream(r)>>>(p, n, r->d_consts, level + 1, s, ratio ? 1 : 0, sub ? 1 : 0, scaled_is_b ? 1 : 0, g.nt);
   return rh_launch_ok("ckks_scale_then_add_kernel");
+}
+
+// Page-locked staging of the table on its way to the device: a few slots per calling thread, each reused once the copy that read it has run
+// (its event).  Nothing of a call lives in the ring handle; the slots stay with their thread.
+struct LcStage { u64* h = nullptr; size_t words = 0; hipEvent_t done = nullptr; };
+static int lc_stage(size_t words, LcStage** out) {
+  static thread_local LcStage slots[4];
+  static thread_local unsigned next = 0;
+  LcStage& s = slots[next++ % 4];
+  if (s.done && hipEventSynchronize(s.done) != hipSuccess) return rh_fail(RH_ERR_DEVICE, "rh_ckks_linear_combination: waiting for an earlier table copy failed");
+  if (!s.done && hipEventCreateWithFlags(&s.done, hipEventDisableTiming) != hipSuccess) return rh_fail(RH_ERR_DEVICE, "rh_ckks_linear_combination: hipEventCreate failed");
+  if (s.words < words) {
+    if (s.h) (void)hipHostFree(s.h);
+    s.h = nullptr; s.words = 0;
+    if (hipHostMalloc((void**)&s.h, words * 8, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return rh_fail(RH_ERR_NOMEM, "rh_ckks_linear_combination: hipHostMalloc(%zu words) failed", words); }
+    s.words = words;
+  }
+  *out = &s;
+  return RH_OK;
+}
+
+extern "C" size_t rh_ckks_linear_combination_table_words(int nterms, int level) { return nterms < 0 || level < 0 ? 0 : lc_table_words(nterms, level + 1); }
+extern "C" int rh_ckks_linear_combination_chunk(void) { return LC_CHUNK; }
+extern "C" int rh_ckks_linear_combination_width(void) { return LC_WIDTH; }
+
+extern "C" int rh_ckks_linear_combination(rh_ring* r, int level, int nterms, const uint64_t* const* x, const int* x_rows, const uint64_t* s0,
+                                          const uint64_t* s1, const uint64_t* c0, const uint64_t* c1, uint64_t* out0, uint64_t* out1, uint64_t* out2,
+                                          int npoly, uint64_t* table, size_t table_words) {
+  const char* who = "rh_ckks_linear_combination";
+  if (int rc = rh_scheme_args(r, level, npoly, CKKS_RINGS, 4, who)) return rc;
+  if (nterms < 0) return rh_fail(RH_ERR_ARG, "%s: nterms < 0", who);
+  if (!out0 || (out2 && !out1) || (c0 == nullptr) != (c1 == nullptr) || (nterms && (!x || !x_rows || !s0 || !s1))) return rh_fail(RH_ERR_ARG, "%s: null argument", who);
+  if (!table) return rh_fail(RH_ERR_ARG, "%s: null table (device scratch of rh_ckks_linear_combination_table_words(nterms, level) words)", who);
+  const int L = level + 1, nc = out2 ? 3 : out1 ? 2 : 1;
+  const size_t words = lc_table_words(nterms, L), N = (size_t)r->N;
+  if (table_words < words) return rh_fail(RH_ERR_ARG, "%s: the table holds %zu words, %d terms at level %d need %zu", who, table_words, nterms, level, words);
+  for (int i = 0; i < L; ++i)
+    if (r->moduli[i] >> LC_MODULUS_BITS) return rh_fail(RH_ERR_ARG, "%s: modulus %d is not below 2^%d, the bound the %d-term chunks are sized for", who, i, LC_MODULUS_BITS, LC_CHUNK);
+  u64* outs[3] = {out0, out1, out2};
+  IsBlock written[4], read[3];
+  for (int j = 0; j < nc; ++j) written[j] = {outs[j], (size_t)npoly * L * N};
+  written[nc] = {table, words};
+  for (int k = 0; k < nterms; ++k) {
+    if (x_rows[k] < L) return rh_fail(RH_ERR_ARG, "%s: term %d holds %d limbs per poly, fewer than level %d needs", who, k, x_rows[k], level);
+    for (int j = 0; j < nc; ++j) {
+      if (!x[3 * k + j]) return rh_fail(RH_ERR_ARG, "%s: term %d has no component %d", who, k, j);
+      read[j] = {x[3 * k + j], (size_t)npoly * (size_t)x_rows[k] * N};
+    }
+    if (int rc = is_blocks(written, nc + 1, read, nc, who, "an output (or the table) overlaps a term: the sum is not computed in place")) return rc;
+  }
+  if (int rc = is_blocks(written, nc, written + nc, 1, who, "an output overlaps the table")) return rc;
+  const unsigned rows = (unsigned)npoly * (unsigned)L;
+  const RhStreamGrid g = rh_stream_begin(r, rows);
+  hipStream_t st = rh_stream(r);
+  LcStage* stage;
+  if (int rc = lc_stage(words, &stage)) return rc;
+  u64* t = stage->h;
+  RhScalars s;
+  if (int rc = rh_pack_scalars(r, level, c0, c1, false, &s, who, "constant")) return rc;   // Add of a scalar (:82-101): the residues as they are
+  for (int i = 0; i < L; ++i) { t[i] = s.a[i]; t[L + i] = s.b[i]; }
+  for (int k = 0; k < nterms; ++k) {
+    u64* e = t + 2 * (size_t)L + (size_t)k * (LC_TERM_HEAD + 2 * (size_t)L);
+    for (int j = 0; j < 3; ++j) e[j] = j < nc ? (u64)(uintptr_t)x[3 * k + j] : 0;
+    e[3] = (u64)x_rows[k];
+    if (int rc = rh_pack_scalars(r, level, s0 + (size_t)k * L, s1 + (size_t)k * L, true, &s, who)) return rc;   // MulDoubleRNSScalarThenAdd: MForm(scalar)
+    for (int i = 0; i < L; ++i) { e[LC_TERM_HEAD + i] = s.a[i]; e[LC_TERM_HEAD + L + i] = s.b[i]; }
+  }
+  if (hipMemcpyAsync(table, t, words * 8, hipMemcpyHostToDevice, st) != hipSuccess || hipEventRecord(stage->done, st) != hipSuccess)
+    return rh_fail(RH_ERR_DEVICE, "%s: table copy failed", who);
+  if (rows == 0) return RH_OK;
+  const CkksComps p{{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, {out0, out1, out2}};
+  const unsigned n = (unsigned)r->N;
+#define CKKS_LC(NC) ckks_linear_combination_kernel<NC><<<g.grid, 256, 0, st>>>(p, table, nterms, c0 ? 1 : 0, n, r->d_consts, L, g.nt)
+  if (nc == 1) CKKS_LC(1); else if (nc == 2) CKKS_LC(2); else CKKS_LC(3);
+#undef CKKS_LC
+  return rh_launch_ok("ckks_linear_combination_kernel");
 }

@@ -11,7 +11,9 @@ the lift and Q to T alone, one kernel each against the reference's sequence of r
 gap 2 and T = 786433 for gap 1) and writes profiles/bgv_encoder.json; `bench_ops.py inner_sum [OUT.json]` the sums of rotations
 (PartialTracesSum for n = 7 and n = 8 at the config 5 ring, fused against composed, and each of the two kernels of csrc/inner_sum.hip against the
 passes it replaces) and writes profiles/inner_sum.json; `bench_ops.py ring_packing [OUT.json]` the ring-packing evaluator (Expand, Pack, Split, Merge at the
-config 5 ring and at N = 2^12, fused against composed, batched against per-ciphertext) and writes profiles/ring_packing.json."""
+config 5 ring and at N = 2^12, fused against composed, batched against per-ciphertext) and writes profiles/ring_packing.json;
+`bench_ops.py polynomial [OUT.json]` the polynomial evaluator (the baby step and the whole Evaluate at N = 2^16, 16 limbs, batches of 1 and 64,
+K = 7, 15, 31: rh_ckks_linear_combination against the composed sequence of MulThenAdd calls) and writes profiles/ckks_polynomial.json."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -668,6 +670,99 @@ def ring_packing_group(out_path):
         json.dump(res, fh, indent=1)
         fh.write("\n")
     print(json.dumps(res, indent=1))
+
+
+def polynomial_group(out_path):
+    """N = 2^16, 16 limbs of Q (GenModuli [55] + [45] * 15, scale 2^45: the regime the reference's own test runs in), 4 of P, batches of 1 and 64.
+    The baby step: EvaluatePolynomialVectorFromPowerBasis of a degree-K polynomial on a synthetic power basis of K degree-1 powers at the target
+    level, K = 7, 15, 31 -- one rh_ckks_linear_combination (fused=True) against the Add and K MulThenAdd calls of the composed path, which is the
+    baseline, timed HERE, alternating with the fused one.  Rows moved per component and limb: K + 1 against 3 K (the first MulThenAdd included,
+    the zeroing of the accumulator not).  Then the whole Evaluate of a degree-K polynomial (the powers, K's baby steps, the giant steps with their
+    relinearisations and rescalings), where the baby steps are a small share.  Every window repeats one evaluation, so the evaluator's memo of the
+    host scalars (ckks.Evaluator._rns_scalar) is warm on both sides: the figures are the steady state of a circuit that is evaluated again and again.  Medians of `rounds` windows; `fused_default` as in ckks_group."""
+    import statistics
+    from oracle import primes
+    N, LQ, LP, rounds = 1 << 16, 16, 4, 5
+    Qg, Pg = primes.gen_moduli(17, [55] + [45] * (LQ - 1), [61] * LP)
+    Q, P = [int(q) for q in Qg], [int(p) for p in Pg]
+    rq, rp = rh.Ring(N, Q), rh.Ring(N, P); rq.set_stream(stream.cuda_stream); rp.set_stream(stream.cuda_stream)
+    digits = (LQ + LP - 1) // LP
+    evq, evp = rand_block(2 * digits, Q, N), rand_block(2 * digits, P, N)
+    rlk = rh.rlwe.GadgetCiphertext.__new__(rh.rlwe.GadgetCiphertext)
+    rlk.digits, rlk.levelQ, rlk.levelP, rlk.BaseTwoDecomposition, rlk.digits_per_limb = digits, LQ - 1, LP - 1, 0, None
+    rlk.Q, rlk.P = rh.DevicePoly.from_torch(rq, evq), rh.DevicePoly.from_torch(rp, evp)
+    evs = {f: rh.ckks.Evaluator(rq, rp, rlk=rlk) for f in (True, False)}          # every other kernel by its measured default on both sides
+    for f, ev in evs.items():
+        ev.fused["linear_combination"] = f
+    pes = {f: rh.polynomial.PolynomialEvaluator(evs[f]) for f in (True, False)}
+    Pm, Sc = rh.polynomial, rh.ckks.Scale
+    stat = lambda v: {"ms_median": round(statistics.median(v), 4), "ms_min": round(min(v), 4), "ms_max": round(max(v), 4)}
+    rng = np.random.default_rng(7)
+    results = []
+
+    def record(name, B, K, fn, reps, extra, warm=2):
+        outs = [fn(f) for f in (True, False)]                           # same bits first, at the shape that is timed
+        same = all(np.array_equal(x.numpy(), y.numpy()) for x, y in zip(outs[0].Value, outs[1].Value)) and outs[0].Scale.Value == outs[1].Scale.Value
+        assert same, "fused and composed differ: %s B=%d K=%d" % (name, B, K)
+        del outs
+        tf, tc = [], []
+        for _ in range(rounds):
+            tf.append(timed(lambda: fn(True), reps=reps, warm=warm)); tc.append(timed(lambda: fn(False), reps=reps, warm=warm))
+        f, c = stat(tf), stat(tc)
+        spread = round(c["ms_max"] - c["ms_min"], 4)
+        e = {"op": name, "batch": B, "K": K, "fused": f, "composed": c, "ratio_composed_over_fused": round(c["ms_median"] / f["ms_median"], 3),
+             "composed_run_to_run_spread_ms": spread, "fused_default": bool(f["ms_median"] <= c["ms_median"] + spread)}
+        e.update(extra(f, c))
+        results.append(e)
+        print(json.dumps(e), flush=True)
+
+    for B in (1, 64):
+        for K in (7, 15, 31):
+            co = [complex(a, b) for a, b in rng.uniform(-1, 1, (K + 1, 2))]
+            pol = Pm.PolynomialVector([Pm.Polynomial(Pm.Monomial, co)])
+            # ---- the baby step: K powers at the target level, scales below the target scale
+            first = rh.Ciphertext([rh.DevicePoly.from_torch(rq, rand_block(B, Q, N)) for _ in range(2)], is_ntt=True)
+            first.Scale = Sc(2 ** 45)
+            pb = Pm.PowerBasis(first, Pm.Monomial)
+            for k in range(2, K + 1):
+                pb.Value[k] = rh.Ciphertext([rh.DevicePoly.from_torch(rq, rand_block(B, Q, N)) for _ in range(2)], is_ntt=True)
+                pb.Value[k].Scale = Sc(2 ** 45 + k)
+            target = Sc(2 ** 45).Mul(Sc(Q[LQ - 1]))
+            row_bytes = 8.0 * N * LQ * B * 2                            # one row of every limb, both components
+
+            def bw(f, c, K=K, row_bytes=row_bytes):
+                f["algorithmic_GBps"] = round((K + 1) * row_bytes / (f["ms_median"] * 1e-3) / 1e9, 1)
+                f["frac_of_8TBps"] = round(f["algorithmic_GBps"] / PEAK, 3)
+                c["algorithmic_GBps"] = round(3 * K * row_bytes / (c["ms_median"] * 1e-3) / 1e9, 1)
+                return {"rows_fused": K + 1, "rows_composed": 3 * K}
+            record("baby step: EvaluatePolynomialVectorFromPowerBasis", B, K,
+                   lambda f: pes[f].EvaluatePolynomialVectorFromPowerBasis(LQ - 1, pol, pb, target), 10 if B == 1 else 5, bw)
+            del pb, first
+            torch.cuda.empty_cache()
+            # ---- the whole Evaluate
+            ct = rh.Ciphertext([rh.DevicePoly.from_torch(rq, rand_block(B, Q, N)) for _ in range(2)], is_ntt=True)
+            ct.Scale = Sc(2 ** 45)
+            record("Evaluate", B, K, lambda f: pes[f].Evaluate(ct, pol.Value[0], 2 ** 45), 5 if B == 1 else 2, lambda f, c: {}, warm=1)
+            del ct
+            torch.cuda.empty_cache()
+    from bench import csrc_tree_hash
+    baby64 = [e for e in results if e["op"].startswith("baby") and e["batch"] == 64]
+    res = {"device": torch.cuda.get_device_name(0), "csrc_tree": csrc_tree_hash(), "shape": {"N": N, "limbs_Q": LQ, "limbs_P": LP, "batches": [1, 64], "K": [7, 15, 31]},
+           "method": "%d alternating windows per case, device events, 2 warm-up calls per window (1 for Evaluate); clocks left to the driver's default governor" % rounds,
+           "linear_combination_default": bool(all(e["fused_default"] for e in baby64)),
+           "results": results}
+    with open(out_path, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(res, indent=1))
+    for ev in evs.values():
+        ev.close()
+    rq.close(); rp.close()
+
+
+if sys.argv[1:2] == ["polynomial"]:
+    polynomial_group(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "ckks_polynomial.json"))
+    sys.exit(0)
 
 
 if sys.argv[1:2] == ["ring_packing"]:
