@@ -471,6 +471,39 @@ func (k *KeySwitcher) ModDownPair(levelQ, levelP int, ctQ0, ctQ1, ctP0, ctP1, ct
 	k.q.must(C.rh_bext_moddown_qp_to_q_ntt_pair(k.be, C.int(levelQ), C.int(levelP), ctQ0.ptr, ctQ1.ptr, ctP0.ptr, ctP1.ptr, ct0.ptr, ct1.ptr, C.int(ct0.npoly)))
 }
 
+// DiagMacQP, RotateSumAccumulateQP and RotateMulAccumulateQP are the three streaming passes of the diagonal matrix x ciphertext product
+// (circuits/common/lintrans/lintrans_evaluator.go): the inner loop of MultiplyByDiagMatrixBSGS for one giant step (:311-357), its giant-step
+// tail (:384-393) and one diagonal of MultiplyByDiagMatrix (:200-218), one launch each over both components and the Q and P rows.
+// DiagMacQP: ptQ / ptP hold one device block per term (a one-poly diagonal), x four per term (xQ0, xQ1, xP0, xP1; xP0 = xP1 = nil for the baby
+// step 0 term, which lives modulo Q); table is the caller's device scratch of DiagMacTableWords(len(ptQ), levelQ, levelP) words.
+func DiagMacTableWords(nterms, levelQ, levelP int) int {
+	return int(C.rh_rlwe_diag_mac_qp_table_words(C.int(nterms), C.int(levelQ), C.int(levelP)))
+}
+func (k *KeySwitcher) DiagMacQP(levelQ, levelP int, ptQ, ptP, x []*C.uint64_t, tmpQ0, tmpQ1, tmpP0, tmpP1 *DevPoly, table *C.uint64_t, tableWords int) {
+	var q, p, xs **C.uint64_t
+	if len(ptQ) > 0 {
+		q, p, xs = &ptQ[0], &ptP[0], &x[0]
+	}
+	k.q.must(C.rh_rlwe_diag_mac_qp(k.be, C.int(levelQ), C.int(levelP), C.int(len(ptQ)), q, p, xs, tmpQ0.ptr, tmpQ1.ptr, tmpP0.ptr, tmpP1.ptr,
+		C.int(tmpQ0.npoly), table, C.size_t(tableWords)))
+}
+func (k *KeySwitcher) RotateSumAccumulateQP(levelQ, levelP int, galEl uint64, cQ0, cQ1, cP0, cP1, tmpQ0, tmpP0, accQ0, accQ1, accP0, accP1 *DevPoly, first bool) {
+	f := C.int(0)
+	if first {
+		f = 1
+	}
+	k.q.must(C.rh_rlwe_rotate_sum_accumulate_qp(k.be, C.int(levelQ), C.int(levelP), C.uint64_t(galEl), cQ0.ptr, cQ1.ptr, cP0.ptr, cP1.ptr, tmpQ0.ptr, tmpP0.ptr,
+		accQ0.ptr, accQ1.ptr, accP0.ptr, accP1.ptr, C.int(accQ0.npoly), f))
+}
+func (k *KeySwitcher) RotateMulAccumulateQP(levelQ, levelP int, galEl uint64, ptQ, ptP, ct0, cQ0, cQ1, cP0, cP1, accQ0, accQ1, accP0, accP1 *DevPoly, first bool) {
+	f := C.int(0)
+	if first {
+		f = 1
+	}
+	k.q.must(C.rh_rlwe_rotate_mul_accumulate_qp(k.be, C.int(levelQ), C.int(levelP), C.uint64_t(galEl), ptQ.ptr, ptP.ptr, ct0.ptr, cQ0.ptr, cQ1.ptr, cP0.ptr, cP1.ptr,
+		accQ0.ptr, accQ1.ptr, accP0.ptr, accP1.ptr, C.int(accQ0.npoly), f))
+}
+
 // ExternalProduct mirrors rgsw.Evaluator.ExternalProduct for RGSW ciphertexts with LevelP >= 1 and an NTT-domain RLWE ciphertext
 // (core/rgsw/evaluator.go:42-80, 188-257): the two lazy gadget products of (c0, c1) against rgsw.Value[0] and rgsw.Value[1] are added
 // modulo Q and modulo P (every Reduce of the reference's single accumulator pair is canonical, so the sum of the two canonical lazy products

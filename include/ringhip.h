@@ -392,6 +392,42 @@ int rh_rlwe_rotate_add_q(rh_ring* r, int level, uint64_t gen, const uint64_t* tm
 int rh_rlwe_partial_traces_sum(rh_bext* be, int levelQ, int levelP, const uint64_t* in0_dev, const uint64_t* in1_dev, int is_ntt, int offset,
                                int n, const rh_galois_key* keys, int nkeys, uint64_t* out0_dev, uint64_t* out1_dev, int npoly, int fused);
 
+/* ---- linear transformations (circuits/common/lintrans/lintrans_evaluator.go): the three streaming passes of the diagonal matrix x ciphertext
+ * product.  Standard rings (RH_ERR_UNSUPPORTED otherwise), NTT domain, dense blocks of npoly polys with levelQ+1 / levelP+1 limbs, canonical
+ * residues in and out; ONE launch over both components, the Q and the P rows and every poly.  A diagonal is ONE PolyQP (ptQ: at least levelQ+1
+ * rows, ptP: at least levelP+1 rows of N words, Montgomery form, NTT domain) shared by every poly of the batch.  The reference's lazy sums all
+ * end in Reduce before anything reads them (:220-239, :349-357, :419-427), so every output word is the canonical residue of the exact sum.
+ * Every block is 16-byte aligned and no written block may overlap a read one (RH_ERR_ARG).
+ *   rh_rlwe_diag_mac_qp               the inner loop of MultiplyByDiagMatrixBSGS for one giant step (:311-357: MulCoeffsMontgomeryLazy(ThenAddLazy)
+ *                                     modulo QP over the baby steps and the Reduce that closes them):
+ *                                       tmp_c[j] = (sum_k pt_k[j] * x_{k,c}[j]) * 2^-64 mod q,   c = 0, 1
+ *                                     x: four device blocks per term, { xQ0, xQ1, xP0, xP1 }: a pre-rotated ciphertext modulo QP, or with
+ *                                     xP0 = xP1 = NULL the baby step 0 term (P ct0, P ct1) modulo Q (:316-325), which adds nothing on the P rows; P
+ *                                     rows without another term are written as zero (:320-321).  The products are summed in 128 bits and reduced
+ *                                     once per rh_ckks_linear_combination_chunk() = 56 terms, which needs every modulus of Q and P below 2^61
+ *                                     (checked per call) and operands below q.  table: the caller's device scratch of at least
+ *                                     rh_rlwe_diag_mac_qp_table_words(nterms, levelQ, levelP) words, which carries the terms to the kernel: the
+ *                                     call keeps no state in the handle.  No output may overlap a term or the table.
+ *   rh_rlwe_rotate_sum_accumulate_qp  the giant-step tail of MultiplyByDiagMatrixBSGS (:384-393: ringQP.Add(cQP[0], tmp0QP) and the two
+ *                                     AutomorphismNTTWithIndex(ThenAddLazy) passes modulo QP):
+ *                                       acc_c[j] = [first ? 0 : acc_c[j]] + (c_c + [c == 0] tmp0)[index(j)]
+ *                                     c: the output of the lazy gadget product; acc may overlap neither c nor tmp0.
+ *   rh_rlwe_rotate_mul_accumulate_qp  one diagonal of MultiplyByDiagMatrix (:200-218: ringQ.Add of ct0TimesP, the two AutomorphismNTTWithIndex
+ *                                     passes modulo QP, MulCoeffsMontgomery(ThenAdd) by the diagonal):
+ *                                       acc_c[j] = [first ? 0 : acc_c[j]] + pt[j] * (c_c + [c == 0, Q rows] (P mod q_i) * ct0)[index(j)] * 2^-64
+ *                                     c: the output of rh_bext_gadget_product_hoisted_lazy; ct0: ctIn.Value[0]; acc may overlap none of them. */
+size_t rh_rlwe_diag_mac_qp_table_words(int nterms, int levelQ, int levelP);
+int rh_rlwe_diag_mac_qp(rh_bext* be, int levelQ, int levelP, int nterms, const uint64_t* const* ptQ_dev, const uint64_t* const* ptP_dev,
+                        const uint64_t* const* x_dev, uint64_t* tmpQ0_dev, uint64_t* tmpQ1_dev, uint64_t* tmpP0_dev, uint64_t* tmpP1_dev, int npoly,
+                        uint64_t* table_dev, size_t table_words);
+int rh_rlwe_rotate_sum_accumulate_qp(rh_bext* be, int levelQ, int levelP, uint64_t gen, const uint64_t* cQ0_dev, const uint64_t* cQ1_dev,
+                                     const uint64_t* cP0_dev, const uint64_t* cP1_dev, const uint64_t* tmpQ0_dev, const uint64_t* tmpP0_dev,
+                                     uint64_t* accQ0_dev, uint64_t* accQ1_dev, uint64_t* accP0_dev, uint64_t* accP1_dev, int npoly, int first);
+int rh_rlwe_rotate_mul_accumulate_qp(rh_bext* be, int levelQ, int levelP, uint64_t gen, const uint64_t* ptQ_dev, const uint64_t* ptP_dev,
+                                     const uint64_t* ct0_dev, const uint64_t* cQ0_dev, const uint64_t* cQ1_dev, const uint64_t* cP0_dev,
+                                     const uint64_t* cP1_dev, uint64_t* accQ0_dev, uint64_t* accQ1_dev, uint64_t* accP0_dev, uint64_t* accP1_dev,
+                                     int npoly, int first);
+
 /* ---- ring packing (core/rlwe/ring_packing.go).  Standard rings (RH_ERR_UNSUPPORTED otherwise), dense blocks of level+1 limbs per poly, canonical
  * residues in and out, both components of a batch of ciphertexts in one launch; the NTT-domain index map of the Galois element (any odd number,
  * taken modulo 2N) is computed in the kernel.  Every block is 16-byte aligned and no written block may overlap a read one (RH_ERR_ARG).

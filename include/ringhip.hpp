@@ -346,6 +346,26 @@ class BasisExtender {
     check(rh_rlwe_rotate_accumulate_qp(h_.get(), lq, lp, galEl, ct0.data(), tmpQ0.data(), tmpQ1.data(), tmpP0.data(), tmpP1.data(), accQ0.data(),
                                        accQ1.data(), accP0.data(), accP1.data(), ct0.npoly(), first ? 1 : 0));
   }
+  // The three streaming passes of the diagonal matrix x ciphertext product (circuits/common/lintrans/lintrans_evaluator.go): the inner loop of
+  // MultiplyByDiagMatrixBSGS for one giant step (:311-357), its giant-step tail (:384-393), one diagonal of MultiplyByDiagMatrix (:200-218).
+  // DiagMacQP: per term one diagonal (ptQ, ptP: one poly each) and four blocks {xQ0, xQ1, xP0, xP1} (xP0 = xP1 = nullptr: the baby step 0 term);
+  // table: the caller's device scratch of DiagMacTableWords(nterms, lq, lp) words
+  static size_t DiagMacTableWords(size_t nterms, int lq, int lp) { return rh_rlwe_diag_mac_qp_table_words((int)nterms, lq, lp); }
+  void DiagMacQP(int lq, int lp, const std::vector<const uint64_t*>& ptQ, const std::vector<const uint64_t*>& ptP, const std::vector<const uint64_t*>& x,
+                 Poly& tmpQ0, Poly& tmpQ1, Poly& tmpP0, Poly& tmpP1, Poly& table) const {
+    check(rh_rlwe_diag_mac_qp(h_.get(), lq, lp, (int)ptQ.size(), ptQ.data(), ptP.data(), x.data(), tmpQ0.data(), tmpQ1.data(), tmpP0.data(), tmpP1.data(),
+                              tmpQ0.npoly(), table.data(), table.words()));
+  }
+  void RotateSumAccumulateQP(int lq, int lp, uint64_t galEl, const Poly& cQ0, const Poly& cQ1, const Poly& cP0, const Poly& cP1, const Poly& tmpQ0,
+                             const Poly& tmpP0, Poly& accQ0, Poly& accQ1, Poly& accP0, Poly& accP1, bool first) const {
+    check(rh_rlwe_rotate_sum_accumulate_qp(h_.get(), lq, lp, galEl, cQ0.data(), cQ1.data(), cP0.data(), cP1.data(), tmpQ0.data(), tmpP0.data(), accQ0.data(),
+                                           accQ1.data(), accP0.data(), accP1.data(), accQ0.npoly(), first ? 1 : 0));
+  }
+  void RotateMulAccumulateQP(int lq, int lp, uint64_t galEl, const Poly& ptQ, const Poly& ptP, const Poly& ct0, const Poly& cQ0, const Poly& cQ1,
+                             const Poly& cP0, const Poly& cP1, Poly& accQ0, Poly& accQ1, Poly& accP0, Poly& accP1, bool first) const {
+    check(rh_rlwe_rotate_mul_accumulate_qp(h_.get(), lq, lp, galEl, ptQ.data(), ptP.data(), ct0.data(), cQ0.data(), cQ1.data(), cP0.data(), cP1.data(),
+                                           accQ0.data(), accQ1.data(), accP0.data(), accP1.data(), accQ0.npoly(), first ? 1 : 0));
+  }
  private:
   std::shared_ptr<rh_bext> h_;
 };

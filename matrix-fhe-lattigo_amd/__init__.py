@@ -13,3 +13,4 @@ from . import ckks  # noqa: F401,E402
 from . import rgsw  # noqa: F401,E402
 from . import bgv  # noqa: F401,E402
 from . import polynomial  # noqa: F401,E402
+from . import lintrans  # noqa: F401,E402

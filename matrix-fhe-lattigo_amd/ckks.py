@@ -920,10 +920,12 @@ class Encoder:
     Refused by name: conjugate-invariant and 3N rings, precision > 53 (the *big.Float / *bignum.Complex path), Decode with IsBatched = false
     at a level that is neither 0 nor the ring's top level."""
 
-    def __init__(self, ringQ, precision=53, roots=None):
+    def __init__(self, ringQ, precision=53, roots=None, ringP=None):
+        """ringP: the key-switch ring, for Embed into an rlwe.PolyQP (the ringqp.Poly arm of embedDouble, encoder.go:304-311: the diagonals of a
+        linear transformation); None (default): a PolyQP is refused by name"""
         import ctypes as C
-        self.ringQ, self.prec = ringQ, int(precision)
-        self._h = None
+        self.ringQ, self.ringP, self.prec = ringQ, ringP, int(precision)
+        self._h = self._hP = None
         if self.prec < 0:
             raise RingHipError("cannot NewEncoder: negative precision")
         self.m = 2 * ringQ.N
@@ -931,6 +933,12 @@ class Encoder:
         h = C.c_void_p()
         _check(lib().rh_ckks_encoder_create(C.byref(h), ringQ._h, r.ctypes.data_as(C.POINTER(C.c_double)), r.size // 2, self.prec))
         self._h = h
+        if ringP is not None:                                      # the same quantizer and transform over the P moduli
+            if ringP.N != ringQ.N or ringP.kind != ringQ.kind:
+                raise RingHipError("cannot NewEncoder: ringP must be a ring of ringQ's degree and type")
+            hP = C.c_void_p()
+            _check(lib().rh_ckks_encoder_create(C.byref(hP), ringP._h, r.ctypes.data_as(C.POINTER(C.c_double)), r.size // 2, self.prec))
+            self._hP = hP
         self.LogMaxSlots = ringQ.N.bit_length() - 2
         import threading
         self._tls = threading.local()      # per host thread: the upload blocks host values go through, kept so that no call frees device memory
@@ -939,6 +947,9 @@ class Encoder:
         if self._h:
             lib().rh_ckks_encoder_destroy(self._h)
             self._h = None
+        if getattr(self, "_hP", None):
+            lib().rh_ckks_encoder_destroy(self._hP)
+            self._hP = None
 
     def __del__(self):
         try:
@@ -1003,9 +1014,20 @@ class Encoder:
     # ---- Encode / Embed (:141-320) -------------------------------------------------------------------------------------------------------
     def Embed(self, values, metadata, polyOut):
         """embedDouble: metadata is anything with Scale, LogDimensions, IsNTT and IsMontgomery (a Plaintext, a Ciphertext given them);
-        polyOut a DevicePoly whose limb count sets the level"""
+        polyOut a DevicePoly whose limb count sets the level, or an rlwe.PolyQP (the ringqp.Poly arm, :304-311): its Q part is encoded as a
+        DevicePoly is, its P part is the same values quantized modulo the P moduli, each part at the level its limb count sets"""
         logs = self._log_slots(metadata.LogDimensions, "Embed")
         scale = metadata.Scale if isinstance(metadata.Scale, Scale) else Scale(metadata.Scale)
+        if isinstance(polyOut, rlwe.PolyQP):
+            if self._hP is None:
+                raise RingHipError("cannot Embed: polyOut is a ringqp.Poly but the encoder was built without ringP (Encoder(ringQ, ringP=...))")
+            if polyOut.Q.npoly != polyOut.P.npoly:
+                raise RingHipError("cannot Embed: the Q and P parts of polyOut hold different numbers of polys")
+            block = self._block(values, polyOut.Q.npoly, 1 << logs, "Embed")
+            ntt, mont = 1 if metadata.IsNTT else 0, 1 if getattr(metadata, "IsMontgomery", False) else 0
+            for h, part in ((self._h, polyOut.Q), (self._hP, polyOut.P)):
+                _check(lib().rh_ckks_encode(h, part.limbs - 1, logs, scale.Float64(), block.ptr, part.npoly, part.ptr, ntt, mont))
+            return
         block = self._block(values, polyOut.npoly, 1 << logs, "Embed")
         _check(lib().rh_ckks_encode(self._h, polyOut.limbs - 1, logs, scale.Float64(), block.ptr, polyOut.npoly, polyOut.ptr,
                                     1 if metadata.IsNTT else 0, 1 if getattr(metadata, "IsMontgomery", False) else 0))

@@ -24,6 +24,7 @@
 #include <cstring>
 #include "engine_internal.hpp"
 #include "stream_kernels.hip.hpp"
+#include "lc_reduce.hip.hpp"
 
 struct CkksComps { const u64* in[3]; const u64* in2[3]; u64* out[3]; };
 
@@ -152,28 +153,11 @@ ckks_scale_then_add_kernel(CkksComps p, unsigned n, const LimbConsts* __restrict
 }
 
 // ---- linear combination ---------------------------------------------------------------------------------------------------------------
-// Every step of the reference's sequence ends in CRed(acc + MRed(x, s')), s' = MForm(s): the result is the canonical residue of
-// const + sum_k x_k s'_k 2^-64, whatever the order of the reductions.  Here T = sum x_k s'_k is kept in 128 bits and reduced by one Montgomery
-// step, (T - (T_lo qinv mod 2^64) q) / 2^64 = T_hi - H with H < q, and one Barrett step on the 64-bit word T_hi - H + q.
-// The chunk bound: q < 2^61 gives x s' <= (q - 1)^2 < 2^122, so after C terms T < C 2^122 (no carry out of 128 bits for C <= 64) and
-// T_hi - H + q <= T_hi + q < C 2^58 + 2^61 = (C + 8) 2^58, which stays a 64-bit word for C <= 56.
-#define LC_CHUNK 56            // terms summed between two reductions
-#define LC_WIDTH 4             // terms whose loads are in flight together
-#define LC_MODULUS_BITS 61     // the bound holds for q < 2^61 (checked per call)
-static_assert(LC_CHUNK <= 64 && (unsigned __int128)(LC_CHUNK + 8) << (2 * LC_MODULUS_BITS - 64) <= (unsigned __int128)1 << 64, "LC_CHUNK terms of q < 2^61 pass 64 bits after the Montgomery step");
-static_assert(LC_CHUNK % LC_WIDTH == 0, "a chunk is a whole number of load groups");
+// The 128-bit accumulate-then-reduce, its chunk bound (LC_CHUNK, LC_WIDTH, LC_MODULUS_BITS) and lc_reduce: lc_reduce.hip.hpp, shared with lintrans.hip.
 // The device table of a call, in words: the constant's scalars a[L], b[L] (coefficients [0, N/2), [N/2, N)), then per term
 // { block of component 0, 1, 2; limbs per poly of the blocks; a[L]; b[L] }, the scalars in Montgomery form.
 #define LC_TERM_HEAD 4
 static inline size_t lc_table_words(int nterms, int L) { return 2 * (size_t)L + (size_t)nterms * (LC_TERM_HEAD + 2 * (size_t)L); }
-
-RH_DEV u64 lc_reduce(u128 t, const LimbConsts& c) {
-  const u64 lo = (u64)t, hi = (u64)(t >> 64);
-  return bred_add(hi - mulhi64(lo * c.qinv, c.q) + c.q, c.q, c.bred0);
-}
-
-// a block address out of the table: global memory, which the compiler cannot know of a word it loaded (it would emit flat loads)
-RH_DEV const u64* lc_block(u64 addr) { return (const u64*)reinterpret_cast<const __attribute__((address_space(1))) u64*>(addr); }
 
 // grid: (npoly * L, chunks).  The term loops run on kernel arguments and table words alone: wave-uniform.
 template <int NC>

@@ -9,7 +9,6 @@
 #pragma once
 #include "paired_gather.hip.hpp"
 
-struct RhPmodQ { u64 s[RH_MAX_LIMBS_K]; };      // MForm(P mod q_i) per limb of Q
 struct InnerSumQP {
   u64* accQ[2]; u64* accP[2];                   // accumulators modulo Q (LQ limbs per poly) and modulo P (LP limbs per poly), dense
   const u64* tmpQ[2]; const u64* tmpP[2];       // the lazy hoisted product, same shapes

@@ -1,5 +1,5 @@
 // paired_gather.hip.hpp -- the NTT-domain index map of an automorphism read as aligned 16-byte pairs (the derivation: inner_sum_kernels.hip.hpp).
-// Shared by the kernels that fuse the map with what follows it: inner_sum_kernels.hip.hpp, ring_packing_kernels.hip.hpp.
+// Shared by the kernels that fuse the map with what follows it: inner_sum_kernels.hip.hpp, ring_packing_kernels.hip.hpp, lintrans_kernels.hip.hpp.
 #pragma once
 #include "stream_kernels.hip.hpp"
 
@@ -15,3 +15,5 @@ RH_DEV ulonglong2 is_gather2(const u64* row, u32 idx) {
   const ulonglong2 w = *reinterpret_cast<const ulonglong2*>(row + (idx & ~1u));
   return (idx & 1) ? make_ulonglong2(w.y, w.x) : w;
 }
+
+struct RhPmodQ { u64 s[RH_MAX_LIMBS_K]; };      // MForm(P mod q_i) per limb of Q

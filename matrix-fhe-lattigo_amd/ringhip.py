@@ -138,6 +138,10 @@ def lib():
         "rh_rlwe_rotate_accumulate_qp": (i, [vp, i, i, C.c_uint64] + [vp] * 9 + [i, i]),
         "rh_rlwe_rotate_add_q": (i, [vp, i, C.c_uint64, vp, vp, vp, vp, i]),
         "rh_rlwe_partial_traces_sum": (i, [vp, i, i, vp, vp, i, i, i, C.POINTER(GaloisKeyEntry), i, vp, vp, i, i]),
+        "rh_rlwe_diag_mac_qp_table_words": (sz, [i, i, i]),
+        "rh_rlwe_diag_mac_qp": (i, [vp, i, i, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, vp, vp, i, vp, sz]),
+        "rh_rlwe_rotate_sum_accumulate_qp": (i, [vp, i, i, C.c_uint64] + [vp] * 10 + [i, i]),
+        "rh_rlwe_rotate_mul_accumulate_qp": (i, [vp, i, i, C.c_uint64] + [vp] * 11 + [i, i]),
         "rh_rlwe_expand_step": (i, [vp, i, C.c_uint64, vp, vp, vp, vp, vp, i]),
         "rh_rlwe_pack_combine": (i, [vp, i, vp, vp, i, vp, C.POINTER(C.c_int32), i, vp, vp, vp]),
         "rh_rlwe_rotate_addsub_q": (i, [vp, i, C.c_uint64, vp, vp, vp, vp, i, vp, C.POINTER(C.c_int32), i]),

@@ -13,7 +13,10 @@ gap 2 and T = 786433 for gap 1) and writes profiles/bgv_encoder.json; `bench_ops
 passes it replaces) and writes profiles/inner_sum.json; `bench_ops.py ring_packing [OUT.json]` the ring-packing evaluator (Expand, Pack, Split, Merge at the
 config 5 ring and at N = 2^12, fused against composed, batched against per-ciphertext) and writes profiles/ring_packing.json;
 `bench_ops.py polynomial [OUT.json]` the polynomial evaluator (the baby step and the whole Evaluate at N = 2^16, 16 limbs, batches of 1 and 64,
-K = 7, 15, 31: rh_ckks_linear_combination against the composed sequence of MulThenAdd calls) and writes profiles/ckks_polynomial.json."""
+K = 7, 15, 31: rh_ckks_linear_combination against the composed sequence of MulThenAdd calls) and writes profiles/ckks_polynomial.json;
+`bench_ops.py lintrans [OUT.json]` the linear transformations (lintrans.Evaluator.Evaluate at the config 5 ring, batches of 1 and 8: the reference
+test's nine diagonals with and without BSGS and a dense 64-diagonal matrix, each kernel of csrc/lintrans.hip alone against the ring calls it
+replaces and inside the whole Evaluate) and writes profiles/lintrans.json."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -758,6 +761,125 @@ def polynomial_group(out_path):
     for ev in evs.values():
         ev.close()
     rq.close(); rp.close()
+
+
+def lintrans_group(out_path):
+    """The config 5 ring of ckks_group: N = 2^16, 24 limbs of Qi60, 6 of Pi60, batches of 1 and 8 ciphertexts.  lintrans.Evaluator.Evaluate of the
+    reference test's nine diagonals with BSGS ratio 1, of a dense 64-diagonal matrix (ratio 1) and of the nine diagonals without BSGS; each of the
+    three kernels of csrc/lintrans.hip alone against the ring calls it replaces, and inside the whole Evaluate (that kernel fused, the other passes
+    composed) against the composed Evaluate.  Both sides are timed HERE, in alternating windows, as in inner_sum_group; `fused_default` is the rule
+    lintrans.Evaluator.FUSED_LINTRANS follows: the fused median within the composed windows' max - min of the composed median, or below it, alone
+    AND in the whole call, at every batch.  Diagonals and keys hold uniform residues: the passes do not look at values."""
+    import statistics
+    N, LQ, LP, rounds, reps = 1 << 16, 24, 6, 5, 3
+    Q, P = QI60[:LQ], PI60[:LP]
+    rq, rp = rh.Ring(N, Q), rh.Ring(N, P); rq.set_stream(stream.cuda_stream); rp.set_stream(stream.cuda_stream)
+    digits = (LQ + LP - 1) // LP
+    level, levelP = LQ - 1, LP - 1
+    log_slots = 15
+    slots = 1 << log_slots
+    lt_ = rh.lintrans
+
+    def key():
+        k = rh.rlwe.GadgetCiphertext.__new__(rh.rlwe.GadgetCiphertext)
+        k.digits, k.levelQ, k.levelP, k.BaseTwoDecomposition, k.digits_per_limb = digits, level, levelP, 0, None
+        k.Q, k.P = rh.DevicePoly.from_torch(rq, rand_block(2 * digits, Q, N)), rh.DevicePoly.from_torch(rp, rand_block(2 * digits, P, N))
+        return k
+
+    def transformation(diags, ratio):
+        lt = lt_.NewTransformation(rq, rp, lt_.Parameters(diags, level, levelP, 1 << 40, log_slots, ratio))
+        for k in lt.Vec:
+            lt.Vec[k] = rh.rlwe.PolyQP(rh.DevicePoly.from_torch(rq, rand_block(1, Q, N)), rh.DevicePoly.from_torch(rp, rand_block(1, P, N)))
+        return lt
+    nine = [-15, -4, -1, 0, 1, 2, 3, 4, 15]
+    lts = {"nine diagonals, BSGS ratio 1": transformation(nine, 1), "dense 64 diagonals, BSGS ratio 1": transformation(list(range(64)), 1),
+           "nine diagonals, no BSGS": transformation(nine, -1)}
+    galEls = sorted({g for lt in lts.values() for g in lt.GaloisElements(N) if g != 1})
+    cev = rh.ckks.Evaluator(rq, rp, galois_keys={g: key() for g in galEls})
+    lev = lt_.Evaluator(cev)
+    ks = cev.ks
+    g = rh.rlwe.GaloisElement(N, 8)
+    stat = lambda v: {"ms_median": round(statistics.median(v), 4), "ms_min": round(min(v), 4), "ms_max": round(max(v), 4)}
+    results = []
+
+    def measure(name, B, fn, kernel, reps=reps):
+        tf, tc = [], []
+        for _ in range(rounds):
+            tf.append(timed(lambda: fn(True), reps=reps)); tc.append(timed(lambda: fn(False), reps=reps))
+        f, c = stat(tf), stat(tc)
+        spread = round(c["ms_max"] - c["ms_min"], 4)
+        results.append({"op": name, "batch": B, "kernel": kernel, "fused": f, "composed": c, "ratio_composed_over_fused": round(c["ms_median"] / f["ms_median"], 3),
+                        "composed_run_to_run_spread_ms": spread, "fused_default": bool(f["ms_median"] <= c["ms_median"] + spread)})
+    for B in (1, 8):
+        mkq = lambda n=B: rh.DevicePoly.from_torch(rq, rand_block(n, Q, N))
+        mkp = lambda n=B: rh.DevicePoly.from_torch(rp, rand_block(n, P, N))
+        ct, out = rh.Ciphertext([mkq(), mkq()], is_ntt=True), rh.Ciphertext([mkq(), mkq()], is_ntt=True)
+        ct.Scale = rh.ckks.Scale(1 << 40)
+        qp = lambda: rh.rlwe.ElementQP([rh.rlwe.PolyQP(mkq(), mkp()), rh.rlwe.PolyQP(mkq(), mkp())])
+        tmp, acc, cqp, rot = qp(), qp(), qp(), qp()
+        pct = rh.Ciphertext([mkq(), mkq()], is_ntt=True)
+        pres = [qp() for _ in range(3)]
+        rql, rpl = rq.AtLevel(level), rp.AtLevel(levelP)
+        for name, lt in lts.items():                      # same bits first, at the timed shape
+            res = []
+            for fused in (True, False):
+                lev.Evaluate(ct, lt, out, fused=fused)
+                res.append([v.numpy() for v in out.Value])
+            assert all(np.array_equal(x, y) for x, y in zip(*res)), "fused and composed Evaluate differ: " + name
+            del res
+        pts = list(lts["dense 64 diagonals, BSGS ratio 1"].Vec.values())
+        for K in (5, 8):                                  # the baby steps of one giant step: the nine diagonals' longest, the dense matrix's
+            terms = [(pts[0], None)] + [(pts[k], pres[k % 3]) for k in range(1, K)]
+            measure("baby-step sum of %d terms, the kernel alone" % K, B,
+                    lambda f: lev._diag_mac(level, levelP, terms, pct, tmp, B) if f else lev._diag_mac_composed(rql, rpl, terms, pct, tmp), "diag_mac", reps=30)
+
+        def tail(f):
+            if f:
+                rh.ringhip._check(rh.lib().rh_rlwe_rotate_sum_accumulate_qp(ks.be._h, level, levelP, g, cqp.Value[0].Q.ptr, cqp.Value[1].Q.ptr, cqp.Value[0].P.ptr,
+                                  cqp.Value[1].P.ptr, tmp.Value[0].Q.ptr, tmp.Value[0].P.ptr, acc.Value[0].Q.ptr, acc.Value[1].Q.ptr, acc.Value[0].P.ptr, acc.Value[1].P.ptr, B, 0))
+                return
+            rql.Add(cqp.Value[0].Q, tmp.Value[0].Q, cqp.Value[0].Q); rpl.Add(cqp.Value[0].P, tmp.Value[0].P, cqp.Value[0].P)
+            for c in (0, 1):
+                rql.AutomorphismNTT(cqp.Value[c].Q, g, rot.Value[c].Q); rpl.AutomorphismNTT(cqp.Value[c].P, g, rot.Value[c].P)
+                rql.Add(acc.Value[c].Q, rot.Value[c].Q, acc.Value[c].Q); rpl.Add(acc.Value[c].P, rot.Value[c].P, acc.Value[c].P)
+        measure("giant-step tail, the kernel alone", B, tail, "giant_tail", reps=50)
+        Pbig = 1
+        for p in P:
+            Pbig *= int(p)
+        ct0P = mkq()
+        pt = pts[1]
+
+        def step(f):
+            if f:
+                rh.ringhip._check(rh.lib().rh_rlwe_rotate_mul_accumulate_qp(ks.be._h, level, levelP, g, pt.Q.ptr, pt.P.ptr, ct.Value[0].ptr, cqp.Value[0].Q.ptr, cqp.Value[1].Q.ptr,
+                                  cqp.Value[0].P.ptr, cqp.Value[1].P.ptr, acc.Value[0].Q.ptr, acc.Value[1].Q.ptr, acc.Value[0].P.ptr, acc.Value[1].P.ptr, B, 0))
+                return
+            rql.Add(cqp.Value[0].Q, ct0P, cqp.Value[0].Q)     # P ct0 is formed once per call, outside the step
+            for c in (0, 1):
+                rql.AutomorphismNTT(cqp.Value[c].Q, g, rot.Value[c].Q); rpl.AutomorphismNTT(cqp.Value[c].P, g, rot.Value[c].P)
+                lev._mul_diag(rql, pt.Q, rot.Value[c].Q, acc.Value[c].Q, False); lev._mul_diag(rpl, pt.P, rot.Value[c].P, acc.Value[c].P, False)
+        measure("one diagonal without BSGS, the kernel alone", B, step, "naive_step", reps=50)
+        for name, lt in lts.items():
+            for kernel in (("naive_step",) if lt.N1 == 0 else ("diag_mac", "giant_tail")):
+                measure("Evaluate, %s, %s fused" % (name, kernel), B, lambda f: lev.Evaluate(ct, lt, out, fused={k: f and k == kernel for k in lev.FUSED_LINTRANS}), kernel)
+            measure("Evaluate, %s, every kernel fused" % name, B, lambda f: lev.Evaluate(ct, lt, out, fused=f), "all")
+    defaults = {k: bool(all(e["fused_default"] for e in results if e["kernel"] == k)) for k in lt_.Evaluator.FUSED_LINTRANS}
+    from bench import csrc_tree_hash
+    res = {"device": torch.cuda.get_device_name(0), "csrc_tree": csrc_tree_hash(), "shape": {"N": N, "limbs_Q": LQ, "limbs_P": LP, "batches": [1, 8], "slots": slots},
+           "method": "%d alternating windows of %d calls each (30 to 50 for a kernel alone), device events, 2 warm-up calls per window; clocks left to the "
+                     "driver's default governor" % (rounds, reps),
+           "fused_lintrans_default": defaults, "results": results}
+    with open(out_path, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(res, indent=1))
+    cev.close()
+    rq.close(); rp.close()
+
+
+if sys.argv[1:2] == ["lintrans"]:
+    lintrans_group(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "lintrans.json"))
+    sys.exit(0)
 
 
 if sys.argv[1:2] == ["polynomial"]:
