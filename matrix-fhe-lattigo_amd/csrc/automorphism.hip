@@ -8,8 +8,6 @@
 #include <hip/hip_runtime.h>
 #include "engine_internal.hpp"
 
-RH_DEV u32 brevn(u32 x, int bits) { return bits ? (__brev(x) >> (32 - bits)) : 0u; }
-
 // out[row][j] (=|+=) in[row][index(j)], index(j) = bitrev(((gen*(2*bitrev(j)+1) mod NthRoot) - 1)/2), bit reversals over
 // lg = log2(NthRoot) - 1 bits (:26-33): NthRoot = 2N (standard, lg = logN) or 4N (conjugate invariant, lg = logN + 1)
 __global__ void __launch_bounds__(256)
@@ -17,9 +15,9 @@ automorphism_ntt_kernel(const u64* in, u64* out, int logN, int lg, u32 gen, int 
   const u32 N = 1u << logN, mask = (2u << lg) - 1;
   const size_t base = (size_t)blockIdx.x << logN;
   for (u32 j = blockIdx.y * blockDim.x + threadIdx.x; j < N; j += gridDim.y * blockDim.x) {
-    const u32 t1 = 2 * brevn(j, lg) + 1;
+    const u32 t1 = 2 * rh_brev(j, lg) + 1;
     const u32 t2 = (((gen * t1) & mask) - 1) >> 1;
-    const u64 v = in[base + brevn(t2, lg)];
+    const u64 v = in[base + rh_brev(t2, lg)];
     out[base + j] = add_lazy ? out[base + j] + v : v;
   }
 }

@@ -314,25 +314,6 @@ extern "C" int rh_ckks_scale_then_add(rh_ring* r, int level, const uint64_t* a0,
   return rh_launch_ok("ckks_scale_then_add_kernel");
 }
 
-// Page-locked staging of the table on its way to the device: a few slots per calling thread, each reused once the copy that read it has run
-// (its event).  Nothing of a call lives in the ring handle; the slots stay with their thread.
-struct LcStage { u64* h = nullptr; size_t words = 0; hipEvent_t done = nullptr; };
-static int lc_stage(size_t words, LcStage** out) {
-  static thread_local LcStage slots[4];
-  static thread_local unsigned next = 0;
-  LcStage& s = slots[next++ % 4];
-  if (s.done && hipEventSynchronize(s.done) != hipSuccess) return rh_fail(RH_ERR_DEVICE, "rh_ckks_linear_combination: waiting for an earlier table copy failed");
-  if (!s.done && hipEventCreateWithFlags(&s.done, hipEventDisableTiming) != hipSuccess) return rh_fail(RH_ERR_DEVICE, "rh_ckks_linear_combination: hipEventCreate failed");
-  if (s.words < words) {
-    if (s.h) (void)hipHostFree(s.h);
-    s.h = nullptr; s.words = 0;
-    if (hipHostMalloc((void**)&s.h, words * 8, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return rh_fail(RH_ERR_NOMEM, "rh_ckks_linear_combination: hipHostMalloc(%zu words) failed", words); }
-    s.words = words;
-  }
-  *out = &s;
-  return RH_OK;
-}
-
 extern "C" size_t rh_ckks_linear_combination_table_words(int nterms, int level) { return nterms < 0 || level < 0 ? 0 : lc_table_words(nterms, level + 1); }
 extern "C" int rh_ckks_linear_combination_chunk(void) { return LC_CHUNK; }
 extern "C" int rh_ckks_linear_combination_width(void) { return LC_WIDTH; }
@@ -348,10 +329,9 @@ extern "C" int rh_ckks_linear_combination(rh_ring* r, int level, int nterms, con
   const int L = level + 1, nc = out2 ? 3 : out1 ? 2 : 1;
   const size_t words = lc_table_words(nterms, L), N = (size_t)r->N;
   if (table_words < words) return rh_fail(RH_ERR_ARG, "%s: the table holds %zu words, %d terms at level %d need %zu", who, table_words, nterms, level, words);
-  for (int i = 0; i < L; ++i)
-    if (r->moduli[i] >> LC_MODULUS_BITS) return rh_fail(RH_ERR_ARG, "%s: modulus %d is not below 2^%d, the bound the %d-term chunks are sized for", who, i, LC_MODULUS_BITS, LC_CHUNK);
+  if (int rc = rh_moduli_below(r, L, LC_MODULUS_BITS, LC_CHUNK, who)) return rc;
   u64* outs[3] = {out0, out1, out2};
-  IsBlock written[4], read[3];
+  RhBlock written[4], read[3];
   for (int j = 0; j < nc; ++j) written[j] = {outs[j], (size_t)npoly * L * N};
   written[nc] = {table, words};
   for (int k = 0; k < nterms; ++k) {
@@ -360,14 +340,14 @@ extern "C" int rh_ckks_linear_combination(rh_ring* r, int level, int nterms, con
       if (!x[3 * k + j]) return rh_fail(RH_ERR_ARG, "%s: term %d has no component %d", who, k, j);
       read[j] = {x[3 * k + j], (size_t)npoly * (size_t)x_rows[k] * N};
     }
-    if (int rc = is_blocks(written, nc + 1, read, nc, who, "an output (or the table) overlaps a term: the sum is not computed in place")) return rc;
+    if (int rc = rh_blocks_ok(written, nc + 1, read, nc, who, "an output (or the table) overlaps a term: the sum is not computed in place")) return rc;
   }
-  if (int rc = is_blocks(written, nc, written + nc, 1, who, "an output overlaps the table")) return rc;
+  if (int rc = rh_blocks_ok(written, nc, written + nc, 1, who, "an output overlaps the table")) return rc;
   const unsigned rows = (unsigned)npoly * (unsigned)L;
   const RhStreamGrid g = rh_stream_begin(r, rows);
   hipStream_t st = rh_stream(r);
-  LcStage* stage;
-  if (int rc = lc_stage(words, &stage)) return rc;
+  RhStage* stage;
+  if (int rc = rh_stage_slot(words, &stage, who)) return rc;
   u64* t = stage->h;
   RhScalars s;
   if (int rc = rh_pack_scalars(r, level, c0, c1, false, &s, who, "constant")) return rc;   // Add of a scalar (:82-101): the residues as they are
@@ -379,8 +359,7 @@ extern "C" int rh_ckks_linear_combination(rh_ring* r, int level, int nterms, con
     if (int rc = rh_pack_scalars(r, level, s0 + (size_t)k * L, s1 + (size_t)k * L, true, &s, who)) return rc;   // MulDoubleRNSScalarThenAdd: MForm(scalar)
     for (int i = 0; i < L; ++i) { e[LC_TERM_HEAD + i] = s.a[i]; e[LC_TERM_HEAD + L + i] = s.b[i]; }
   }
-  if (hipMemcpyAsync(table, t, words * 8, hipMemcpyHostToDevice, st) != hipSuccess || hipEventRecord(stage->done, st) != hipSuccess)
-    return rh_fail(RH_ERR_DEVICE, "%s: table copy failed", who);
+  if (int rc = rh_stage_upload(stage, table, words, st, who)) return rc;
   if (rows == 0) return RH_OK;
   const CkksComps p{{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, {out0, out1, out2}};
   const unsigned n = (unsigned)r->N;

@@ -21,8 +21,6 @@ __device__ __forceinline__ EncCplx enc_cmul(EncCplx x, EncCplx w) {
   return r;
 }
 
-__device__ __forceinline__ unsigned enc_bitrev(unsigned x, int bits) { return bits ? __brev(x) >> (32 - bits) : 0u; }
-
 // root of the stage with len = 1 << loglen for the butterfly whose upper element sits at offset j < len/2 of its block
 // IFFT: roots[(lenq - (rotGroup[j] & mask)) << logGap]    FFT: roots[(rotGroup[j] & mask) << logGap]      (lenq = 4 len, mask = lenq - 1)
 template <bool INVERSE>
@@ -88,7 +86,7 @@ ckks_fft_lds_kernel(const EncCplx* src, EncCplx* dst, int logn, int logb, int lo
   const size_t vbase = (size_t)blockIdx.y << logn;
   const unsigned b0 = blockIdx.x << logb;
   for (unsigned i = threadIdx.x; i < nb; i += 256) {
-    const EncCplx x = src[vbase + (INVERSE ? b0 + i : enc_bitrev(b0 + i, logn))];
+    const EncCplx x = src[vbase + (INVERSE ? b0 + i : rh_brev(b0 + i, logn))];
     sre[i] = x.re; sim[i] = x.im;
   }
   __syncthreads();
@@ -134,7 +132,7 @@ ckks_fft_lds_kernel(const EncCplx* src, EncCplx* dst, int logn, int logb, int lo
   const double n = (double)(1u << logn);
   for (unsigned i = threadIdx.x; i < nb; i += 256) {
     EncCplx x{sre[i], sim[i]};
-    if (INVERSE) dst[vbase + enc_bitrev(b0 + i, logn)] = enc_div_n(x, n);
+    if (INVERSE) dst[vbase + rh_brev(b0 + i, logn)] = enc_div_n(x, n);
     else dst[vbase + b0 + i] = x;
   }
 }

@@ -326,6 +326,26 @@ unsigned rh_stream_chunks(const rh_ring* r) {
 RhStreamGrid rh_stream_grid(const rh_ring* r, unsigned rows) {
   return {dim3(rows, rh_stream_chunks(r)), rh_nt_policy(r->nt_streams, (size_t)rows * (size_t)r->N * 8, (size_t)512 << 20) ? 1 : 0};
 }
+int rh_stage_slot(size_t words, RhStage** out, const char* who) {
+  static thread_local RhStage slots[4];
+  static thread_local unsigned next = 0;
+  RhStage& s = slots[next++ % 4];
+  if (s.done && hipEventSynchronize(s.done) != hipSuccess) return rh_fail(RH_ERR_DEVICE, "%s: waiting for an earlier table copy failed", who);
+  if (!s.done && hipEventCreateWithFlags(&s.done, hipEventDisableTiming) != hipSuccess) return rh_fail(RH_ERR_DEVICE, "%s: hipEventCreate failed", who);
+  if (s.words < words) {
+    if (s.h) (void)hipHostFree(s.h);
+    s.h = nullptr; s.words = 0;
+    if (hipHostMalloc((void**)&s.h, words * 8, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return rh_fail(RH_ERR_NOMEM, "%s: hipHostMalloc(%zu words) failed", who, words); }
+    s.words = words;
+  }
+  *out = &s;
+  return RH_OK;
+}
+int rh_stage_upload(RhStage* s, u64* table_dev, size_t words, hipStream_t st, const char* who) {
+  if (hipMemcpyAsync(table_dev, s->h, words * 8, hipMemcpyHostToDevice, st) != hipSuccess || hipEventRecord(s->done, st) != hipSuccess)
+    return rh_fail(RH_ERR_DEVICE, "%s: table copy failed", who);
+  return RH_OK;
+}
 int rh_scheme_args(const rh_ring* r, int level, int npoly, unsigned kinds, int n_multiple, const char* who) {
   if (!r) return rh_fail(RH_ERR_ARG, "%s: null ring handle", who);
   if (!(kinds >> r->kind & 1))

@@ -85,19 +85,38 @@ inline RhStreamGrid rh_stream_begin(const rh_ring* r, unsigned rows) {   // ... 
   return rh_stream_grid(r, rows);
 }
 // Blocks [p, p + words) as byte ranges: no written block may overlap a permuted (gathered) one, and every block moves as 16-byte pairs
-struct IsBlock { const void* p; size_t words; };
-inline bool is_overlap(const IsBlock& a, const IsBlock& b) {
+struct RhBlock { const void* p; size_t words; };
+inline bool rh_overlap(const RhBlock& a, const RhBlock& b) {
   const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
   return a0 < b0 + b.words * 8 && b0 < a0 + a.words * 8;
 }
-inline int is_blocks(const IsBlock* written, int nw, const IsBlock* read, int nr, const char* who, const char* text) {
+inline int rh_blocks_ok(const RhBlock* written, int nw, const RhBlock* read, int nr, const char* who, const char* text) {
   for (int i = 0; i < nw; ++i) {
     if ((uintptr_t)written[i].p & 15) return rh_fail(RH_ERR_ARG, "%s: every block must be 16-byte aligned", who);
-    for (int j = 0; j < nr; ++j) if (is_overlap(written[i], read[j])) return rh_fail(RH_ERR_ARG, "%s: %s", who, text);
+    for (int j = 0; j < nr; ++j) if (rh_overlap(written[i], read[j])) return rh_fail(RH_ERR_ARG, "%s: %s", who, text);
   }
   for (int j = 0; j < nr; ++j) if ((uintptr_t)read[j].p & 15) return rh_fail(RH_ERR_ARG, "%s: every block must be 16-byte aligned", who);
   return RH_OK;
 }
+// ... and no two written blocks may overlap each other
+inline int rh_blocks_disjoint(const RhBlock* written, int nw, const char* who, const char* text) {
+  for (int i = 0; i < nw; ++i) for (int j = i + 1; j < nw; ++j)
+    if (rh_overlap(written[i], written[j])) return rh_fail(RH_ERR_ARG, "%s: %s", who, text);
+  return RH_OK;
+}
+// Limbs 0 .. L-1 of a ring below 2^bits, the bound the `chunk`-term 128-bit sums of lc_reduce.hip.hpp are sized for (LC_MODULUS_BITS, LC_CHUNK);
+// `of`: " of Q" or " of P" where the entry has both rings
+inline int rh_moduli_below(const rh_ring* r, int L, int bits, int chunk, const char* who, const char* of = "") {
+  for (int i = 0; i < L; ++i)
+    if (r->moduli[i] >> bits) return rh_fail(RH_ERR_ARG, "%s: modulus %d%s is not below 2^%d, the bound the %d-term chunks are sized for", who, i, of, bits, chunk);
+  return RH_OK;
+}
+// Page-locked staging of a host-built table on its way to the device (rh_ckks_linear_combination, rh_rlwe_diag_mac_qp): ONE ring of four slots
+// per calling thread, each reused once the copy that read it has run (its event).  Nothing of a call lives in a handle; the slots stay with
+// their thread.
+struct RhStage { u64* h = nullptr; size_t words = 0; hipEvent_t done = nullptr; };
+int rh_stage_slot(size_t words, RhStage** out, const char* who);                                  // the next slot, grown to at least `words` words
+int rh_stage_upload(RhStage* s, u64* table_dev, size_t words, hipStream_t st, const char* who);   // h[0 .. words) -> table_dev on st; records the slot's event
 // Argument checks of the scheme-level entry points (bgv.hip, ckks.hip): kinds: a mask of 1 << RH_RING_* admitted (the refusal names the scheme
 // the mask belongs to); N a multiple of n_multiple
 int rh_scheme_args(const rh_ring* r, int level, int npoly, unsigned kinds, int n_multiple, const char* who);

@@ -18,24 +18,19 @@ extern "C" int rh_rlwe_rotate_accumulate_qp(rh_bext* be, int levelQ, int levelP,
                                             const uint64_t* tmpQ1, const uint64_t* tmpP0, const uint64_t* tmpP1, uint64_t* accQ0, uint64_t* accQ1,
                                             uint64_t* accP0, uint64_t* accP1, int npoly, int first) {
   const char* who = "rotate_accumulate_qp";
-  rh_ring *RQ, *RP;
-  if (int rc = is_rings(be, levelQ, levelP, who, &RQ, &RP)) return rc;
-  if (!ct0 || !tmpQ0 || !tmpQ1 || !tmpP0 || !tmpP1 || !accQ0 || !accQ1 || !accP0 || !accP1) return rh_fail(RH_ERR_ARG, "%s: null argument", who);
-  if (npoly < 0) return rh_fail(RH_ERR_ARG, "%s: npoly < 0", who);
-  {
-    const size_t wq = (size_t)npoly * (levelQ + 1) * RQ->N, wp = (size_t)npoly * (levelP + 1) * RQ->N;
-    const IsBlock wr[4] = {{accQ0, wq}, {accQ1, wq}, {accP0, wp}, {accP1, wp}};
-    const IsBlock rd[5] = {{tmpQ0, wq}, {tmpQ1, wq}, {tmpP0, wp}, {tmpP1, wp}, {ct0, wq}};
-    if (int rc = is_blocks(wr, 4, rd, 5, who, "the accumulator cannot overlap the permuted operands")) return rc;
-  }
-  u32 g; if (int rc = is_gen(RQ, gen, who, &g)) return rc;
+  rh_ring *RQ = nullptr, *RP = nullptr; u32 g = 0;
+  const uint64_t* tmp[4] = {tmpQ0, tmpQ1, tmpP0, tmpP1};
+  uint64_t* acc[4] = {accQ0, accQ1, accP0, accP1};
+  const QpExtra extra[1] = {{ct0, QP_BATCH_Q}};
+  if (int rc = qp_accumulate_args(be, levelQ, levelP, gen, who, tmp, extra, 1, acc, npoly, "the accumulator cannot overlap the permuted operands", &RQ, &RP, &g)) return rc;
   if (!npoly) return RH_OK;
   RhBextGuard guard(be);
   const int LQ = levelQ + 1, LP = levelP + 1;
   const RhPmodQ pq = is_pmodq(RQ, RP, LQ, LP);
   const RhStreamGrid sg = rh_stream_begin(RQ, 2u * (unsigned)npoly * (unsigned)(LQ + LP));
-  const InnerSumQP a{{accQ0, accQ1}, {accP0, accP1}, {tmpQ0, tmpQ1}, {tmpP0, tmpP1}, ct0};
-  rotate_accumulate_qp_kernel<<<sg.grid, 256, 0, rh_stream(RQ)>>>(a, RQ->logN, g, RQ->d_consts, RP->d_consts, LQ, LP, npoly, pq, first ? 1 : 0, sg.nt);
+  const RhQP a{{accQ0, accQ1}, {accP0, accP1}};
+  const RhQPc t{{tmpQ0, tmpQ1}, {tmpP0, tmpP1}};
+  rotate_accumulate_qp_kernel<<<sg.grid, 256, 0, rh_stream(RQ)>>>(a, t, ct0, RQ->logN, g, RQ->d_consts, RP->d_consts, LQ, LP, npoly, pq, first ? 1 : 0, sg.nt);
   return rh_launch_ok("rotate_accumulate_qp_kernel");
 }
 
@@ -44,14 +39,11 @@ extern "C" int rh_rlwe_rotate_add_q(rh_ring* r, int level, uint64_t gen, const u
                                     int npoly) {
   const char* who = "rotate_add_q";
   if (!r || !tmp0 || !tmp1 || !ct0 || !ct1) return rh_fail(RH_ERR_ARG, "%s: null argument", who);
-  if (r->kind != RH_RING_STANDARD) return rh_fail(RH_ERR_UNSUPPORTED, "%s: standard rings only (3N and conjugate-invariant rings are not supported)", who);
-  if (level < 0 || level >= r->L) return rh_fail(RH_ERR_ARG, "%s: level %d out of range [0,%d)", who, level, r->L);
-  if (r->N < 4) return rh_fail(RH_ERR_ARG, "%s: N < 4", who);
-  if (npoly < 0) return rh_fail(RH_ERR_ARG, "%s: npoly < 0", who);
+  if (int rc = rh_ring_ok(r, level, npoly, who, "npoly < 0")) return rc;
   {
     const size_t w = (size_t)npoly * (level + 1) * r->N;
-    const IsBlock wr[2] = {{ct0, w}, {ct1, w}}, rd[2] = {{tmp0, w}, {tmp1, w}};
-    if (int rc = is_blocks(wr, 2, rd, 2, who, "the permuted operand cannot be the ciphertext it is added to")) return rc;
+    const RhBlock wr[2] = {{ct0, w}, {ct1, w}}, rd[2] = {{tmp0, w}, {tmp1, w}};
+    if (int rc = rh_blocks_ok(wr, 2, rd, 2, who, "the permuted operand cannot be the ciphertext it is added to")) return rc;
   }
   u32 g; if (int rc = is_gen(r, gen, who, &g)) return rc;
   if (!npoly) return RH_OK;

@@ -9,39 +9,29 @@
 #pragma once
 #include "paired_gather.hip.hpp"
 
-struct InnerSumQP {
-  u64* accQ[2]; u64* accP[2];                   // accumulators modulo Q (LQ limbs per poly) and modulo P (LP limbs per poly), dense
-  const u64* tmpQ[2]; const u64* tmpP[2];       // the lazy hoisted product, same shapes
-  const u64* ct0;                               // ctIn[0], LQ limbs per poly
-};
-
 // The tail of AutomorphismHoistedLazy (core/rlwe/evaluator_automorphism.go:107-160, NTT-domain ctQP) followed by ringQP.Add (inner_sum.go:245-246):
 //   acc_c[j] = [first ? 0 : acc_c[j]] + tmp_c[index(j)] + [c == 0 and the row is a Q row] (P mod q_i) * ct0[index(j)]      (canonical)
 // Every intermediate of the reference's sequence is a canonical residue (MulScalarBigintThenAdd and Add end in CRed), so the value is the reference's.
-// grid: (2 * npoly * (LQ + LP), chunks): component, poly, then the LQ rows of Q and the LP rows of P.
+// tmp: the lazy hoisted product; ct0: ctIn[0], LQ limbs per poly.   grid: (2 * npoly * (LQ + LP), chunks): StreamComp, then StreamRowQP
 __global__ void __launch_bounds__(256)
-rotate_accumulate_qp_kernel(InnerSumQP a, int logN, u32 gen, const LimbConsts* __restrict__ constsQ, const LimbConsts* __restrict__ constsP,
-                            int LQ, int LP, int npoly, RhPmodQ pq, int first, int nt) {
-  const u32 LT_ = (u32)(LQ + LP), per = (u32)npoly * LT_;
-  const u32 comp = blockIdx.x / per, rem = blockIdx.x % per, poly = rem / LT_, l = rem % LT_;
-  const bool inQ = l < (u32)LQ;
-  const LimbConsts c = inQ ? constsQ[l] : constsP[l - LQ];
-  const size_t ro = (inQ ? (size_t)poly * LQ + l : (size_t)poly * LP + (l - LQ)) << logN;
-  u64* acc = (inQ ? a.accQ[comp] : a.accP[comp]) + ro;
-  const u64* tmp = (inQ ? a.tmpQ[comp] : a.tmpP[comp]) + ro;
-  const bool with_ct0 = inQ && comp == 0;
-  const u64* ct0 = a.ct0 + ro;                  // read only when with_ct0
-  const u64 s = inQ ? pq.s[l] : 0;
+rotate_accumulate_qp_kernel(RhQP acc, RhQPc tmp, const u64* ct0, int logN, u32 gen, const LimbConsts* __restrict__ constsQ,
+                            const LimbConsts* __restrict__ constsP, int LQ, int LP, int npoly, RhPmodQ pq, int first, int nt) {
+  const StreamComp sc((u32)npoly * (u32)(LQ + LP));
+  const StreamRowQP r(sc.row, constsQ, constsP, LQ, LP, logN);
+  u64* a = r.of(acc, sc.comp);
+  const u64* x = r.of(tmp, sc.comp);
+  const bool with_ct0 = r.inQ && sc.comp == 0;
+  const u64* c0 = ct0 + r.ro;                   // read only when with_ct0
+  const u64 s = r.inQ ? pq.s[r.l] : 0;
+  const u64 q = r.c.q, qinv = r.c.qinv;
   RH_FOR_EACH_PAIR(i, 0, 1u << (logN - 1)) {
-    const u32 idx = is_index_even(i, logN, gen);
-    const ulonglong2 t = is_gather2(tmp, idx);
-    ulonglong2 v = first ? make_ulonglong2(0, 0) : rh_ld2(acc + 2 * (size_t)i, nt);
-    v.x = cred(v.x + t.x, c.q); v.y = cred(v.y + t.y, c.q);
+    const u32 idx = rh_galois_index_even(i, logN, gen);
+    ulonglong2 t = rh_gather2(x, idx);
     if (with_ct0) {
-      const ulonglong2 x = is_gather2(ct0, idx);
-      v.x = cred(v.x + mred(x.x, s, c.q, c.qinv), c.q); v.y = cred(v.y + mred(x.y, s, c.q, c.qinv), c.q);
+      const ulonglong2 u = rh_gather2(c0, idx);
+      t.x = cred(t.x + mred(u.x, s, q, qinv), q); t.y = cred(t.y + mred(u.y, s, q, qinv), q);
     }
-    rh_st2(acc + 2 * (size_t)i, v, nt);
+    rh_accumulate2(a, i, t, q, first, nt);
   }
 }
 
@@ -49,14 +39,13 @@ rotate_accumulate_qp_kernel(InnerSumQP a, int logN, u32 gen, const LimbConsts* _
 //   ct_c[j] = ct_c[j] + tmp_c[index(j)] mod q, in place on ct; tmp is another buffer.   grid: (2 * npoly * L, chunks)
 __global__ void __launch_bounds__(256)
 rotate_add_q_kernel(u64* ct0, u64* ct1, const u64* tmp0, const u64* tmp1, int logN, u32 gen, const LimbConsts* __restrict__ consts, int L, int npoly, int nt) {
-  const u32 per = (u32)npoly * (u32)L;
-  const u32 comp = blockIdx.x / per, rem = blockIdx.x % per;
-  const u64 q = consts[rem % (u32)L].q;
-  const size_t ro = (size_t)rem << logN;
-  u64* ct = (comp ? ct1 : ct0) + ro;
-  const u64* tmp = (comp ? tmp1 : tmp0) + ro;
+  const StreamComp sc((u32)npoly * (u32)L);
+  const u64 q = consts[sc.row % (u32)L].q;
+  const size_t ro = (size_t)sc.row << logN;
+  u64* ct = (sc.comp ? ct1 : ct0) + ro;
+  const u64* tmp = (sc.comp ? tmp1 : tmp0) + ro;
   RH_FOR_EACH_PAIR(i, 0, 1u << (logN - 1)) {
-    const ulonglong2 t = is_gather2(tmp, is_index_even(i, logN, gen));
+    const ulonglong2 t = rh_gather2(tmp, rh_galois_index_even(i, logN, gen));
     ulonglong2 v = rh_ld2(ct + 2 * (size_t)i, nt);
     v.x = cred(v.x + t.x, q); v.y = cred(v.y + t.y, q);
     rh_st2(ct + 2 * (size_t)i, v, nt);

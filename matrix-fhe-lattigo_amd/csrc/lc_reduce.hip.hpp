@@ -12,7 +12,7 @@
 
 #define LC_CHUNK 56            // terms summed between two reductions
 #define LC_WIDTH 4             // terms whose loads are in flight together
-#define LC_MODULUS_BITS 61     // the bound holds for q < 2^61 (checked per call)
+#define LC_MODULUS_BITS 61     // the bound holds for q < 2^61 (checked per call: rh_moduli_below)
 static_assert(LC_CHUNK <= 64 && (unsigned __int128)(LC_CHUNK + 8) << (2 * LC_MODULUS_BITS - 64) <= (unsigned __int128)1 << 64, "LC_CHUNK terms of q < 2^61 pass 64 bits after the Montgomery step");
 static_assert(LC_CHUNK % LC_WIDTH == 0, "a chunk is a whole number of load groups");
 

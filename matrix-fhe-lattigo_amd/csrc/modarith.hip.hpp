@@ -28,6 +28,9 @@ RH_DEV u64 mulhi64(u64 a, u64 b) { return __umul64hi(a, b); }
 RH_DEV u32 uni32(u32 x) { return (u32)__builtin_amdgcn_readfirstlane((int)x); }
 RH_DEV u64 uni64(u64 x) { return ((u64)uni32((u32)(x >> 32)) << 32) | uni32((u32)x); }
 
+// the low `bits` bits of x reversed (bits <= 32; 0 for bits = 0, where the shift by 32 would be undefined)
+RH_DEV u32 rh_brev(u32 x, int bits) { return bits ? __brev(x) >> (32 - bits) : 0u; }
+
 // ---- reference primitives (ring/modular_reduction.go) --------------------------------------------------------
 
 RH_DEV u64 cred(u64 a, u64 q) { return a >= q ? a - q : a; }                       // :200-205

@@ -117,7 +117,6 @@ ntt3n_split_inv(const u64* in, u64* out, int N, const Limb3N* __restrict__ l3, c
   }
 }
 
-RH_DEV u32 brev(u32 x, int bits) { return bits ? (__brev(x) >> (32 - bits)) : 0u; }
 // forward permutation: out[nb*bitrev(j) + rank[c]] = in[c*n2 + j]; thread per OUTPUT element (contiguous writes)
 __global__ void __launch_bounds__(256)
 ntt3n_perm_fwd(const u64* in, u64* out, int N, int nb, int log_n2, const int* __restrict__ block_of_rank,
@@ -127,7 +126,7 @@ ntt3n_perm_fwd(const u64* in, u64* out, int N, int nb, int log_n2, const int* __
   for (int o = blockIdx.y * blockDim.x + threadIdx.x; o < N; o += gridDim.y * blockDim.x) {
     const int jb = o / nb, rk = o - jb * nb;
     const int c = block_of_rank[rk];
-    u64 v = in[base + ((size_t)c << log_n2) + brev((u32)jb, log_n2)];
+    u64 v = in[base + ((size_t)c << log_n2) + rh_brev((u32)jb, log_n2)];
     out[base + o] = canon ? canon4(v, q) : v;     // canon: only when there is no radix-2 part (a == 1), values < 4q
   }
 }
@@ -138,7 +137,7 @@ ntt3n_perm_inv(const u64* in, u64* out, int N, int nb, int log_n2, const int* __
   for (int o = blockIdx.y * blockDim.x + threadIdx.x; o < N; o += gridDim.y * blockDim.x) {
     const int jb = o / nb, rk = o - jb * nb;
     const int c = block_of_rank[rk];
-    out[base + ((size_t)c << log_n2) + brev((u32)jb, log_n2)] = in[base + o];
+    out[base + ((size_t)c << log_n2) + rh_brev((u32)jb, log_n2)] = in[base + o];
   }
 }
 

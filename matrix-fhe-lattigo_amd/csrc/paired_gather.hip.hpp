@@ -3,15 +3,15 @@
 #pragma once
 #include "stream_kernels.hip.hpp"
 
-RH_DEV u32 is_brev(u32 x, int bits) { return __brev(x) >> (32 - bits); }            // bits >= 1
-// index(2 i) of the automorphism `gen` on a standard ring of degree 2^logN >= 2
-RH_DEV u32 is_index_even(u32 i, int logN, u32 gen) {
+// index(2 i) of the automorphism `gen` on a standard ring of degree 2^logN >= 4 (every entry refuses N < 4)
+RH_DEV u32 rh_galois_index_even(u32 i, int logN, u32 gen) {
+  __builtin_assume(logN >= 2);
   const u32 mask = (2u << logN) - 1;
-  const u32 t1 = 2 * is_brev(2 * i, logN) + 1;
-  return is_brev((((gen * t1) & mask) - 1) >> 1, logN);
+  const u32 t1 = 2 * rh_brev(2 * i, logN) + 1;
+  return rh_brev((((gen * t1) & mask) - 1) >> 1, logN);
 }
 // the words index(2 i), index(2 i) ^ 1 of the row at `row`
-RH_DEV ulonglong2 is_gather2(const u64* row, u32 idx) {
+RH_DEV ulonglong2 rh_gather2(const u64* row, u32 idx) {
   const ulonglong2 w = *reinterpret_cast<const ulonglong2*>(row + (idx & ~1u));
   return (idx & 1) ? make_ulonglong2(w.y, w.x) : w;
 }

@@ -10,24 +10,10 @@
 #include "engine_internal.hpp"
 #include "hostmath.hpp"
 #include "ring_packing_kernels.hip.hpp"
+#include "qp_rows_host.hpp"
 
 static_assert(sizeof(RpEntry) == 3 * sizeof(int32_t), "the plan of a Pack level is a table of int32 triples");
 
-static int rp_ring(const rh_ring* r, int level, int count, const char* who) {
-  if (!r) return rh_fail(RH_ERR_ARG, "%s: null ring handle", who);
-  if (r->kind != RH_RING_STANDARD) return rh_fail(RH_ERR_UNSUPPORTED, "%s: standard rings only (3N and conjugate-invariant rings are not supported)", who);
-  if (level < 0 || level >= r->L) return rh_fail(RH_ERR_ARG, "%s: level %d out of range [0,%d)", who, level, r->L);
-  if (level + 1 > RH_MAX_LIMBS) return rh_fail(RH_ERR_ARG, "%s: at most %d limbs", who, RH_MAX_LIMBS);
-  if (r->N < 4) return rh_fail(RH_ERR_ARG, "%s: N < 4", who);
-  if (count < 0) return rh_fail(RH_ERR_ARG, "%s: negative count", who);
-  if ((size_t)count * 2 * (size_t)(level + 1) > 0x7fffffffu) return rh_fail(RH_ERR_ARG, "%s: too many rows for one launch", who);
-  return RH_OK;
-}
-static int rp_gen(const rh_ring* r, uint64_t gen, const char* who, u32* out) {
-  if ((gen & 1) == 0) return rh_fail(RH_ERR_ARG, "%s: the Galois element must be odd", who);
-  *out = (u32)(gen & (2 * (u64)r->N - 1));
-  return RH_OK;
-}
 // The plan of a Pack level as the host holds it: every entry in range, and no slot written twice (a written slot is `a` of AB, `b` of B, and the
 // slot the finishing kernel adds to: `a` of A and AB, `b` of B) or read by another entry
 static int rp_table(const int32_t* table_host, int K, int nslots, const char* who) {
@@ -51,15 +37,15 @@ static int rp_table(const int32_t* table_host, int K, int nslots, const char* wh
 extern "C" int rh_rlwe_expand_step(rh_ring* r, int level, uint64_t gen, const uint64_t* tmp0, const uint64_t* tmp1, uint64_t* ct0, uint64_t* ct1,
                                    const uint64_t* xpow, int cnt) {
   const char* who = "expand_step";
-  if (int rc = rp_ring(r, level, cnt, who)) return rc;
+  if (int rc = rh_ring_ok(r, level, cnt, who)) return rc;
   if (!tmp0 || !tmp1 || !ct0 || !ct1 || !xpow) return rh_fail(RH_ERR_ARG, "%s: null argument", who);
   const size_t w = (size_t)cnt * (level + 1) * r->N;
   {
-    const IsBlock wr[2] = {{ct0, 2 * w}, {ct1, 2 * w}}, rd[3] = {{tmp0, w}, {tmp1, w}, {xpow, (size_t)(level + 1) * r->N}};
-    if (int rc = is_blocks(wr, 2, rd, 3, who, "the permuted operand and the table cannot overlap the batch")) return rc;
-    if (is_overlap(wr[0], wr[1])) return rh_fail(RH_ERR_ARG, "%s: the two components of the batch overlap", who);
+    const RhBlock wr[2] = {{ct0, 2 * w}, {ct1, 2 * w}}, rd[3] = {{tmp0, w}, {tmp1, w}, {xpow, (size_t)(level + 1) * r->N}};
+    if (int rc = rh_blocks_ok(wr, 2, rd, 3, who, "the permuted operand and the table cannot overlap the batch")) return rc;
+    if (int rc = rh_blocks_disjoint(wr, 2, who, "the two components of the batch overlap")) return rc;
   }
-  u32 g; if (int rc = rp_gen(r, gen, who, &g)) return rc;
+  u32 g; if (int rc = is_gen(r, gen, who, &g)) return rc;
   if (!cnt) return RH_OK;
   const RhStreamGrid sg = rh_stream_begin(r, 2u * (unsigned)cnt * (unsigned)(level + 1));
   expand_step_kernel<<<sg.grid, 256, 0, rh_stream(r)>>>(ct0, ct1, tmp0, tmp1, xpow, r->logN, g, r->d_consts, level + 1, cnt, sg.nt);
@@ -70,15 +56,14 @@ extern "C" int rh_rlwe_expand_step(rh_ring* r, int level, uint64_t gen, const ui
 extern "C" int rh_rlwe_pack_combine(rh_ring* r, int level, uint64_t* ct0, uint64_t* ct1, int nslots, const int32_t* table_dev, const int32_t* table_host,
                                     int K, const uint64_t* xpow, uint64_t* u0, uint64_t* u1) {
   const char* who = "pack_combine";
-  if (int rc = rp_ring(r, level, K, who)) return rc;
+  if (int rc = rh_ring_ok(r, level, K, who)) return rc;
   if (!ct0 || !ct1 || !u0 || !u1 || !xpow || !table_dev || nslots <= 0) return rh_fail(RH_ERR_ARG, "%s: null argument", who);
   if (int rc = rp_table(table_host, K, nslots, who)) return rc;
   const size_t row = (size_t)(level + 1) * r->N;
   {
-    const IsBlock wr[4] = {{ct0, nslots * row}, {ct1, nslots * row}, {u0, K * row}, {u1, K * row}}, rd[1] = {{xpow, row}};
-    if (int rc = is_blocks(wr, 4, rd, 1, who, "the table of powers of X cannot overlap a written block")) return rc;
-    for (int i = 0; i < 4; ++i) for (int j = i + 1; j < 4; ++j)
-      if (is_overlap(wr[i], wr[j])) return rh_fail(RH_ERR_ARG, "%s: the batch and the key-switch operand overlap", who);
+    const RhBlock wr[4] = {{ct0, nslots * row}, {ct1, nslots * row}, {u0, K * row}, {u1, K * row}}, rd[1] = {{xpow, row}};
+    if (int rc = rh_blocks_ok(wr, 4, rd, 1, who, "the table of powers of X cannot overlap a written block")) return rc;
+    if (int rc = rh_blocks_disjoint(wr, 4, who, "the batch and the key-switch operand overlap")) return rc;
   }
   if (!K) return RH_OK;
   const RhStreamGrid sg = rh_stream_begin(r, 2u * (unsigned)K * (unsigned)(level + 1));
@@ -91,16 +76,16 @@ extern "C" int rh_rlwe_pack_combine(rh_ring* r, int level, uint64_t* ct0, uint64
 extern "C" int rh_rlwe_rotate_addsub_q(rh_ring* r, int level, uint64_t gen, const uint64_t* tmp0, const uint64_t* tmp1, uint64_t* ct0, uint64_t* ct1,
                                        int nslots, const int32_t* table_dev, const int32_t* table_host, int K) {
   const char* who = "rotate_addsub_q";
-  if (int rc = rp_ring(r, level, K, who)) return rc;
+  if (int rc = rh_ring_ok(r, level, K, who)) return rc;
   if (!tmp0 || !tmp1 || !ct0 || !ct1 || !table_dev || nslots <= 0) return rh_fail(RH_ERR_ARG, "%s: null argument", who);
   if (int rc = rp_table(table_host, K, nslots, who)) return rc;
   const size_t row = (size_t)(level + 1) * r->N;
   {
-    const IsBlock wr[2] = {{ct0, nslots * row}, {ct1, nslots * row}}, rd[2] = {{tmp0, K * row}, {tmp1, K * row}};
-    if (int rc = is_blocks(wr, 2, rd, 2, who, "the permuted operand cannot overlap the batch it is added to")) return rc;
-    if (is_overlap(wr[0], wr[1])) return rh_fail(RH_ERR_ARG, "%s: the two components of the batch overlap", who);
+    const RhBlock wr[2] = {{ct0, nslots * row}, {ct1, nslots * row}}, rd[2] = {{tmp0, K * row}, {tmp1, K * row}};
+    if (int rc = rh_blocks_ok(wr, 2, rd, 2, who, "the permuted operand cannot overlap the batch it is added to")) return rc;
+    if (int rc = rh_blocks_disjoint(wr, 2, who, "the two components of the batch overlap")) return rc;
   }
-  u32 g; if (int rc = rp_gen(r, gen, who, &g)) return rc;
+  u32 g; if (int rc = is_gen(r, gen, who, &g)) return rc;
   if (!K) return RH_OK;
   const RhStreamGrid sg = rh_stream_begin(r, 2u * (unsigned)K * (unsigned)(level + 1));
   rotate_addsub_q_kernel<<<sg.grid, 256, 0, rh_stream(r)>>>(ct0, ct1, tmp0, tmp1, reinterpret_cast<const RpEntry*>(table_dev), r->logN, g, r->d_consts,
@@ -117,16 +102,15 @@ static int rp_gap(const rh_ring* r, int logGap, const char* who) {
 extern "C" int rh_rlwe_ring_split(rh_ring* r, int level, const uint64_t* in0, const uint64_t* in1, uint64_t* even0, uint64_t* even1, uint64_t* odd0,
                                   uint64_t* odd1, int logGap, int npoly) {
   const char* who = "ring_split";
-  if (int rc = rp_ring(r, level, npoly, who)) return rc;
+  if (int rc = rh_ring_ok(r, level, npoly, who)) return rc;
   if (int rc = rp_gap(r, logGap, who)) return rc;
   if (!in0 || !in1 || !even0 || !even1 || (odd0 == nullptr) != (odd1 == nullptr)) return rh_fail(RH_ERR_ARG, "%s: null argument", who);
   const size_t w = (size_t)npoly * (level + 1) * r->N, ws = w >> logGap;
   {
-    const IsBlock wr[4] = {{even0, ws}, {even1, ws}, {odd0, ws}, {odd1, ws}}, rd[2] = {{in0, w}, {in1, w}};
+    const RhBlock wr[4] = {{even0, ws}, {even1, ws}, {odd0, ws}, {odd1, ws}}, rd[2] = {{in0, w}, {in1, w}};
     const int nw = odd0 ? 4 : 2;
-    if (int rc = is_blocks(wr, nw, rd, 2, who, "an output cannot overlap the input")) return rc;
-    for (int i = 0; i < nw; ++i) for (int j = i + 1; j < nw; ++j)
-      if (is_overlap(wr[i], wr[j])) return rh_fail(RH_ERR_ARG, "%s: two outputs overlap", who);
+    if (int rc = rh_blocks_ok(wr, nw, rd, 2, who, "an output cannot overlap the input")) return rc;
+    if (int rc = rh_blocks_disjoint(wr, nw, who, "two outputs overlap")) return rc;
   }
   if (!npoly) return RH_OK;
   const RhStreamGrid sg = rh_stream_begin(r, 2u * (unsigned)npoly * (unsigned)(level + 1));
@@ -138,16 +122,16 @@ extern "C" int rh_rlwe_ring_split(rh_ring* r, int level, const uint64_t* in0, co
 extern "C" int rh_rlwe_ring_merge(rh_ring* r, int level, const uint64_t* even0, const uint64_t* even1, const uint64_t* odd0, const uint64_t* odd1,
                                   const uint64_t* xpow, uint64_t* out0, uint64_t* out1, int logGap, int npoly) {
   const char* who = "ring_merge";
-  if (int rc = rp_ring(r, level, npoly, who)) return rc;
+  if (int rc = rh_ring_ok(r, level, npoly, who)) return rc;
   if (int rc = rp_gap(r, logGap, who)) return rc;
   if (!even0 || !even1 || !out0 || !out1 || (odd0 == nullptr) != (odd1 == nullptr)) return rh_fail(RH_ERR_ARG, "%s: null argument", who);
   if (odd0 && !xpow) return rh_fail(RH_ERR_ARG, "%s: an odd operand needs the table of X", who);
   const size_t w = (size_t)npoly * (level + 1) * r->N, ws = w >> logGap;
   {
-    const IsBlock wr[2] = {{out0, w}, {out1, w}};
-    const IsBlock rd[5] = {{even0, ws}, {even1, ws}, {odd0, ws}, {odd1, ws}, {xpow, (size_t)(level + 1) * r->N}};
-    if (int rc = is_blocks(wr, 2, rd, odd0 ? 5 : 2, who, "the output cannot overlap an input")) return rc;
-    if (is_overlap(wr[0], wr[1])) return rh_fail(RH_ERR_ARG, "%s: the two outputs overlap", who);
+    const RhBlock wr[2] = {{out0, w}, {out1, w}};
+    const RhBlock rd[5] = {{even0, ws}, {even1, ws}, {odd0, ws}, {odd1, ws}, {xpow, (size_t)(level + 1) * r->N}};
+    if (int rc = rh_blocks_ok(wr, 2, rd, odd0 ? 5 : 2, who, "the output cannot overlap an input")) return rc;
+    if (int rc = rh_blocks_disjoint(wr, 2, who, "the two outputs overlap")) return rc;
   }
   if (!npoly) return RH_OK;
   const RhStreamGrid sg = rh_stream_begin(r, 2u * (unsigned)npoly * (unsigned)(level + 1));
@@ -170,7 +154,7 @@ extern "C" int rh_rlwe_expand(rh_bext* be, int levelQ, int levelP, uint64_t* ct0
   if (logGap < 0 || logGap > logN) return rh_fail(RH_ERR_ARG, "%s: need 0 <= logGap <= logN", who);
   const size_t nout = (size_t)nin << (logN - logGap);
   if (nin < 0 || nout > 0x7fffffffu) return rh_fail(RH_ERR_ARG, "%s: bad ciphertext count", who);
-  if (int rc = rp_ring(RQ, levelQ, (int)nout, who)) return rc;
+  if (int rc = rh_ring_ok(RQ, levelQ, (int)nout, who)) return rc;
   if (!ct0 || !ct1 || !xinvpow || (nkeys > 0 && !keys) || nkeys < 0) return rh_fail(RH_ERR_ARG, "%s: null argument", who);
   if (xrows < levelQ + 1) return rh_fail(RH_ERR_ARG, "%s: the table of X^(-2^i) has %d limbs, the level needs %d", who, xrows, levelQ + 1);
   const int LQ = levelQ + 1, beta = (levelQ + levelP + 1) / (levelP + 1);

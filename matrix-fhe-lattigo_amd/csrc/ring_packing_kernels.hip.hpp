@@ -2,7 +2,7 @@
 // (:555-575), the two halves of one level of Pack (:726-769, :786-787), and the coefficient maps between the rings of degree N and N / gap that
 // Split and Merge are built on (core/rlwe/element.go:250-312, ring/operations.go:380-392).  All on the scaffold of stream_kernels.hip.hpp: one
 // (poly, limb) row per blockIdx.x, the row's pairs over blockIdx.y, 16-byte moves.  The gathered operand (the un-permuted output of the key
-// switch) is read through is_index_even / is_gather2 (paired_gather.hip.hpp): index(2i + 1) = index(2i) ^ 1 holds for EVERY odd element,
+// switch) is read through rh_galois_index_even / rh_gather2 (paired_gather.hip.hpp): index(2i + 1) = index(2i) ^ 1 holds for EVERY odd element,
 // N / n + 1 and 2N - 1 included, because the proof there only uses that gen is odd.
 //
 // Every intermediate of the reference's sequences is a canonical residue (Add, Sub and MulCoeffsMontgomery end in CRed), so the values below
@@ -18,15 +18,16 @@ __global__ void __launch_bounds__(256)
 expand_step_kernel(u64* ct0, u64* ct1, const u64* tmp0, const u64* tmp1, const u64* __restrict__ x, int logN, u32 gen,
                    const LimbConsts* __restrict__ consts, int L, int cnt, int nt) {
   const u32 per = (u32)cnt * (u32)L;
-  const u32 comp = blockIdx.x / per, rem = blockIdx.x % per, l = rem % (u32)L;
+  const StreamComp sc(per);
+  const u32 l = sc.row % (u32)L;
   const LimbConsts c = consts[l];
-  const size_t ro = (size_t)rem << logN;
-  u64* lo = (comp ? ct1 : ct0) + ro;
+  const size_t ro = (size_t)sc.row << logN;
+  u64* lo = (sc.comp ? ct1 : ct0) + ro;
   u64* hi = lo + ((size_t)per << logN);
-  const u64* tmp = (comp ? tmp1 : tmp0) + ro;
+  const u64* tmp = (sc.comp ? tmp1 : tmp0) + ro;
   const u64* xr = x + ((size_t)l << logN);
   RH_FOR_EACH_PAIR(i, 0, 1u << (logN - 1)) {
-    const ulonglong2 t = is_gather2(tmp, is_index_even(i, logN, gen));
+    const ulonglong2 t = rh_gather2(tmp, rh_galois_index_even(i, logN, gen));
     const ulonglong2 v = rh_ld2(lo + 2 * (size_t)i, nt);
     const ulonglong2 w = rh_ld2(xr + 2 * (size_t)i, false);         // the table is read by every poly: default policy
     ulonglong2 a, d;
@@ -52,15 +53,15 @@ RH_DEV bool rp_entry_ok(const RpEntry& e, int nslots) {
 __global__ void __launch_bounds__(256)
 pack_combine_kernel(u64* ct0, u64* ct1, u64* u0, u64* u1, const u64* __restrict__ x, const RpEntry* __restrict__ table, int logN,
                     const LimbConsts* __restrict__ consts, int L, int K, int nslots, int nt) {
-  const u32 per = (u32)K * (u32)L;
-  const u32 comp = blockIdx.x / per, rem = blockIdx.x % per, k = rem / (u32)L, l = rem % (u32)L;
+  const StreamComp sc((u32)K * (u32)L);
+  const u32 k = sc.row / (u32)L, l = sc.row % (u32)L;
   const RpEntry e = table[k];
   if (!rp_entry_ok(e, nslots)) return;
   const LimbConsts c = consts[l];
-  u64* base = comp ? ct1 : ct0;
+  u64* base = sc.comp ? ct1 : ct0;
   u64* a = base + (((size_t)e.a * L + l) << logN);
   u64* b = base + (((size_t)e.b * L + l) << logN);
-  u64* u = (comp ? u1 : u0) + ((size_t)rem << logN);
+  u64* u = (sc.comp ? u1 : u0) + ((size_t)sc.row << logN);
   const u64* xr = x + ((size_t)l << logN);
   RH_FOR_EACH_PAIR(i, 0, 1u << (logN - 1)) {
     const size_t o = 2 * (size_t)i;
@@ -83,16 +84,16 @@ pack_combine_kernel(u64* ct0, u64* ct1, u64* u0, u64* u1, const u64* __restrict_
 __global__ void __launch_bounds__(256)
 rotate_addsub_q_kernel(u64* ct0, u64* ct1, const u64* tmp0, const u64* tmp1, const RpEntry* __restrict__ table, int logN, u32 gen,
                        const LimbConsts* __restrict__ consts, int L, int K, int nslots, int nt) {
-  const u32 per = (u32)K * (u32)L;
-  const u32 comp = blockIdx.x / per, rem = blockIdx.x % per, k = rem / (u32)L, l = rem % (u32)L;
+  const StreamComp sc((u32)K * (u32)L);
+  const u32 k = sc.row / (u32)L, l = sc.row % (u32)L;
   const RpEntry e = table[k];
   if (!rp_entry_ok(e, nslots)) return;
   const u64 q = consts[l].q;
   const bool minus = e.mode == RP_MODE_B;
-  u64* ct = (comp ? ct1 : ct0) + (((size_t)(minus ? e.b : e.a) * L + l) << logN);
-  const u64* tmp = (comp ? tmp1 : tmp0) + ((size_t)rem << logN);
+  u64* ct = (sc.comp ? ct1 : ct0) + (((size_t)(minus ? e.b : e.a) * L + l) << logN);
+  const u64* tmp = (sc.comp ? tmp1 : tmp0) + ((size_t)sc.row << logN);
   RH_FOR_EACH_PAIR(i, 0, 1u << (logN - 1)) {
-    const ulonglong2 t = is_gather2(tmp, is_index_even(i, logN, gen));
+    const ulonglong2 t = rh_gather2(tmp, rh_galois_index_even(i, logN, gen));
     ulonglong2 v = rh_ld2(ct + 2 * (size_t)i, nt);
     v.x = cred(minus ? v.x + q - t.x : v.x + t.x, q); v.y = cred(minus ? v.y + q - t.y : v.y + t.y, q);
     rh_st2(ct + 2 * (size_t)i, v, nt);
@@ -105,12 +106,11 @@ rotate_addsub_q_kernel(u64* ct0, u64* ct1, const u64* tmp0, const u64* tmp1, con
 // yields the same canonical residues: (c X^-1)[2i] = c[2i + 1], no wrap.   grid: (2 * npoly * L, chunks); logM = log2(N / gap) >= 1
 __global__ void __launch_bounds__(256)
 ring_split_kernel(const u64* in0, const u64* in1, u64* even0, u64* even1, u64* odd0, u64* odd1, int logN, int logM, int nt) {
-  const u32 rows = gridDim.x / 2;
-  const u32 comp = blockIdx.x / rows, rem = blockIdx.x % rows;
-  const u64* in = (comp ? in1 : in0) + ((size_t)rem << logN);
-  u64* ev = (comp ? even1 : even0) + ((size_t)rem << logM);
-  u64* od = comp ? odd1 : odd0;
-  if (od) od += (size_t)rem << logM;
+  const StreamComp sc(gridDim.x / 2);
+  const u64* in = (sc.comp ? in1 : in0) + ((size_t)sc.row << logN);
+  u64* ev = (sc.comp ? even1 : even0) + ((size_t)sc.row << logM);
+  u64* od = sc.comp ? odd1 : odd0;
+  if (od) od += (size_t)sc.row << logM;
   const int lg = logN - logM;
   RH_FOR_EACH_PAIR(i, 0, 1u << (logM - 1)) {
     ulonglong2 e, o;
@@ -133,13 +133,13 @@ ring_split_kernel(const u64* in0, const u64* in1, u64* even0, u64* even1, u64* o
 __global__ void __launch_bounds__(256)
 ring_merge_kernel(const u64* even0, const u64* even1, const u64* odd0, const u64* odd1, const u64* __restrict__ x, u64* out0, u64* out1,
                   int logN, int logM, const LimbConsts* __restrict__ consts, int L, int nt) {
-  const u32 rows = gridDim.x / 2;
-  const u32 comp = blockIdx.x / rows, rem = blockIdx.x % rows, l = rem % (u32)L;
+  const StreamComp sc(gridDim.x / 2);
+  const u32 l = sc.row % (u32)L;
   const LimbConsts c = consts[l];
-  const u64* ev = (comp ? even1 : even0) + ((size_t)rem << logM);
-  const u64* od = comp ? odd1 : odd0;
-  if (od) od += (size_t)rem << logM;
-  u64* out = (comp ? out1 : out0) + ((size_t)rem << logN);
+  const u64* ev = (sc.comp ? even1 : even0) + ((size_t)sc.row << logM);
+  const u64* od = sc.comp ? odd1 : odd0;
+  if (od) od += (size_t)sc.row << logM;
+  u64* out = (sc.comp ? out1 : out0) + ((size_t)sc.row << logN);
   const u64* xr = x ? x + ((size_t)l << logN) : nullptr;
   const int lg = logN - logM;
   const u32 half = 1u << (lg - 1);                                   // 16-byte words per replicated coefficient

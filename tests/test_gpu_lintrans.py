@@ -153,6 +153,70 @@ def test_diag_mac_overflow_bound(rh):
     d.close()
 
 
+def test_table_staging_is_shared_with_the_linear_combination(rh):
+    """rh_rlwe_diag_mac_qp and rh_ckks_linear_combination stage their tables through ONE ring of four page-locked slots per calling thread
+    (csrc/engine.hip: rh_stage_slot).  On a thread of its own -- fresh slots, so the schedule below does not depend on the tests before it -- the
+    two alternate nine times with tables that grow and shrink: diag_mac with 1, 57, 4, 113, 0, ... terms (6 words a term; no term, no slot) and
+    the linear combination with 1, 9, 2, ... terms (4 + 8 words a term at level 1).  Slots in order of use:
+      0 1 2 3 | 0 1 2 (grown by their own caller) 3 (reused) | - 0 (grown under diag_mac's last use) | 1 (diag_mac reuses the other's) 2 | 3 (grown
+      under the other's last use) 0 | 1 2 | 3 0
+    Nothing is read back before the last call, so a slot is taken again while the copies before it may still be in flight; then every output,
+    whole and bit for bit, against the Python-integer expectations of this file and of tests/test_gpu_polynomial.py."""
+    import threading
+    import test_gpu_polynomial as tp
+    name, setting = SHAPES[0]
+    d = Device(rh, name, setting)
+    N, Q, P = d.N, d.Q, d.P
+    level, levelP = d.levels[0], len(P) - 1
+    mods, pm = [int(q) for q in Q[:level + 1]], [int(p) for p in P]
+    rql, rpl = d.rq.AtLevel(level), d.rp.AtLevel(levelP)
+    hpt, hx, _ = mac_operands(name, level)
+    dpt = [(up(rh, d.rq.AtLevel(d.levels[0]), [q]), up(rh, rpl, [p])) for q, p in hpt]
+    dx = [(up(rh, rql, q[0]), up(rh, rql, q[1]), up(rh, rpl, p[0]), up(rh, rpl, p[1])) for q, p in hx]
+    L = rh.lib()
+    mac_table = rh.DevicePoly(d.rq.AtLevel(0), -(-L.rh_rlwe_diag_mac_qp_table_words(113, level, levelP) // N), 1)
+
+    logN, logQ, lc_level, npoly = tp.SHAPES[0]
+    assert (1 << logN, npoly) == (N, B)
+    c = tp.Ctx(rh, logN, logQ)
+    _, _, rows, X, s0, s1, _, prefix = tp.lc_case(logN, logQ, lc_level, npoly)
+    rl = c.rq.AtLevel(lc_level)
+    dev = [[rh.DevicePoly.from_numpy(c.rq.AtLevel(rows[k] - 1), b) for b in X[k][:2]] for k in range(9)]
+    lc_table = rh.DevicePoly(rl, 1, -(-L.rh_ckks_linear_combination_table_words(9, lc_level) // N))
+
+    MAC_K, LC_K = [1, 57, 4, 113, 0, 1, 57, 4, 113], [1, 9, 2] * 3
+    rnd = random.Random("staging")
+    picks = [[(rnd.randrange(2), rnd.randrange(2)) for _ in range(K)] for K in MAC_K]
+    mac_out = [[rql.NewPoly(B), rql.NewPoly(B), rpl.NewPoly(B), rpl.NewPoly(B)] for _ in MAC_K]
+    lc_out = [[rl.NewPoly(npoly), rl.NewPoly(npoly)] for _ in LC_K]
+    status = []
+
+    def calls():
+        for i in range(9):
+            rc = diag_mac(rh, d, level, levelP, [dpt[a] for a, _ in picks[i]], [dx[b] for _, b in picks[i]], mac_out[i], mac_table)
+            status.append(rc if rc == 0 else (rc, L.rh_last_error()))
+            rc = tp.lc_call(rh, c.rq, lc_level, dev[:LC_K[i]], rows, s0, s1, None, lc_out[i], lc_table, npoly)
+            status.append(rc if rc == 0 else (rc, L.rh_last_error()))
+
+    th = threading.Thread(target=calls)
+    th.start()
+    th.join()
+    assert status == [0] * 18, status
+    rinv = lambda ms: np.array([pow(R, -1, q) for q in ms], dtype=object).reshape(1, -1, 1)
+    for i, K in enumerate(MAC_K):
+        for comp in (0, 1):
+            sq, sp = np.zeros((B, level + 1, N), dtype=object), np.zeros((B, len(pm), N), dtype=object)
+            for a, b in picks[i]:
+                sq = sq + obj([hpt[a][0][:level + 1]]) * obj(hx[b][0][comp])
+                sp = sp + obj([hpt[a][1]]) * obj(hx[b][1][comp])
+            assert np.array_equal(mac_out[i][comp].numpy(), ((sq * rinv(mods)) % col(mods)).astype(np.uint64)), (i, K, comp, "Q")
+            assert np.array_equal(mac_out[i][2 + comp].numpy(), ((sp * rinv(pm)) % col(pm)).astype(np.uint64)), (i, K, comp, "P")
+    for i, K in enumerate(LC_K):
+        for j in (0, 1):
+            assert np.array_equal(lc_out[i][j].numpy(), np.stack(prefix[K][j])), (i, K, j)
+    d.close()
+
+
 # ---- the two rotate kernels ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("nt_streams", [1, 2], ids=["nt-by-size", "nt-always"])
 @pytest.mark.parametrize("shape", SHAPES, ids=_ids)
