@@ -428,6 +428,24 @@ int rh_rlwe_rotate_mul_accumulate_qp(rh_bext* be, int levelQ, int levelP, uint64
                                      const uint64_t* cP1_dev, uint64_t* accQ0_dev, uint64_t* accQ1_dev, uint64_t* accP0_dev, uint64_t* accP1_dev,
                                      int npoly, int first);
 
+/* ---- blind rotation (core/rgsw/blindrot/evaluator.go): BlindRotateCore (:134-186) and evaluateFromDiscreteLogSets (:189-229) for a batch of
+ * accumulators in ONE launch, one workgroup per accumulator, resident for the accumulator's whole chain.  It replaces the calls of
+ * rgsw.Evaluator.ExternalProduct (core/rgsw/evaluator.go:42-186: the 32-bit branch :82-117 and the Montgomery branch :119-186, which give the same
+ * canonical residues) and of rlwe.Evaluator.Automorphism (core/rlwe/evaluator_automorphism.go:14-60) that the reference issues per accumulator.
+ * Standard ring (RH_ERR_UNSUPPORTED otherwise) of degree 2^6 .. 2^11 (RH_ERR_UNSUPPORTED otherwise), its modulus 0 alone (levelQ = 0), keys
+ * without P and with a power-of-two decomposition: pw2 = BaseTwoDecomposition >= 1, `digits` rows per gadget ciphertext.
+ *   rgsw_dev         [key][k < 2][digit][component < 2][N]: Value[k] of BlindRotationKeys[key], NTT domain, Montgomery form; nkeys keys
+ *   galois_dev       [slot][digit][component < 2][N]: the automorphism keys; galois_elements: their Galois elements (HOST array, odd, taken
+ *                    modulo 2N), ngalois <= 16 slots
+ *   prog_offsets_dev nacc + 1 int32 on the device: accumulator b runs prog_ops_dev[prog_offsets[b] .. prog_offsets[b + 1]), in order
+ *   prog_ops_dev     nops int32 on the device.  op >= 0: acc = acc x rgsw[op] (ExternalProduct in place); op < 0: acc = Automorphism(acc) with
+ *                    key slot -op - 1.  An op that names a key outside the tables, or an offset outside [0, nops], is skipped by the kernel
+ *   c0_dev, c1_dev   the accumulators, nacc polys each, NTT domain, canonical residues in and out, updated in place
+ * Asynchronous on the ring's stream; keeps no state in the handle. */
+int rh_blindrot_core(rh_ring* r, int pw2, int digits, const uint64_t* rgsw_dev, int nkeys, const uint64_t* galois_dev,
+                     const uint64_t* galois_elements, int ngalois, const int32_t* prog_offsets_dev, const int32_t* prog_ops_dev, int nops,
+                     uint64_t* c0_dev, uint64_t* c1_dev, int nacc);
+
 /* ---- ring packing (core/rlwe/ring_packing.go).  Standard rings (RH_ERR_UNSUPPORTED otherwise), dense blocks of level+1 limbs per poly, canonical
  * residues in and out, both components of a batch of ciphertexts in one launch; the NTT-domain index map of the Galois element (any odd number,
  * taken modulo 2N) is computed in the kernel.  Every block is 16-byte aligned and no written block may overlap a read one (RH_ERR_ARG).

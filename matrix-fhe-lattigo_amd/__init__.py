@@ -11,6 +11,7 @@ from .schemes import Ciphertext, MatrixCKKSEvaluator, ckks_tensor_degree1, ckks_
 from . import rlwe  # noqa: F401,E402
 from . import ckks  # noqa: F401,E402
 from . import rgsw  # noqa: F401,E402
+from . import blindrot  # noqa: F401,E402
 from . import bgv  # noqa: F401,E402
 from . import polynomial  # noqa: F401,E402
 from . import lintrans  # noqa: F401,E402

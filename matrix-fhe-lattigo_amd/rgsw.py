@@ -8,7 +8,9 @@ The reference accumulates both products in one pair of lazy accumulators with a 
 Reduce is the canonical residue, so the accumulators after the loop are the canonical residues of the sum whatever the schedule -- here
 the two lazy products (rlwe.Evaluator.GadgetProductLazy: canonical residues modulo Q and modulo P) are added with ring.Add and handed to
 ModDown: the same bits (tests/test_gpu_rgsw.py checks it against the reference's loop restated over the oracle pieces).  LevelP <= 0 takes
-externalProductInPlaceSinglePAndBitDecomp (:119-186) the same way; the 32-bit branch (:82-117, one modulus below 2^29) is not built."""
+externalProductInPlaceSinglePAndBitDecomp (:119-186) the same way, and so does the 32-bit branch (:82-117, one modulus below 2^29 without P):
+its wrapping 64-bit sum of NTTLazy digits times Montgomery-form key rows never overflows (:57) and IMForm closes it, so it is the canonical residue
+of the same sum (tests/test_blindrot_oracle.py restates the literal loop against the Montgomery branch)."""
 from .ringhip import RingHipError
 from .rlwe import ElementQP, Evaluator as RLWEEvaluator, GadgetCiphertext
 
@@ -60,11 +62,13 @@ class Evaluator(RLWEEvaluator):
         every modulus (mask = all ones without a power-of-two decomposition), the products accumulated with the canonical
         MulCoeffsMontgomery(ThenAdd) over both components k -- then ModDownQPtoQNTT (LevelP = 0) or CopyLvl (no P).  Each component's sum is
         rh_bext_gadget_product_single_p_lazy in its rgsw digit form; the two canonical sums are added with ring.Add.  The reference's 32-bit
-        branch (:54-57, :82-117: one modulus below 2^29, plain wrapping products) is not built and refused."""
+        branch (:54-57, :82-117: one modulus below 2^29, plain wrapping products closed by IMForm) gives the same canonical residues and runs
+        through the same calls."""
         import ctypes as C
         from .ringhip import _check, lib, DevicePoly
-        if levelQ == 0 and levelP == -1 and (int(self.ringQ.moduli[0]) >> 29) == 0:
-            raise RingHipError("ExternalProduct: the 32-bit branch (core/rgsw/evaluator.go:82-117) is not built")
+        if levelQ == 0 and levelP == -1 and (int(self.ringQ.moduli[0]) >> 29) == 0 and op1.Value[0].BaseTwoDecomposition == 0:
+            raise RingHipError("ExternalProduct: the 32-bit branch (core/rgsw/evaluator.go:82-117) without a power-of-two decomposition masks "
+                               "every digit with (1 << 0) - 1 = 0 in the reference; that zero product is not built")
         if not op0.IsNTT or opOut.IsNTT is not True:
             raise RingHipError("ExternalProduct (LevelP <= 0): NTT-domain ciphertexts (the reference takes INTT of op0.Value[k], :148)")
         self._rows(levelQ, op0.Value[0], op0.Value[1], opOut.Value[0], opOut.Value[1])

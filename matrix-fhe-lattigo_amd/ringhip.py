@@ -142,6 +142,7 @@ def lib():
         "rh_rlwe_diag_mac_qp": (i, [vp, i, i, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, vp, vp, i, vp, sz]),
         "rh_rlwe_rotate_sum_accumulate_qp": (i, [vp, i, i, C.c_uint64] + [vp] * 10 + [i, i]),
         "rh_rlwe_rotate_mul_accumulate_qp": (i, [vp, i, i, C.c_uint64] + [vp] * 11 + [i, i]),
+        "rh_blindrot_core": (i, [vp, i, i, vp, i, vp, U64P, i, vp, vp, i, vp, vp, i]),
         "rh_rlwe_expand_step": (i, [vp, i, C.c_uint64, vp, vp, vp, vp, vp, i]),
         "rh_rlwe_pack_combine": (i, [vp, i, vp, vp, i, vp, C.POINTER(C.c_int32), i, vp, vp, vp]),
         "rh_rlwe_rotate_addsub_q": (i, [vp, i, C.c_uint64, vp, vp, vp, vp, i, vp, C.POINTER(C.c_int32), i]),

@@ -9,7 +9,8 @@ the HIP library; no key generation, no encoders (those stay with the reference).
 
 GadgetProduct covers both branches of GadgetProductLazy (:102-121): gadgetProductMultiplePLazy (levelP >= 1) and
 gadgetProductSinglePAndBitDecompLazy (levelP <= 0, optional BaseTwoDecomposition), for NTT- and coefficient-domain ciphertexts.
-The hoisted forms and the automorphism / relinearisation callers take NTT-domain ciphertexts and levelP >= 1.
+The hoisted forms and the automorphism / relinearisation callers take NTT-domain ciphertexts and levelP >= 1; Automorphism alone also takes
+keys of levelP <= 0 (single P, or no P with a power-of-two decomposition) through GadgetProduct, ringQ.Add and AutomorphismNTT.
 
   PartialTracesSum       core/rlwe/inner_sum.go:152-291     Trace  :36-121     InnerFunction  :316-440     Replicate  :477-479
   GaloisElementsForInnerSum  :444-468     GaloisElementsForReplicate  :483-485     GaloisElementsForTrace  :125-146
@@ -351,7 +352,11 @@ class Evaluator:
         evk = self._galois_key(galEl)
         npoly = ctIn.Value[1].npoly
         tmp = Ciphertext([self.buffer("auto0", ringQ, npoly, level + 1), self.buffer("auto1", ringQ, npoly, level + 1)], is_ntt=True)
-        self.GadgetProductThenAdd(level, ctIn.Value[1], evk, ctIn.Value[0], None, tmp)         # product + ringQ.Add (:42-44)
+        if evk.LevelP() >= 1:
+            self.GadgetProductThenAdd(level, ctIn.Value[1], evk, ctIn.Value[0], None, tmp)     # product + ringQ.Add (:42-44)
+        else:                                                         # single P, or no P with a power-of-two decomposition: the other branch of GadgetProduct
+            self.GadgetProduct(level, ctIn.Value[1], evk, tmp)
+            ringQ.Add(tmp.Value[0], ctIn.Value[0], tmp.Value[0])
         ringQ.AutomorphismNTT(tmp.Value[0], galEl, opOut.Value[0])   # AutomorphismNTTWithIndex (ring/automorphism.go:52-73)
         ringQ.AutomorphismNTT(tmp.Value[1], galEl, opOut.Value[1])
         opOut.IsNTT = ctIn.IsNTT

@@ -16,7 +16,10 @@ config 5 ring and at N = 2^12, fused against composed, batched against per-ciphe
 K = 7, 15, 31: rh_ckks_linear_combination against the composed sequence of MulThenAdd calls) and writes profiles/ckks_polynomial.json;
 `bench_ops.py lintrans [OUT.json]` the linear transformations (lintrans.Evaluator.Evaluate at the config 5 ring, batches of 1 and 8: the reference
 test's nine diagonals with and without BSGS and a dense 64-diagonal matrix, each kernel of csrc/lintrans.hip alone against the ring calls it
-replaces and inside the whole Evaluate) and writes profiles/lintrans.json."""
+replaces and inside the whole Evaluate) and writes profiles/lintrans.json; `bench_ops.py blindrot [OUT.json [BASELINE.json]]` the blind rotation's
+accumulator loop at the reference test's parameters (N = 2^10 / 2^9, Q = 0x7fff801, pw2 = 7) with 16, 64 and 256 accumulators, the kernel against
+the composed calls, and writes profiles/blindrot.json; `bench_ops.py blindrot_baseline [OUT.json]` one ExternalProduct and one key-switched
+automorphism at npoly = 1 through calls that predate the kernel (run it on the parent commit: BASELINE.json above)."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -875,6 +878,110 @@ def lintrans_group(out_path):
     print(json.dumps(res, indent=1))
     cev.close()
     rq.close(); rp.close()
+
+
+def _wall_ms(fn, sync, reps, warm=1):
+    """host wall clock around `reps` calls, the device drained before and after: what a caller waits for"""
+    for _ in range(warm):
+        fn()
+    sync()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    sync()
+    return (time.perf_counter() - t0) * 1e3 / reps
+
+
+def _random_gadget(rng, rq, q, N, rows, pw2):
+    return rh.rlwe.GadgetCiphertext(rq, None, rng.integers(0, q, size=(rows, 2, 1, N), dtype=np.uint64), None, BaseTwoDecomposition=pw2, digits_per_limb=[rows])
+
+
+def blindrot_baseline(out_path):
+    """One rgsw ExternalProduct and one key-switched automorphism (GadgetProduct, Add, two AutomorphismNTT) on ONE ciphertext at N = 2^10, one
+    55-bit modulus, no P, pw2 = 14: the launch-per-ring-call cost of one step of a blind rotation, through calls the commit before the kernel has."""
+    N, q, pw2, rows = 1024, 0x7ffffffffb4001, 14, 4
+    rng = np.random.default_rng(1)
+    rq = rh.Ring(N, [q])
+    ev = rh.rgsw.Evaluator(rq, None)
+    rgsw = rh.rgsw.Ciphertext(_random_gadget(rng, rq, q, N, rows, pw2), _random_gadget(rng, rq, q, N, rows, pw2))
+    gk = _random_gadget(rng, rq, q, N, rows, pw2)
+    new = lambda: rh.DevicePoly.from_numpy(rq, rng.integers(0, q, size=(1, 1, N), dtype=np.uint64))
+    ct, tmp = rh.Ciphertext([new(), new()], is_ntt=True), rh.Ciphertext([new(), new()], is_ntt=True)
+
+    def auto():
+        ev.GadgetProduct(0, ct.Value[1], gk, tmp)
+        rq.Add(tmp.Value[0], ct.Value[0], tmp.Value[0])
+        rq.AutomorphismNTT(tmp.Value[0], 5, ct.Value[0])
+        rq.AutomorphismNTT(tmp.Value[1], 5, ct.Value[1])
+    ext_ms = min(_wall_ms(lambda: ev.ExternalProduct(ct, rgsw, ct), rq.sync, 200, warm=20) for _ in range(3))
+    auto_ms = min(_wall_ms(auto, rq.sync, 200, warm=20) for _ in range(3))
+    from bench import csrc_tree_hash
+    res = {"device": torch.cuda.get_device_name(0), "csrc_tree": csrc_tree_hash(), "shape": {"N": N, "modulus_bits": 55, "limbs_P": 0, "pw2": pw2, "npoly": 1},
+           "method": "host wall clock over 200 back-to-back calls after 20 warm-up calls, device drained before and after, best of 3 windows",
+           "external_product_us": round(ext_ms * 1e3, 2), "automorphism_us": round(auto_ms * 1e3, 2)}
+    with open(out_path, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(res, indent=1))
+    ev.close(); rq.close()
+
+
+def blindrot_group(out_path, baseline_path=None):
+    """The reference test's parameters (core/rgsw/blindrot/blindrot_test.go:53-71): N_BR = 2^10, Q = 0x7fff801, N_LWE = 2^9, pw2 = 7 (4 digits), 512
+    RGSW keys and 11 automorphism keys (uniformly random words: timing needs no encryption), accumulators with uniformly random odd a vectors.
+    The accumulator loop (Evaluator._run) as one kernel launch against the composed ExternalProduct / Automorphism calls, for 16, 64 and 256
+    accumulators; the composed calls walk one accumulator at a time, so they are timed on the first 4 accumulators of each batch."""
+    N, q, NL, pw2, rows = 1024, 0x7fff801, 512, 7, 4
+    rng = np.random.default_rng(2)
+    rq, rl = rh.Ring(N, [q]), rh.Ring(NL, [0x3001])
+    ev = rh.blindrot.Evaluator(rq, rl)
+    BRK = rh.blindrot.MemBlindRotationEvaluationKeySet(
+        [rh.rgsw.Ciphertext(_random_gadget(rng, rq, q, N, rows, pw2), _random_gadget(rng, rq, q, N, rows, pw2)) for _ in range(NL)],
+        {g: _random_gadget(rng, rq, q, N, rows, pw2) for g in rh.blindrot.GaloisElements(N)})
+    baseline = json.load(open(baseline_path)) if baseline_path else None
+    results = []
+    for slots in (16, 64, 256):
+        a = rng.integers(0, N, size=(slots, NL)) * 2 + 1
+        progs = [rh.blindrot.blind_rotate_program([int(x) for x in row], N, ev.galoisGenDiscreteLog) for row in a]
+        n_ext = NL
+        n_auto = sum(1 for p in progs for kind, _ in p if kind == rh.blindrot.AUTO) / slots
+        acc = rh.Ciphertext([rh.DevicePoly.from_numpy(rq, rng.integers(0, q, size=(slots, 1, N), dtype=np.uint64)) for _ in (0, 1)], is_ntt=True)
+        fused_ms = min(_wall_ms(lambda: ev._run(progs, acc, BRK, True), rq.sync, 3) for _ in range(3))
+        nc = 4
+        sub = rh.Ciphertext([rh.rlwe._view(v, 0, nc) for v in acc.Value], is_ntt=True)
+        comp_ms = _wall_ms(lambda: ev._run(progs[:nc], sub, BRK, False), rq.sync, 1, warm=1) / nc      # per accumulator
+        e = {"accumulators": slots, "ext_steps_per_accumulator": n_ext, "auto_steps_per_accumulator": round(n_auto, 1),
+             "fused_ms": round(fused_ms, 3), "fused_accumulators_per_s": round(slots / (fused_ms * 1e-3), 1),
+             "fused_us_per_ext_step_of_a_chain": round(fused_ms * 1e3 / n_ext, 3), "fused_us_per_ext_step_of_the_batch": round(fused_ms * 1e3 / (n_ext * slots), 4),
+             "composed_ms_per_accumulator": round(comp_ms, 3), "composed_accumulators_per_s": round(1e3 / comp_ms, 2),
+             "composed_us_per_ext_step": round(comp_ms * 1e3 / n_ext, 3), "composed_accumulators_timed": nc,
+             "fused_over_composed": round((slots / fused_ms) / (1.0 / comp_ms), 1)}
+        if baseline:
+            proj = (n_ext * baseline["external_product_us"] + n_auto * baseline["automorphism_us"]) * 1e-3
+            e["parent_projected_ms_per_accumulator"] = round(proj, 3)
+            e["fused_over_parent_projection"] = round((slots / fused_ms) / (1.0 / proj), 1)
+        results.append(e)
+    from bench import csrc_tree_hash
+    res = {"device": torch.cuda.get_device_name(0), "csrc_tree": csrc_tree_hash(),
+           "shape": {"N_BR": N, "Q_BR": hex(q), "N_LWE": NL, "pw2": pw2, "digits": rows, "rgsw_keys": NL, "automorphism_keys": 11},
+           "method": "host wall clock around Evaluator._run (program upload, launch and drain included), best of 3 windows of 3 calls for the kernel; one call "
+                     "after one warm-up call on 4 accumulators for the composed calls; clocks left to the driver's default governor",
+           "parent_commit_baseline": baseline, "fused_blindrot_default": bool(all(e["fused_over_composed"] >= 1.0 for e in results)), "results": results}
+    with open(out_path, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(res, indent=1))
+    ev.close(); rq.close(); rl.close()
+
+
+if sys.argv[1:2] == ["blindrot_baseline"]:
+    blindrot_baseline(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "blindrot_baseline.json"))
+    sys.exit(0)
+
+
+if sys.argv[1:2] == ["blindrot"]:
+    blindrot_group(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "blindrot.json"), sys.argv[3] if len(sys.argv) > 3 else None)
+    sys.exit(0)
 
 
 if sys.argv[1:2] == ["lintrans"]:
