@@ -125,17 +125,7 @@ bext_multi_kernel(const u64* in, int in_rows, BextMulti m, u64* out0, size_t str
 static void bext_dispatch(dim3 grid, hipStream_t st, const BextPlan& p, const u64* in, int in_rows, int src_limb0, u64* out0, int out0_rows,
                           u64* out1, int out1_rows, const u64* other, int other_rows, int N, int add_mode) {
   const size_t vt_bytes = (size_t)p.ntgt_c * (p.nsrc + 1) * 8;      // at most 64 targets x 33 entries = 16.5 KiB
-  switch (p.nsrc) {
-    case 1: bext_kernel<1, true><<<grid, 256, vt_bytes, st>>>(RH_BEXT_ARGS); return;
-    case 2: bext_kernel<2, true><<<grid, 256, vt_bytes, st>>>(RH_BEXT_ARGS); return;
-    case 3: bext_kernel<3, true><<<grid, 256, vt_bytes, st>>>(RH_BEXT_ARGS); return;
-    case 4: bext_kernel<4, true><<<grid, 256, vt_bytes, st>>>(RH_BEXT_ARGS); return;
-    case 5: bext_kernel<5, true><<<grid, 256, vt_bytes, st>>>(RH_BEXT_ARGS); return;
-    case 6: bext_kernel<6, true><<<grid, 256, vt_bytes, st>>>(RH_BEXT_ARGS); return;
-    case 7: bext_kernel<7, true><<<grid, 256, vt_bytes, st>>>(RH_BEXT_ARGS); return;
-    case 8: bext_kernel<8, true><<<grid, 256, vt_bytes, st>>>(RH_BEXT_ARGS); return;
-    default: break;
-  }
+  if (rh_with_s1<1, 8>(p.nsrc, [&](auto NS) { bext_kernel<NS(), true><<<grid, 256, vt_bytes, st>>>(RH_BEXT_ARGS); })) return;   // exactly NS source limbs
   if (p.nsrc <= 16) bext_kernel<16, false><<<grid, 256, vt_bytes, st>>>(RH_BEXT_ARGS);
   else if (p.nsrc <= 32) bext_kernel<32, false><<<grid, 256, vt_bytes, st>>>(RH_BEXT_ARGS);
   else bext_kernel<0, false><<<grid, 256, vt_bytes + (size_t)p.nsrc * 256 * 8, st>>>(RH_BEXT_ARGS);

@@ -375,33 +375,65 @@ int rh_pack_scalars(const rh_ring* r, int level, const u64* a, const u64* b, boo
 }
 
 // ------------------------------------------------------------------------------------------------ NTT launches
+// The launchers below take what they cannot decide themselves -- rows, strides, tables, body, cache policy, scale -- from the site that calls them
+// (the sites' cache policies differ: engine_internal.hpp, rh_nt_rows and the lines after it).
 
-template <class P>
-static void launch_fwd_cols(int S1, dim3 grid, hipStream_t st, const u64* in, u64* out, const typename P::tw_t* tw,
-                            const LimbConsts* c, int L, int logN, int Ls = 0, int Lso = 0) {
-  switch (S1) {
-    case 1: ntt_fwd_cols<P, 1><<<grid, 256, 0, st>>>(in, out, tw, c, L, logN, Ls, Lso); break;
-    case 2: ntt_fwd_cols<P, 2><<<grid, 256, 0, st>>>(in, out, tw, c, L, logN, Ls, Lso); break;
-    case 3: ntt_fwd_cols<P, 3><<<grid, 256, 0, st>>>(in, out, tw, c, L, logN, Ls, Lso); break;
-    case 4: ntt_fwd_cols<P, 4><<<grid, 256, 0, st>>>(in, out, tw, c, L, logN, Ls, Lso); break;
-    case 5: ntt_fwd_cols<P, 5><<<grid, 256, 0, st>>>(in, out, tw, c, L, logN, Ls, Lso); break;
-  }
+// Tables and per-limb constants of limbs [limb0, ...).  mont_product: N^-1 * 2^64 in the last inverse stage (rh_ring_intt_mul, rh_ring_polymul)
+struct NttTabs {
+  const tw2 *tw_fwd, *twk_fwd, *tw_inv, *twk_inv, *lastw;
+  const u64 *tw_fwd_mont, *twk_fwd_mont, *tw_inv_mont;
+  const LimbConsts* c;
+};
+static NttTabs ntt_tabs(const rh_ring* r, int limb0, bool mont_product = false) {
+  const size_t toff = (size_t)limb0 * r->N;
+  auto at = [](auto* p, size_t off) { return p ? p + off : nullptr; };
+  return {at(r->d_tw_fwd, toff), at(r->d_twk_fwd, toff), at(r->d_tw_inv, toff), at(r->d_twk_inv, toff), at(mont_product ? r->d_lastw_r : r->d_lastw, limb0),
+          at(r->d_tw_fwd_mont, toff), at(r->d_twk_fwd_mont, toff), at(r->d_tw_inv_mont, toff), at(mont_product ? r->d_consts_r : r->d_consts, limb0)};
 }
-static void launch_inv_cols(int S1, dim3 grid, hipStream_t st, u64* data, const tw2* tw, const tw2* lastw,
-                            const LimbConsts* c, int L, int logN, int scale, int Ls = 0) {
-  switch (S1) {
-    case 1: ntt_inv_cols<1><<<grid, 256, 0, st>>>(data, tw, lastw, c, L, logN, scale, Ls); break;
-    case 2: ntt_inv_cols<2><<<grid, 256, 0, st>>>(data, tw, lastw, c, L, logN, scale, Ls); break;
-    case 3: ntt_inv_cols<3><<<grid, 256, 0, st>>>(data, tw, lastw, c, L, logN, scale, Ls); break;
-    case 4: ntt_inv_cols<4><<<grid, 256, 0, st>>>(data, tw, lastw, c, L, logN, scale, Ls); break;
-    case 5: ntt_inv_cols<5><<<grid, 256, 0, st>>>(data, tw, lastw, c, L, logN, scale, Ls); break;
-  }
+// The rows of one launch: npoly polys of Lrows limbs; Ls / Lso: rows per poly of the input / output block (0: dense, Lrows)
+struct NttRows {
+  const u64* in; u64* out; int npoly, Lrows, Ls, Lso;
+  unsigned rows() const { return (unsigned)npoly * (unsigned)Lrows; }
+};
+enum NttBody { BODY_CPP, BODY_ASM, BODY_MONT };   // compiled Shoup body; hand-scheduled body; compiled Montgomery body (the forward lazy form keeps the reference's representatives)
+
+// forward column stages, in -> out (N >= 8192; the hand-scheduled body exists for N = 2^14 .. 2^16, other degrees get the compiled one)
+static void launch_fwd_cols(const NttTabs& t, hipStream_t st, int logN, const NttRows& x, NttBody body, bool nt) {
+  const int S1 = logN - LT;
+  const dim3 g(x.rows() * 16);
+  if (body == BODY_ASM && rh_with_s1<2, 4>(S1, [&](auto S) { rh_with_flag(nt, [&](auto NT) {
+        ntt_fwd_cols_asm<S(), NT()><<<g, 256, 0, st>>>(x.in, x.out, t.tw_fwd, t.c, x.Lrows, x.Ls, x.Lso); }); })) return;
+  rh_with_s1<1, 5>(S1, [&](auto S) {
+    if (body == BODY_MONT) ntt_fwd_cols<MontPolicy, S()><<<g, 256, 0, st>>>(x.in, x.out, t.tw_fwd_mont, t.c, x.Lrows, logN, x.Ls, x.Lso);
+    else ntt_fwd_cols<ShoupPolicy, S()><<<g, 256, 0, st>>>(x.in, x.out, t.tw_fwd, t.c, x.Lrows, logN, x.Ls, x.Lso);
+  });
+}
+// forward tile stages, in -> out
+static void launch_fwd_tile(const NttTabs& t, hipStream_t st, int logN, const NttRows& x, NttBody body, bool nt) {
+  const unsigned tiles = x.rows() << (logN - LT);
+  if (body == BODY_MONT) ntt_fwd_tile<MontPolicy><<<tiles, 256, 0, st>>>(x.in, x.out, t.twk_fwd_mont, t.c, x.Lrows, logN, 0, x.npoly, x.Ls, x.Lso);
+  else if (body == BODY_ASM) rh_with_flag(nt, [&](auto NT) { ntt_fwd_tile_asm<NT()><<<tiles, 256, 0, st>>>(x.in, x.out, t.twk_fwd, t.c, x.Lrows, logN, x.npoly, x.Ls, x.Lso); });
+  else ntt_fwd_tile<ShoupPolicy><<<tiles, 256, 0, st>>>(x.in, x.out, t.twk_fwd, t.c, x.Lrows, logN, 1, x.npoly, x.Ls, x.Lso);
+}
+// inverse tile stages, in -> out.  The hand-scheduled body leaves values < 4q unscaled; scale: the compiled body of N = 4096 multiplies by N^-1
+static void launch_inv_tile(const NttTabs& t, hipStream_t st, int logN, const NttRows& x, NttBody body, bool nt, int scale) {
+  const unsigned tiles = x.rows() << (logN - LT);
+  if (body == BODY_ASM) rh_with_flag(nt, [&](auto NT) { ntt_inv_tile_asm<NT()><<<tiles, 256, 0, st>>>(x.in, x.out, t.twk_inv, t.c, x.Lrows, logN, x.npoly, x.Ls, x.Lso); });
+  else ntt_inv_tile<<<tiles, 256, 0, st>>>(x.in, x.out, t.twk_inv, t.c, x.Lrows, logN, scale, x.npoly, x.Ls, x.Lso);
+}
+// inverse column stages, in place on x.out (N >= 8192).  The hand-scheduled body (N = 2^14 .. 2^16) always scales by the table's N^-1
+static void launch_inv_cols(const NttTabs& t, hipStream_t st, int logN, const NttRows& x, NttBody body, bool nt, int scale) {
+  const int S1 = logN - LT;
+  const dim3 g(x.rows() * 16);
+  if (body == BODY_ASM && rh_with_s1<2, 4>(S1, [&](auto S) { rh_with_flag(nt, [&](auto NT) {
+        ntt_inv_cols_asm<S(), NT()><<<g, 256, 0, st>>>(x.out, t.tw_inv, t.lastw, t.c, x.Lrows, x.Lso); }); })) return;
+  rh_with_s1<1, 5>(S1, [&](auto S) { ntt_inv_cols<S()><<<g, 256, 0, st>>>(x.out, t.tw_inv, t.lastw, t.c, x.Lrows, logN, scale, x.Lso); });
 }
 
 // One-pass launches (N = 2^13, 2^14; ntt_kernels_asm.hip.hpp): 68 / 136 KiB of dynamic LDS per workgroup, beyond the 64 KiB default limit.
 static bool one_pass_ok(rh_ring* r) {
   const int S1 = r->logN - LT;
-  if (!(r->one_pass && r->asm_tile && (S1 == 1 || S1 == 2))) return false;
+  if (!(r->one_pass && r->asm_tile && S1 >= 1 && S1 <= 2)) return false;
   if (!r->one_pass_ready) {
     const int b1 = 2 * LDS_WORDS * 8, b2 = 4 * LDS_WORDS * 8;
     hipError_t e = hipSuccess;
@@ -415,215 +447,181 @@ static bool one_pass_ok(rh_ring* r) {
   }
   return true;
 }
+// the whole transform of a limb row in one workgroup: N = 2^13, 2^14, and the inverse of N = 4096 (the tile body, then N^-1 out of LDS)
+static void launch_onepass(const NttTabs& t, hipStream_t st, int S1, const NttRows& x, bool inverse, bool nt, int scale) {
+  const size_t lds = ((size_t)LDS_WORDS * 8) << S1;
+  const dim3 wg(256u << S1);
+  if (!inverse) rh_with_s1<1, 2>(S1, [&](auto S) { rh_with_flag(nt, [&](auto NT) {
+      ntt_fwd_onepass_asm<S(), NT()><<<x.rows(), wg, lds, st>>>(x.in, x.out, t.tw_fwd, t.twk_fwd, t.c, x.Lrows, x.Ls, x.Lso); }); });
+  else rh_with_s1<0, 2>(S1, [&](auto S) { rh_with_flag(nt, [&](auto NT) {
+      ntt_inv_onepass_asm<S(), NT()><<<x.rows(), wg, lds, st>>>(x.in, x.out, t.twk_inv, t.tw_inv, t.lastw, t.c, x.Lrows, x.Ls, x.Lso, scale); }); });
+}
+// rings below N = 4096: one launch.  mont_inv: the non-canonical BackwardLazy of N = 8 on the Montgomery table
+static int launch_small(const NttTabs& t, hipStream_t st, int logN, const NttRows& x, bool inverse, bool lazy, bool mont_inv, int scale) {
+  if (!inverse) {
+    if (lazy) ntt_fwd_small<MontPolicy><<<x.rows(), 256, 0, st>>>(x.in, x.out, t.tw_fwd_mont, t.c, x.Lrows, logN, 0, x.Ls, x.Lso);
+    else      ntt_fwd_small<ShoupPolicy><<<x.rows(), 256, 0, st>>>(x.in, x.out, t.tw_fwd, t.c, x.Lrows, logN, 1, x.Ls, x.Lso);
+  } else if (mont_inv) {
+    if (x.Ls || x.Lso) return rh_fail(RH_ERR_UNSUPPORTED, "strided non-canonical BackwardLazy of N = 8");          // (ntt_rows compacts this one shape)
+    ntt_inv_small_lazy_mont<<<x.rows(), 64, 0, st>>>(x.in, x.out, t.tw_inv_mont, t.c, x.Lrows, logN);   // N = 8: BackwardLazy is not canonical
+  } else {
+    ntt_inv_small<<<x.rows(), 256, 0, st>>>(x.in, x.out, t.tw_inv, t.c, x.Lrows, logN, scale, x.Ls, x.Lso);
+  }
+  return rh_launch_ok("ntt_small");
+}
+
+// The stages of a two-pass span transform as the ring's tuning picks their bodies, with the span's cache policy (rh_nt_rows).
+static void span_fwd_cols(rh_ring* r, const NttRows& x, int limb0, bool lazy) {
+  launch_fwd_cols(ntt_tabs(r, limb0), rh_stream(r), r->logN, x, lazy ? BODY_MONT : (r->asm_cols && r->asm_tile ? BODY_ASM : BODY_CPP), rh_nt_rows(r, x.rows()));
+}
+// x.in: where the column stages wrote (the OUTPUT block, its stride on both sides) or, without column stages (N = 4096), the input block
+static void span_fwd_tile(rh_ring* r, const NttRows& x, int limb0, bool lazy) {
+  const int lso = x.Lso ? x.Lso : (x.Ls ? x.Ls : x.Lrows);
+  const int ls = (x.in == x.out) ? lso : (x.Ls ? x.Ls : x.Lrows);
+  launch_fwd_tile(ntt_tabs(r, limb0), rh_stream(r), r->logN, NttRows{x.in, x.out, x.npoly, x.Lrows, ls, lso},
+                  lazy ? BODY_MONT : (r->asm_tile ? BODY_ASM : BODY_CPP), rh_nt_rows(r, x.rows()));
+}
+// the hand-scheduled body leaves values < 4q unscaled: right whenever column stages follow, and for N = 4096 sub-rings of the 3N transform
+// (inv_scale = false), which scale in their own last layer
+static void span_inv_tile(rh_ring* r, const NttRows& x, int limb0) {
+  const bool n4096 = r->logN == LT;
+  launch_inv_tile(ntt_tabs(r, limb0), rh_stream(r), r->logN, x, r->asm_tile && (!n4096 || !r->inv_scale) ? BODY_ASM : BODY_CPP, rh_nt_rows(r, x.rows()),
+                  (n4096 && r->inv_scale) ? 1 : 0);
+}
+static void span_inv_cols(rh_ring* r, const NttRows& x, int limb0) {
+  launch_inv_cols(ntt_tabs(r, limb0), rh_stream(r), r->logN, x, r->asm_cols && r->asm_tile && r->inv_scale ? BODY_ASM : BODY_CPP, rh_nt_rows(r, x.rows()),
+                  r->inv_scale ? 1 : 0);
+}
 
 // limb0: first limb of the table set to use (host-pointer single-limb path); rows = npoly * Lrows.
-// phase: 0 = whole transform, 1 = column kernel only, 2 = tile kernel only (profiling aid, rh_ring_ntt_phase).
-static int std_ntt_launch_span(rh_ring* r, const u64* in, u64* out, int npoly, int Lrows, int limb0, bool inverse, bool lazy, int phase,
+static int std_ntt_launch_span(rh_ring* r, const u64* in, u64* out, int npoly, int Lrows, int limb0, bool inverse, bool lazy,
                                int Ls = 0, int Lso = 0) {   // Ls / Lso: rows per poly of the input / output block when > Lrows (0: Lrows / Ls): AtLevel views
   (void)hipGetLastError();                       // drop any stale error of an unrelated earlier call
   if (Ls && !Lso) Lso = Ls;                      // one stride given: both sides
   if (Lso && !Ls) Ls = Lrows;
-  const int logN = r->logN, N = r->N;
-  const size_t toff = (size_t)limb0 * N;
-  const LimbConsts* c = r->d_consts + limb0;
-  hipStream_t st = rh_stream(r);
-  const unsigned rows = (unsigned)npoly * (unsigned)Lrows;
-  if (rows == 0) return RH_OK;
-  if (logN < LT) {
-    if (!inverse) {
-      if (lazy) ntt_fwd_small<MontPolicy><<<rows, 256, 0, st>>>(in, out, r->d_tw_fwd_mont + toff, c, Lrows, logN, 0, Ls, Lso);
-      else      ntt_fwd_small<ShoupPolicy><<<rows, 256, 0, st>>>(in, out, r->d_tw_fwd + toff, c, Lrows, logN, 1, Ls, Lso);
-    } else if (lazy && logN < 4 && r->d_tw_inv_mont && r->kind == RH_RING_STANDARD) {
-      if (Ls || Lso) return rh_fail(RH_ERR_UNSUPPORTED, "strided non-canonical BackwardLazy of N = 8");          // (ntt_rows compacts this one shape)
-      ntt_inv_small_lazy_mont<<<rows, 64, 0, st>>>(in, out, r->d_tw_inv_mont + toff, c, Lrows, logN);   // N = 8: BackwardLazy is not canonical
-    } else {
-      ntt_inv_small<<<rows, 256, 0, st>>>(in, out, r->d_tw_inv + toff, c, Lrows, logN, r->inv_scale ? 1 : 0, Ls, Lso);
-    }
-    return rh_launch_ok("ntt_small");
-  }
-  const int S1 = logN - LT;
-  const unsigned tiles = rows << S1;
-  const bool nt = rh_stream_grid(r, rows).nt;   // non-temporal data streams beyond the Infinity Cache
-  if (phase == 0 && !(lazy && !inverse) && one_pass_ok(r)) {          // (the forward lazy form keeps the reference's representatives: Montgomery bodies, two passes)
-    const size_t lds = ((size_t)LDS_WORDS * 8) << S1;
-    const dim3 wg(256u << S1);
-    const int sc = r->inv_scale ? 1 : 0;
-    const unsigned grid = rows;
-    if (!inverse) {
-      if (S1 == 1 && nt) ntt_fwd_onepass_asm<1, true><<<grid, wg, lds, st>>>(in, out, r->d_tw_fwd + toff, r->d_twk_fwd + toff, c, Lrows, Ls, Lso);
-      else if (S1 == 1) ntt_fwd_onepass_asm<1, false><<<grid, wg, lds, st>>>(in, out, r->d_tw_fwd + toff, r->d_twk_fwd + toff, c, Lrows, Ls, Lso);
-      else if (nt) ntt_fwd_onepass_asm<2, true><<<grid, wg, lds, st>>>(in, out, r->d_tw_fwd + toff, r->d_twk_fwd + toff, c, Lrows, Ls, Lso);
-      else ntt_fwd_onepass_asm<2, false><<<grid, wg, lds, st>>>(in, out, r->d_tw_fwd + toff, r->d_twk_fwd + toff, c, Lrows, Ls, Lso);
-    } else {
-      if (S1 == 1 && nt) ntt_inv_onepass_asm<1, true><<<grid, wg, lds, st>>>(in, out, r->d_twk_inv + toff, r->d_tw_inv + toff, r->d_lastw + limb0, c, Lrows, Ls, Lso, sc);
-      else if (S1 == 1) ntt_inv_onepass_asm<1, false><<<grid, wg, lds, st>>>(in, out, r->d_twk_inv + toff, r->d_tw_inv + toff, r->d_lastw + limb0, c, Lrows, Ls, Lso, sc);
-      else if (nt) ntt_inv_onepass_asm<2, true><<<grid, wg, lds, st>>>(in, out, r->d_twk_inv + toff, r->d_tw_inv + toff, r->d_lastw + limb0, c, Lrows, Ls, Lso, sc);
-      else ntt_inv_onepass_asm<2, false><<<grid, wg, lds, st>>>(in, out, r->d_twk_inv + toff, r->d_tw_inv + toff, r->d_lastw + limb0, c, Lrows, Ls, Lso, sc);
-    }
+  const NttRows x{in, out, npoly, Lrows, Ls, Lso};
+  if (x.rows() == 0) return RH_OK;
+  const int logN = r->logN, sc = r->inv_scale ? 1 : 0;
+  const NttTabs t = ntt_tabs(r, limb0);
+  if (logN < LT) return launch_small(t, rh_stream(r), logN, x, inverse, lazy, lazy && logN < 4 && r->d_tw_inv_mont && r->kind == RH_RING_STANDARD, sc);
+  const bool nt = rh_nt_rows(r, x.rows());      // non-temporal data streams beyond the Infinity Cache
+  if (!(lazy && !inverse) && one_pass_ok(r)) {          // (the forward lazy form keeps the reference's representatives: Montgomery bodies, two passes)
+    launch_onepass(t, rh_stream(r), logN - LT, x, inverse, nt, sc);
     return rh_launch_ok("ntt (one pass)");
   }
   if (!inverse) {
-    const u64* src = in;
-    if (S1 > 0) {
-      dim3 g1(rows * 16);
-      if (phase != 2) {
-        if (lazy) launch_fwd_cols<MontPolicy>(S1, g1, st, in, out, r->d_tw_fwd_mont + toff, c, Lrows, logN, Ls, Lso);
-        else if (S1 == 4 && r->asm_cols && r->asm_tile && nt) ntt_fwd_cols_asm<4, true><<<g1, 256, 0, st>>>(in, out, r->d_tw_fwd + toff, c, Lrows, Ls, Lso);
-        else if (S1 == 3 && r->asm_cols && r->asm_tile && nt) ntt_fwd_cols_asm<3, true><<<g1, 256, 0, st>>>(in, out, r->d_tw_fwd + toff, c, Lrows, Ls, Lso);
-        else if (S1 == 2 && r->asm_cols && r->asm_tile && nt) ntt_fwd_cols_asm<2, true><<<g1, 256, 0, st>>>(in, out, r->d_tw_fwd + toff, c, Lrows, Ls, Lso);
-        else if (S1 == 4 && r->asm_cols && r->asm_tile) ntt_fwd_cols_asm<4><<<g1, 256, 0, st>>>(in, out, r->d_tw_fwd + toff, c, Lrows, Ls, Lso);
-        else if (S1 == 3 && r->asm_cols && r->asm_tile) ntt_fwd_cols_asm<3><<<g1, 256, 0, st>>>(in, out, r->d_tw_fwd + toff, c, Lrows, Ls, Lso);
-        else if (S1 == 2 && r->asm_cols && r->asm_tile) ntt_fwd_cols_asm<2><<<g1, 256, 0, st>>>(in, out, r->d_tw_fwd + toff, c, Lrows, Ls, Lso);
-      else      launch_fwd_cols<ShoupPolicy>(S1, g1, st, in, out, r->d_tw_fwd + toff, c, Lrows, logN, Ls, Lso);
-      }
-      if (phase != 2) src = out;                   // phase 2 (tile stages only): the caller's `in` holds the column stages' output
-    }
-    if (phase != 1) {
-      // the tile stages read what the column stages wrote (the OUTPUT block, its stride on both sides); without column stages (N = 4096) they go in -> out
-      const int lso = Lso ? Lso : (Ls ? Ls : Lrows);
-      const int ls = (src == out) ? lso : (Ls ? Ls : Lrows);
-      if (lazy) ntt_fwd_tile<MontPolicy><<<tiles, 256, 0, st>>>(src, out, r->d_twk_fwd_mont + toff, c, Lrows, logN, 0, npoly, ls, lso);
-      else if (r->asm_tile && nt) ntt_fwd_tile_asm<true><<<tiles, 256, 0, st>>>(src, out, r->d_twk_fwd + toff, c, Lrows, logN, npoly, ls, lso);
-      else if (r->asm_tile) ntt_fwd_tile_asm<false><<<tiles, 256, 0, st>>>(src, out, r->d_twk_fwd + toff, c, Lrows, logN, npoly, ls, lso);
-      else      ntt_fwd_tile<ShoupPolicy><<<tiles, 256, 0, st>>>(src, out, r->d_twk_fwd + toff, c, Lrows, logN, 1, npoly, ls, lso);
-    }
+    span_fwd_cols(r, x, limb0, lazy);
+    span_fwd_tile(r, NttRows{logN > LT ? out : in, out, npoly, Lrows, Ls, Lso}, limb0, lazy);
   } else {
-    if (phase != 1) {
-      // the hand-scheduled body leaves values < 4q unscaled: right whenever column stages follow, and for N = 4096
-      // sub-rings of the 3N transform (inv_scale = false), which scale in their own last layer; N = 4096 WITH scaling: the same body, then N^-1 out of LDS
-      if (r->asm_tile && S1 == 0 && r->inv_scale && r->one_pass && phase == 0) {
-        if (nt) ntt_inv_onepass_asm<0, true><<<rows, 256, (size_t)LDS_WORDS * 8, st>>>(in, out, r->d_twk_inv + toff, r->d_tw_inv + toff, r->d_lastw + limb0, c, Lrows, Ls, Lso, 1);
-        else ntt_inv_onepass_asm<0, false><<<rows, 256, (size_t)LDS_WORDS * 8, st>>>(in, out, r->d_twk_inv + toff, r->d_tw_inv + toff, r->d_lastw + limb0, c, Lrows, Ls, Lso, 1);
-        return rh_launch_ok("ntt (N = 4096, inverse)");
-      }
-      if (r->asm_tile && (S1 > 0 || !r->inv_scale) && nt) ntt_inv_tile_asm<true><<<tiles, 256, 0, st>>>(in, out, r->d_twk_inv + toff, c, Lrows, logN, npoly, Ls, Lso);
-      else if (r->asm_tile && (S1 > 0 || !r->inv_scale)) ntt_inv_tile_asm<false><<<tiles, 256, 0, st>>>(in, out, r->d_twk_inv + toff, c, Lrows, logN, npoly, Ls, Lso);
-      else ntt_inv_tile<<<tiles, 256, 0, st>>>(in, out, r->d_twk_inv + toff, c, Lrows, logN, (S1 == 0 && r->inv_scale) ? 1 : 0, npoly, Ls, Lso);
+    if (r->asm_tile && logN == LT && r->inv_scale && r->one_pass) {          // N = 4096 WITH scaling: the tile body, then N^-1 out of LDS
+      launch_onepass(t, rh_stream(r), 0, x, true, nt, 1);
+      return rh_launch_ok("ntt (N = 4096, inverse)");
     }
-    const bool acols = phase != 2 && r->asm_cols && r->asm_tile && r->inv_scale;
-    if (S1 == 4 && acols && nt) ntt_inv_cols_asm<4, true><<<dim3(rows * 16), 256, 0, st>>>(out, r->d_tw_inv + toff, r->d_lastw + limb0, c, Lrows, Lso);
-    else if (S1 == 3 && acols && nt) ntt_inv_cols_asm<3, true><<<dim3(rows * 16), 256, 0, st>>>(out, r->d_tw_inv + toff, r->d_lastw + limb0, c, Lrows, Lso);
-    else if (S1 == 2 && acols && nt) ntt_inv_cols_asm<2, true><<<dim3(rows * 16), 256, 0, st>>>(out, r->d_tw_inv + toff, r->d_lastw + limb0, c, Lrows, Lso);
-    else if (S1 == 4 && acols) ntt_inv_cols_asm<4><<<dim3(rows * 16), 256, 0, st>>>(out, r->d_tw_inv + toff, r->d_lastw + limb0, c, Lrows, Lso);
-    else if (S1 == 3 && acols) ntt_inv_cols_asm<3><<<dim3(rows * 16), 256, 0, st>>>(out, r->d_tw_inv + toff, r->d_lastw + limb0, c, Lrows, Lso);
-    else if (S1 == 2 && acols) ntt_inv_cols_asm<2><<<dim3(rows * 16), 256, 0, st>>>(out, r->d_tw_inv + toff, r->d_lastw + limb0, c, Lrows, Lso);
-    else if (S1 > 0 && phase != 2) launch_inv_cols(S1, dim3(rows * 16), st, out, r->d_tw_inv + toff, r->d_lastw + limb0, c, Lrows, logN, r->inv_scale ? 1 : 0, Lso);
+    span_inv_tile(r, x, limb0);
+    span_inv_cols(r, x, limb0);
   }
   return rh_launch_ok("ntt");
 }
-
-template <int S1>
-static void launch_fused(rh_ring* r, const u64* in1, u64* out1, unsigned n1, u64* data2, unsigned n2, int npoly2,
-                         size_t toff, const LimbConsts* c, int Lrows) {
-  const unsigned grid = n1 > n2 ? n1 : n2;
-  hipStream_t st = rh_stream(r);
-  constexpr bool has_acols = S1 >= 2 && S1 <= 4;              // the hand-scheduled column stages exist for N = 2^14 .. 2^16 only: no instantiation elsewhere
-  if constexpr (has_acols) {
-    if (r->asm_tile && r->asm_cols) {
-      if (r->nt_streams) ntt_fwd_fused_asm<S1, true, true><<<grid, 256, 0, st>>>(in1, out1, n1, data2, n2, npoly2, r->d_tw_fwd + toff, r->d_twk_fwd + toff, c, Lrows, r->logN);
-      else ntt_fwd_fused_asm<S1, true, false><<<grid, 256, 0, st>>>(in1, out1, n1, data2, n2, npoly2, r->d_tw_fwd + toff, r->d_twk_fwd + toff, c, Lrows, r->logN);
-      return;
-    }
-  }
-  if (r->asm_tile)
-    ntt_fwd_fused_asm<S1, false><<<grid, 256, 0, st>>>(in1, out1, n1, data2, n2, npoly2, r->d_tw_fwd + toff, r->d_twk_fwd + toff, c, Lrows, r->logN);
-  else
-    ntt_fwd_fused<ShoupPolicy, S1><<<grid, 256, 0, st>>>(in1, out1, n1, data2, n2, npoly2, r->d_tw_fwd + toff, r->d_twk_fwd + toff,
-                                                      c, Lrows, r->logN, 1);
+// One stage of the two-pass transform (rh_ring_ntt_phase's profiling aid; bext.hip and ntt3n.hip, whose own kernels do the other stage):
+// 1 = column stages only (forward in -> out, inverse in place on out), 2 = tile stages only, in -> out.  Rings below N = 4096 have no stages:
+// the whole transform
+static int std_ntt_launch_stage(rh_ring* r, const u64* in, u64* out, int npoly, int Lrows, int limb0, bool inverse, int phase) {
+  if (r->logN < LT) return std_ntt_launch_span(r, in, out, npoly, Lrows, limb0, inverse, false);
+  (void)hipGetLastError();
+  const NttRows x{in, out, npoly, Lrows, 0, 0};
+  if (x.rows() == 0) return RH_OK;
+  if (phase == 1) inverse ? span_inv_cols(r, x, limb0) : span_fwd_cols(r, x, limb0, false);
+  else            inverse ? span_inv_tile(r, x, limb0) : span_fwd_tile(r, x, limb0, false);
+  return rh_launch_ok("ntt");
 }
 
-// Forward canonical transform of a large batch: software pipeline over spans of `chunk` polys in ONE stream; launch j
-// runs the column stages of span j fused with the tile stages of span j-1 (ntt_fwd_fused).  The spans may come from several
-// blocks (rh_ring_ntt_many): the pipeline runs through the block boundaries, so only the first launch of the first block and
-// the last launch of the last block are not fused.
+// ---- software pipelines over spans of polys in ONE stream: launch j works on span j and on span j-1 (and j-2)
+// Span size for a batch of npoly polys of Lrows limbs, 0 = no pipeline.  chunk_polys < 0 (auto): batches of more than ~auto_span_rows limb rows go in
+// spans of ~auto_span_rows rows (128 polys at 16 limbs; measured optimum: 64..128); > 0: that many polys per span; 0: never
+static int rh_span_polys(const rh_ring* r, int Lrows, long npoly) {
+  int chunk = r->chunk_polys;
+  if (chunk < 0) { chunk = r->auto_span_rows / (Lrows > 0 ? Lrows : 1); if (chunk < 1) chunk = 1; }
+  return chunk > 0 && npoly > chunk ? chunk : 0;
+}
+// The spans of one or several blocks (a block's last span may be shorter); outside [0, count()): 0 polys at the head of block 0, which is what launch j
+// asks for when span j or j-1 does not exist
+struct Span { int block, p0, polys; };
+struct SpanWalk {
+  std::vector<Span> spans;
+  void add(int block, int npoly, int chunk) { for (int p = 0; p < npoly; p += chunk) spans.push_back(Span{block, p, npoly - p < chunk ? npoly - p : chunk}); }
+  SpanWalk() {}
+  SpanWalk(int npoly, int chunk) { add(0, npoly, chunk); }
+  int count() const { return (int)spans.size(); }
+  Span operator()(int j) const { return j >= 0 && j < count() ? spans[j] : Span{0, 0, 0}; }
+};
+
+// Forward canonical transform of a large batch: launch j runs the column stages of span j fused with the tile stages of span j-1 (ntt_fwd_fused).
+// The spans may come from several blocks (rh_ring_ntt_many): the pipeline runs through the block boundaries, so only the first launch of the first
+// block and the last launch of the last block are not fused.
 struct NttSeg { const u64* in; u64* out; int npoly; };
 static int std_ntt_fwd_pipelined_segs(rh_ring* r, const NttSeg* segs, int nseg, int Lrows, int limb0, int chunk) {
   (void)hipGetLastError();
-  const int N = r->N, S1 = r->logN - LT;
-  const size_t toff = (size_t)limb0 * N, stride = (size_t)Lrows * N;
-  const LimbConsts* c = r->d_consts + limb0;
-  std::vector<NttSeg> spans;
-  for (int k = 0; k < nseg; ++k)
-    for (int p = 0; p < segs[k].npoly; p += chunk)
-      spans.push_back(NttSeg{segs[k].in + (size_t)p * stride, segs[k].out + (size_t)p * stride, segs[k].npoly - p < chunk ? segs[k].npoly - p : chunk});
-  const int nspans = (int)spans.size();
-  for (int j = 0; j <= nspans; ++j) {
-    const int n1p = j < nspans ? spans[j].npoly : 0, n2p = j >= 1 ? spans[j - 1].npoly : 0;
-    const unsigned n1 = (unsigned)n1p * Lrows * 16, n2 = ((unsigned)n2p * Lrows) << S1;
-    const u64* i1 = j < nspans ? spans[j].in : nullptr; u64* o1 = j < nspans ? spans[j].out : nullptr; u64* d2 = j >= 1 ? spans[j - 1].out : nullptr;
-    switch (S1) {
-      case 1: launch_fused<1>(r, i1, o1, n1, d2, n2, n2p, toff, c, Lrows); break;
-      case 2: launch_fused<2>(r, i1, o1, n1, d2, n2, n2p, toff, c, Lrows); break;
-      case 3: launch_fused<3>(r, i1, o1, n1, d2, n2, n2p, toff, c, Lrows); break;
-      case 4: launch_fused<4>(r, i1, o1, n1, d2, n2, n2p, toff, c, Lrows); break;
-      case 5: launch_fused<5>(r, i1, o1, n1, d2, n2, n2p, toff, c, Lrows); break;
-    }
+  const int logN = r->logN, S1 = logN - LT;
+  const size_t stride = (size_t)Lrows * r->N;
+  const NttTabs t = ntt_tabs(r, limb0);
+  hipStream_t st = rh_stream(r);
+  SpanWalk w;
+  for (int k = 0; k < nseg; ++k) w.add(k, segs[k].npoly, chunk);
+  for (int j = 0; j <= w.count(); ++j) {
+    const Span s1 = w(j), s2 = w(j - 1);
+    const unsigned n1 = (unsigned)s1.polys * Lrows * 16, n2 = ((unsigned)s2.polys * Lrows) << S1, grid = n1 > n2 ? n1 : n2;
+    const u64* in1 = segs[s1.block].in + (size_t)s1.p0 * stride; u64* out1 = segs[s1.block].out + (size_t)s1.p0 * stride;
+    u64* data2 = segs[s2.block].out + (size_t)s2.p0 * stride;
+    const int npoly2 = s2.polys;
+    if (r->asm_tile && r->asm_cols && rh_with_s1<2, 4>(S1, [&](auto S) { rh_with_flag(rh_nt_key(r), [&](auto NT) {
+          ntt_fwd_fused_asm<S(), true, NT()><<<grid, 256, 0, st>>>(in1, out1, n1, data2, n2, npoly2, t.tw_fwd, t.twk_fwd, t.c, Lrows, logN); }); })) continue;
+    rh_with_s1<1, 5>(S1, [&](auto S) {
+      if (r->asm_tile) ntt_fwd_fused_asm<S(), false, RH_NT_FUSED_DEFAULT><<<grid, 256, 0, st>>>(in1, out1, n1, data2, n2, npoly2, t.tw_fwd, t.twk_fwd, t.c, Lrows, logN);
+      else ntt_fwd_fused<ShoupPolicy, S()><<<grid, 256, 0, st>>>(in1, out1, n1, data2, n2, npoly2, t.tw_fwd, t.twk_fwd, t.c, Lrows, logN, 1);
+    });
   }
   return rh_launch_ok("ntt_fwd_fused");
 }
-static int std_ntt_fwd_pipelined(rh_ring* r, const u64* in, u64* out, int npoly, int Lrows, int limb0, int chunk) {
-  const NttSeg seg{in, out, npoly};
-  return std_ntt_fwd_pipelined_segs(r, &seg, 1, Lrows, limb0, chunk);
-}
 
-template <int S1>
-static void launch_inv_fused(rh_ring* r, const u64* in1, const u64* in1b, u64* out1, unsigned n1, int npoly1, u64* data2, unsigned n2,
-                             size_t toff, int limb0, const LimbConsts* c, int Lrows) {
-  const unsigned grid = n1 > n2 ? n1 : n2;
-  hipStream_t st = rh_stream(r);
-  constexpr bool has_acols = S1 >= 2 && S1 <= 4;              // (as launch_fused: no hand-scheduled column stages outside N = 2^14 .. 2^16)
-  const bool acols = has_acols && r->asm_cols;
-  if (in1b) {                 // rh_ring_intt_mul: product on load, 2^64-scaled N^-1 constants (c = d_consts_r + limb0)
-    const tw2* lw = r->d_lastw_r + limb0;
-    if constexpr (has_acols) {
-      if (acols) { ntt_inv_fused_asm<S1, true, true><<<grid, 256, 0, st>>>(in1, in1b, out1, n1, npoly1, data2, n2, r->d_twk_inv + toff, r->d_tw_inv + toff, lw, c, Lrows, r->logN); return; }
-    }
-    ntt_inv_fused_asm<S1, false, true><<<grid, 256, 0, st>>>(in1, in1b, out1, n1, npoly1, data2, n2, r->d_twk_inv + toff, r->d_tw_inv + toff, lw, c, Lrows, r->logN);
-    return;
-  }
-  const tw2* lw = r->d_lastw + limb0;
-  if constexpr (has_acols) {
-    if (acols && !r->nt_streams) { ntt_inv_fused_asm<S1, true, false, false><<<grid, 256, 0, st>>>(in1, nullptr, out1, n1, npoly1, data2, n2, r->d_twk_inv + toff, r->d_tw_inv + toff, lw, c, Lrows, r->logN); return; }
-    if (acols) { ntt_inv_fused_asm<S1, true, false><<<grid, 256, 0, st>>>(in1, nullptr, out1, n1, npoly1, data2, n2, r->d_twk_inv + toff, r->d_tw_inv + toff, lw, c, Lrows, r->logN); return; }
-  }
-  ntt_inv_fused_asm<S1, false, false><<<grid, 256, 0, st>>>(in1, nullptr, out1, n1, npoly1, data2, n2, r->d_twk_inv + toff, r->d_tw_inv + toff, lw, c, Lrows, r->logN);
-}
-// Inverse transform of a large batch: launch j = tile stages of span j fused with column stages (+ N^-1) of span j-1.
+// Inverse transform of a large batch (hand-scheduled tile body): launch j = tile stages of span j fused with column stages (+ N^-1) of span j-1.
+// in_b: rh_ring_intt_mul: the product a . b on load, 2^64-scaled N^-1 constants
 static int std_ntt_inv_pipelined(rh_ring* r, const u64* in, u64* out, int npoly, int Lrows, int limb0, int chunk, const u64* in_b = nullptr) {
   (void)hipGetLastError();
-  const int N = r->N, S1 = r->logN - LT;
-  const size_t toff = (size_t)limb0 * N, stride = (size_t)Lrows * N;
-  const LimbConsts* c = (in_b ? r->d_consts_r : r->d_consts) + limb0;
-  const int nspans = (npoly + chunk - 1) / chunk;
-  for (int j = 0; j <= nspans; ++j) {
-    const int p1 = j * chunk, n1p = j < nspans ? ((npoly - p1 < chunk) ? npoly - p1 : chunk) : 0;
-    const int p2 = (j - 1) * chunk, n2p = j >= 1 ? ((npoly - p2 < chunk) ? npoly - p2 : chunk) : 0;
-    const unsigned n1 = ((unsigned)n1p * Lrows) << S1, n2 = (unsigned)n2p * Lrows * 16;
-    const u64* i1 = in + (size_t)p1 * stride; u64* o1 = out + (size_t)p1 * stride; u64* d2 = out + (size_t)p2 * stride;
-    const u64* ib = in_b ? in_b + (size_t)p1 * stride : nullptr;
-    switch (S1) {
-      case 1: launch_inv_fused<1>(r, i1, ib, o1, n1, n1p, d2, n2, toff, limb0, c, Lrows); break;
-      case 2: launch_inv_fused<2>(r, i1, ib, o1, n1, n1p, d2, n2, toff, limb0, c, Lrows); break;
-      case 3: launch_inv_fused<3>(r, i1, ib, o1, n1, n1p, d2, n2, toff, limb0, c, Lrows); break;
-      case 4: launch_inv_fused<4>(r, i1, ib, o1, n1, n1p, d2, n2, toff, limb0, c, Lrows); break;
-      case 5: launch_inv_fused<5>(r, i1, ib, o1, n1, n1p, d2, n2, toff, limb0, c, Lrows); break;
-    }
+  const int logN = r->logN, S1 = logN - LT;
+  const size_t stride = (size_t)Lrows * r->N;
+  const NttTabs t = ntt_tabs(r, limb0, in_b != nullptr);
+  hipStream_t st = rh_stream(r);
+  const SpanWalk w(npoly, chunk);
+  for (int j = 0; j <= w.count(); ++j) {
+    const Span s1 = w(j), s2 = w(j - 1);
+    const unsigned n1 = ((unsigned)s1.polys * Lrows) << S1, n2 = (unsigned)s2.polys * Lrows * 16, grid = n1 > n2 ? n1 : n2;
+    const u64* in1 = in + (size_t)s1.p0 * stride; u64* out1 = out + (size_t)s1.p0 * stride; u64* data2 = out + (size_t)s2.p0 * stride;
+    const u64* in1b = in_b ? in_b + (size_t)s1.p0 * stride : nullptr;
+    const int npoly1 = s1.polys;
+    rh_with_flag(in_b != nullptr, [&](auto MUL) {
+      if (r->asm_cols && rh_with_s1<2, 4>(S1, [&](auto S) {
+            if constexpr (MUL()) ntt_inv_fused_asm<S(), true, true, RH_NT_FUSED_DEFAULT><<<grid, 256, 0, st>>>(in1, in1b, out1, n1, npoly1, data2, n2, t.twk_inv, t.tw_inv, t.lastw, t.c, Lrows, logN);
+            else rh_with_flag(rh_nt_key(r), [&](auto NT) {
+              ntt_inv_fused_asm<S(), true, false, NT()><<<grid, 256, 0, st>>>(in1, in1b, out1, n1, npoly1, data2, n2, t.twk_inv, t.tw_inv, t.lastw, t.c, Lrows, logN); });
+          })) return;
+      rh_with_s1<1, 5>(S1, [&](auto S) {
+        ntt_inv_fused_asm<S(), false, MUL(), RH_NT_FUSED_DEFAULT><<<grid, 256, 0, st>>>(in1, in1b, out1, n1, npoly1, data2, n2, t.twk_inv, t.tw_inv, t.lastw, t.c, Lrows, logN); });
+    });
   }
   return rh_launch_ok("ntt_inv_fused_asm");
 }
 
+// phase: 0 = whole transform; 1 / 2: std_ntt_launch_stage, the one place that reads it
 int rh_std_ntt_launch(rh_ring* r, const u64* in, u64* out, int npoly, int Lrows, int limb0, bool inverse, bool lazy, int phase) {
-  int chunk = r->chunk_polys;
-  if (chunk < 0) {                                  // auto: pipeline batches of more than ~2048 limb rows in spans of ~2048 rows
-    const int c = r->auto_span_rows / (Lrows > 0 ? Lrows : 1) > 0 ? r->auto_span_rows / Lrows : 1;   // 128 polys at 16 limbs (measured optimum: 64..128)
-    chunk = npoly > c ? c : 0;
-  }
+  if (phase) return std_ntt_launch_stage(r, in, out, npoly, Lrows, limb0, inverse, phase);
+  const int chunk = rh_span_polys(r, Lrows, npoly);
   const bool two_pass = r->logN > LT && !one_pass_ok(r);
-  if (chunk > 0 && two_pass && phase == 0 && !inverse && !lazy && npoly > chunk)
-    return std_ntt_fwd_pipelined(r, in, out, npoly, Lrows, limb0, chunk);
-  if (chunk > 0 && two_pass && phase == 0 && inverse && r->asm_tile && r->inv_scale && npoly > chunk)
-    return std_ntt_inv_pipelined(r, in, out, npoly, Lrows, limb0, chunk);
-  return std_ntt_launch_span(r, in, out, npoly, Lrows, limb0, inverse, lazy, phase);
+  if (chunk && two_pass && !inverse && !lazy) {
+    const NttSeg seg{in, out, npoly};
+    return std_ntt_fwd_pipelined_segs(r, &seg, 1, Lrows, limb0, chunk);
+  }
+  if (chunk && two_pass && inverse && r->asm_tile && r->inv_scale) return std_ntt_inv_pipelined(r, in, out, npoly, Lrows, limb0, chunk);
+  return std_ntt_launch_span(r, in, out, npoly, Lrows, limb0, inverse, lazy);
 }
 
 // Forward canonical transform, in place, of limbs [limb0, limb0 + Lrows) of each poly of a block that has Ls >= Lrows
@@ -632,7 +630,7 @@ int rh_std_ntt_launch(rh_ring* r, const u64* in, u64* out, int npoly, int Lrows,
 int rh_std_ntt_fwd_strided(rh_ring* r, u64* data, int npoly, int Lrows, int limb0, int Ls) {
   if (r->logN < LT || Ls < Lrows) return rh_fail(RH_ERR_ARG, "strided transform needs N >= 4096 and a row stride >= the row count");
   if (Lrows <= 0 || npoly <= 0) return RH_OK;
-  return std_ntt_launch_span(r, data, data, npoly, Lrows, limb0, false, false, 0, Ls);
+  return std_ntt_launch_span(r, data, data, npoly, Lrows, limb0, false, false, Ls);
 }
 
 // Forward canonical transform, in place, of the non-digit limbs of every digit block of a hybrid decomposition
@@ -672,11 +670,10 @@ int rh_std_ntt_fwd_blocks_small(rh_ring* r, u64* data, size_t block_stride, int 
   fill(ta, r, data, block_stride, nblocks, Ls, gap0, gap_len, false); fill(tb, r2, data2, block_stride2, nblocks2, Ls2, nullptr, nullptr, false);
   if (!n1) return RH_OK;
   const unsigned ny = (unsigned)(nblocks + (r2 ? nblocks2 : 0));
-#define RH_BLK(S) do { ntt_fwd_cols_blocks_asm<S><<<dim3(n1, ny), 256, 0, st>>>(ca, cb, npoly);                                  \
-                       if (lazy_out) ntt_fwd_tile_blocks_asm<S, true><<<dim3(n2, ny), 256, 0, st>>>(ta, tb, npoly);                \
-                       else ntt_fwd_tile_blocks_asm<S, false><<<dim3(n2, ny), 256, 0, st>>>(ta, tb, npoly); } while (0)
-  switch (S1) { case 2: RH_BLK(2); break; case 3: RH_BLK(3); break; case 4: RH_BLK(4); break; }
-#undef RH_BLK
+  rh_with_s1<2, 4>(S1, [&](auto S) {             // (cache policy: RH_NT_NEVER, the kernels have no other form)
+    ntt_fwd_cols_blocks_asm<S()><<<dim3(n1, ny), 256, 0, st>>>(ca, cb, npoly);
+    rh_with_flag(lazy_out, [&](auto LAZY) { ntt_fwd_tile_blocks_asm<S(), LAZY()><<<dim3(n2, ny), 256, 0, st>>>(ta, tb, npoly); });
+  });
   return rh_launch_ok("ntt_fwd_blocks (small batch)");
 }
 int rh_std_ntt_fwd_blocks(rh_ring* r, u64* data, size_t block_stride, int npoly, int nblocks, int Ls, const int* gap0, const int* gap_len,
@@ -692,7 +689,9 @@ int rh_std_ntt_fwd_blocks(rh_ring* r, u64* data, size_t block_stride, int npoly,
   };
   if (small < 0) small = r->ks_small_rows > 0 && (long)npoly * Ls <= r->ks_small_rows;
   if (small && nblocks <= 8) return rh_std_ntt_fwd_blocks_small(r, data, block_stride, nblocks, Ls, gap0, gap_len, nullptr, nullptr, 0, 0, 0, npoly, lazy_out);
-  for (int j = 0; j <= nblocks; ++j) {
+  // non-temporal data streams once a block is too large to be re-read from the Infinity Cache by the next launch's tile stages
+  const bool nt = rh_nt_gap(r, npoly, Ls);          // 256 MiB, not rh_stream_grid's 512: see above
+  for (int j = 0; j <= nblocks; ++j) {               // (every block is one span: launch j = column stages of block j, tile stages of block j-1)
     GapRows g1 = j < nblocks ? rows(j) : GapRows{1, 1, 0, 0}, g2 = j >= 1 ? rows(j - 1) : GapRows{1, 1, 0, 0};
     const unsigned n1 = j < nblocks ? (unsigned)npoly * g1.L * 16 : 0, n2 = j >= 1 ? ((unsigned)npoly * g2.L) << S1 : 0;
     const unsigned grid = n1 > n2 ? n1 : n2;
@@ -700,16 +699,8 @@ int rh_std_ntt_fwd_blocks(rh_ring* r, u64* data, size_t block_stride, int npoly,
     if (!g1.L) g1.L = 1;
     if (!g2.L) g2.L = 1;
     u64* d1 = data + (size_t)(j < nblocks ? j : 0) * block_stride; u64* d2 = data + (size_t)(j >= 1 ? j - 1 : 0) * block_stride;
-    // non-temporal data streams once a block is too large to be re-read from the Infinity Cache by the next launch's tile stages
-#define RH_GAP2(S, Z) do { if (nt) ntt_fwd_fused_gap_asm<S, Z, true><<<grid, 256, 0, st>>>(d1, n1, g1, d2, n2, npoly, g2, r->d_tw_fwd, r->d_twk_fwd, r->d_consts); \
-                           else ntt_fwd_fused_gap_asm<S, Z, false><<<grid, 256, 0, st>>>(d1, n1, g1, d2, n2, npoly, g2, r->d_tw_fwd, r->d_twk_fwd, r->d_consts); } while (0)
-    const bool nt = rh_nt_policy(r->nt_streams, (size_t)npoly * (size_t)Ls * (size_t)r->N * 8, (size_t)256 << 20);   // 256 MiB, not rh_stream_grid's 512: see above
-    switch (S1) {
-      case 2: if (lazy_out) RH_GAP2(2, true); else RH_GAP2(2, false); break;
-      case 3: if (lazy_out) RH_GAP2(3, true); else RH_GAP2(3, false); break;
-      case 4: if (lazy_out) RH_GAP2(4, true); else RH_GAP2(4, false); break;
-    }
-#undef RH_GAP2
+    rh_with_s1<2, 4>(S1, [&](auto S) { rh_with_flag(lazy_out, [&](auto LAZY) { rh_with_flag(nt, [&](auto NT) {
+      ntt_fwd_fused_gap_asm<S(), LAZY(), NT()><<<grid, 256, 0, st>>>(d1, n1, g1, d2, n2, npoly, g2, r->d_tw_fwd, r->d_twk_fwd, r->d_consts); }); }); });
   }
   return rh_launch_ok("ntt_fwd_fused_gap_asm");
 }
@@ -733,14 +724,10 @@ int rh_std_intt_limb_strided(rh_ring* r, const u64* in, int in_rows, int limb, u
   if (!rh_can_intt_limb_strided(r)) return rh_fail(RH_ERR_UNSUPPORTED, "strided single-limb inverse transform needs the hand-scheduled bodies");
   if (npoly <= 0) return RH_OK;
   (void)hipGetLastError();
-  const int S1 = r->logN - LT;
-  const size_t toff = (size_t)limb * r->N;
-  hipStream_t st = rh_stream(r);
-  ntt_inv_tile_asm<<<(unsigned)npoly << S1, 256, 0, st>>>(in + toff, out, r->d_twk_inv + toff, r->d_consts + limb, 1, r->logN, npoly, in_rows, 0);
-  const dim3 g((unsigned)npoly * 16);
-  if (S1 == 4) ntt_inv_cols_asm<4><<<g, 256, 0, st>>>(out, r->d_tw_inv + toff, r->d_lastw + limb, r->d_consts + limb, 1, 0);
-  else if (S1 == 3) ntt_inv_cols_asm<3><<<g, 256, 0, st>>>(out, r->d_tw_inv + toff, r->d_lastw + limb, r->d_consts + limb, 1, 0);
-  else ntt_inv_cols_asm<2><<<g, 256, 0, st>>>(out, r->d_tw_inv + toff, r->d_lastw + limb, r->d_consts + limb, 1, 0);
+  const NttTabs t = ntt_tabs(r, limb);
+  const NttRows x{in + (size_t)limb * r->N, out, npoly, 1, in_rows, 0};
+  launch_inv_tile(t, rh_stream(r), r->logN, x, BODY_ASM, RH_NT_NEVER, 0);
+  launch_inv_cols(t, rh_stream(r), r->logN, x, BODY_ASM, RH_NT_NEVER, 1);
   return rh_launch_ok("strided single-limb inverse transform");
 }
 
@@ -750,14 +737,10 @@ int rh_std_intt_rows(rh_ring* r, const u64* in, int in_rows, u64* out, int out_r
   if (!rh_can_intt_limb_strided(r)) return rh_fail(RH_ERR_UNSUPPORTED, "strided inverse transform needs the hand-scheduled bodies");
   if (npoly <= 0 || Lrows <= 0) return RH_OK;
   (void)hipGetLastError();
-  const int S1 = r->logN - LT;
-  hipStream_t st = rh_stream(r);
-  const unsigned rows = (unsigned)npoly * (unsigned)Lrows;
-  ntt_inv_tile_asm<<<rows << S1, 256, 0, st>>>(in, out, r->d_twk_inv, r->d_consts, Lrows, r->logN, npoly, in_rows, out_rows);
-  const dim3 g(rows * 16);
-  if (S1 == 4) ntt_inv_cols_asm<4><<<g, 256, 0, st>>>(out, r->d_tw_inv, r->d_lastw, r->d_consts, Lrows, out_rows);
-  else if (S1 == 3) ntt_inv_cols_asm<3><<<g, 256, 0, st>>>(out, r->d_tw_inv, r->d_lastw, r->d_consts, Lrows, out_rows);
-  else ntt_inv_cols_asm<2><<<g, 256, 0, st>>>(out, r->d_tw_inv, r->d_lastw, r->d_consts, Lrows, out_rows);
+  const NttTabs t = ntt_tabs(r, 0);
+  const NttRows x{in, out, npoly, Lrows, in_rows, out_rows};
+  launch_inv_tile(t, rh_stream(r), r->logN, x, BODY_ASM, RH_NT_NEVER, 0);
+  launch_inv_cols(t, rh_stream(r), r->logN, x, BODY_ASM, RH_NT_NEVER, 1);
   return rh_launch_ok("strided inverse transform");
 }
 
@@ -766,16 +749,10 @@ void rh_3n_launch_layer(bool inverse, int S1, unsigned nblocks, hipStream_t st, 
   // a unit moves 6 * 2^S1 coefficients per thread: nblocks * 256 * 6 * 2^S1 * 8 bytes per direction; non-temporal streams beyond 512 MiB
   // (rh_stream_grid's threshold on this launch's own byte count: its work comes in blocks, not in rows of N)
   const bool nt = rh_nt_policy(nt_streams, (size_t)nblocks * 256 * 6 * ((size_t)8 << S1), (size_t)512 << 20);   // tuning nt_streams = 0: default policy everywhere, 2: non-temporal at every size
-#define RH_3NL2(S, I) do { if (nt) ntt3n_layer_asm<S, I, true><<<nblocks, 256, 0, st>>>(in, out, a); else ntt3n_layer_asm<S, I, false><<<nblocks, 256, 0, st>>>(in, out, a); } while (0)
-#define RH_3NL(S) do { if (inverse) RH_3NL2(S, true); else RH_3NL2(S, false); } while (0)
-  if (S1 == 1) RH_3NL(1); else if (S1 == 2) RH_3NL(2); else RH_3NL(3);
-#undef RH_3NL
-#undef RH_3NL2
+  rh_with_s1<1, 3>(S1, [&](auto S) { rh_with_flag(inverse, [&](auto INV) { rh_with_flag(nt, [&](auto NT) {
+    ntt3n_layer_asm<S(), INV(), NT()><<<nblocks, 256, 0, st>>>(in, out, a); }); }); });
 }
 bool rh_can_fuse_submul(const rh_ring* r) { return r->kind == RH_RING_STANDARD && r->logN >= LT && r->fuse_submul; }
-// Forward canonical transform of `buf` (in place up to its tile stages) fused with out = MRed(2q - y + NTT(buf), s_limb):
-// column stages as usual, then ntt_fwd_tile_submul.  y / out: (poly, limb) blocks with y_rows / out_rows limbs per poly.
-// Cache policy of a launch's data streams: rh_stream_grid's nt (the generated bodies exist in both forms, tools/gen_tile_asm.py)
 
 // rescale: column stages of limbs 0..Lrows-1 fed by the re-expansion of the coefficient-domain last limb `tmp` (N >= 8192)
 int rh_std_ntt_expand_cols_launch(rh_ring* r, const u64* tmp, u64* buf, int npoly, int Lrows, const void* table_dev, int mode, u64 qL) {
@@ -786,30 +763,28 @@ int rh_std_ntt_expand_cols_launch(rh_ring* r, const u64* tmp, u64* buf, int npol
   (void)hipGetLastError();
   const RescaleLimb* T = (const RescaleLimb*)table_dev;
   const dim3 g(rows * 16);
-  bool lazy_ok = r->asm_tile && r->asm_cols && S1 >= 2 && S1 <= 4;      // hand-scheduled body: needs qL + q <= 8q for every limb
+  hipStream_t st = rh_stream(r);
+  bool lazy_ok = r->asm_tile && r->asm_cols;             // hand-scheduled body (N = 2^14 .. 2^16): needs qL + q <= 8q for every limb
   for (int i = 0; i < Lrows && lazy_ok; ++i) lazy_ok = qL / 7 <= r->moduli[i] && qL - 1 < 7 * r->moduli[i];
-  if (lazy_ok) {
-    const bool nt = rh_stream_grid(r, rows).nt;          // non-temporal data streams for working sets far beyond the Infinity Cache
-    switch (S1 * 2 + (nt ? 1 : 0)) {
-      case 4: ntt_fwd_cols_expand_asm<2, false><<<g, 256, 0, rh_stream(r)>>>(tmp, buf, r->d_tw_fwd, r->d_consts, T, Lrows, mode, qL); break;
-      case 5: ntt_fwd_cols_expand_asm<2, true><<<g, 256, 0, rh_stream(r)>>>(tmp, buf, r->d_tw_fwd, r->d_consts, T, Lrows, mode, qL); break;
-      case 6: ntt_fwd_cols_expand_asm<3, false><<<g, 256, 0, rh_stream(r)>>>(tmp, buf, r->d_tw_fwd, r->d_consts, T, Lrows, mode, qL); break;
-      case 7: ntt_fwd_cols_expand_asm<3, true><<<g, 256, 0, rh_stream(r)>>>(tmp, buf, r->d_tw_fwd, r->d_consts, T, Lrows, mode, qL); break;
-      case 8: ntt_fwd_cols_expand_asm<4, false><<<g, 256, 0, rh_stream(r)>>>(tmp, buf, r->d_tw_fwd, r->d_consts, T, Lrows, mode, qL); break;
-      case 9: ntt_fwd_cols_expand_asm<4, true><<<g, 256, 0, rh_stream(r)>>>(tmp, buf, r->d_tw_fwd, r->d_consts, T, Lrows, mode, qL); break;
-    }
+  const bool nt = rh_nt_rows(r, rows);                   // non-temporal data streams for working sets far beyond the Infinity Cache
+  if (lazy_ok && rh_with_s1<2, 4>(S1, [&](auto S) { rh_with_flag(nt, [&](auto NT) {
+        ntt_fwd_cols_expand_asm<S(), NT()><<<g, 256, 0, st>>>(tmp, buf, r->d_tw_fwd, r->d_consts, T, Lrows, mode, qL); }); }))
     return rh_launch_ok("ntt_fwd_cols_expand_asm");
-  }
-  switch (S1) {
-    case 1: ntt_fwd_cols_expand<1><<<g, 256, 0, rh_stream(r)>>>(tmp, buf, r->d_tw_fwd, r->d_consts, T, Lrows, r->logN, mode, qL); break;
-    case 2: ntt_fwd_cols_expand<2><<<g, 256, 0, rh_stream(r)>>>(tmp, buf, r->d_tw_fwd, r->d_consts, T, Lrows, r->logN, mode, qL); break;
-    case 3: ntt_fwd_cols_expand<3><<<g, 256, 0, rh_stream(r)>>>(tmp, buf, r->d_tw_fwd, r->d_consts, T, Lrows, r->logN, mode, qL); break;
-    case 4: ntt_fwd_cols_expand<4><<<g, 256, 0, rh_stream(r)>>>(tmp, buf, r->d_tw_fwd, r->d_consts, T, Lrows, r->logN, mode, qL); break;
-    case 5: ntt_fwd_cols_expand<5><<<dim3(rows * 16), 256, 0, rh_stream(r)>>>(tmp, buf, r->d_tw_fwd, r->d_consts, T, Lrows, r->logN, mode, qL); break;
-  }
+  rh_with_s1<1, 5>(S1, [&](auto S) { ntt_fwd_cols_expand<S()><<<g, 256, 0, st>>>(tmp, buf, r->d_tw_fwd, r->d_consts, T, Lrows, r->logN, mode, qL); });
   return rh_launch_ok("ntt_fwd_cols_expand");
 }
 
+// Forward canonical transform of `buf` (in place up to its tile stages) fused with out = MRed(2q - y + NTT(buf), s_limb):
+// column stages as usual, then ntt_fwd_tile_submul.  y / out: (poly, limb) blocks with y_rows / out_rows limbs per poly.
+// MRed by a limb's scalar = Shoup multiply by s * 2^-64 mod q: the by-value pack of limbs [limb0, limb0 + Lrows)
+static LimbShoup limb_shoup_pack(const rh_ring* r, int limb0, int Lrows, const u64* scalars_host) {
+  LimbShoup sh; memset(&sh, 0, sizeof(sh));
+  for (int i = 0; i < Lrows; ++i) {
+    const u64 q = r->moduli[limb0 + i];
+    sh.w[i] = rh::imform(scalars_host[i] % q, q); sh.wp[i] = rh::shoup_quotient(sh.w[i], q);
+  }
+  return sh;
+}
 // Both components of a ModDown in ONE launch: buf holds 2 * npoly polys (component 0 then component 1, column stages done), component c goes with
 // (y_c, out_c, z_c); z0 and z1 are both given or both null.  Hand-scheduled bodies only (the caller checks rh_can_fuse_submul and asm_tile).
 int rh_std_ntt_submul_launch_pair(rh_ring* r, u64* buf, int npoly, int Lrows, const u64* y0, const u64* y1, int y_rows, u64* out0, u64* out1, int out_rows,
@@ -819,16 +794,11 @@ int rh_std_ntt_submul_launch_pair(rh_ring* r, u64* buf, int npoly, int Lrows, co
   if (rows == 0) return RH_OK;
   const int S1 = r->logN - LT;
   (void)hipGetLastError();
-  LimbShoup sh; memset(&sh, 0, sizeof(sh));
-  for (int i = 0; i < Lrows; ++i) {
-    const u64 q = r->moduli[i];
-    sh.w[i] = rh::imform(scalars_host[i] % q, q); sh.wp[i] = rh::shoup_quotient(sh.w[i], q);
-  }
-  const bool nt = rh_stream_grid(r, rows / 2).nt;       // (the policy of one component's launch, as before)
+  const LimbShoup sh = limb_shoup_pack(r, 0, Lrows, scalars_host);
+  const bool nt = rh_nt_rows(r, rows / 2);              // (the policy of one component's launch, as before the two were paired)
   hipStream_t st = rh_stream(r);
-#define RH_SMP(ADD, NTF) ntt_fwd_tile_submul_asm<ADD, NTF><<<rows << S1, 256, 0, st>>>(buf, r->d_twk_fwd, r->d_consts, Lrows, r->logN, 2 * npoly, y0, y_rows, out0, out_rows, sh, z0, z_rows, npoly, y1, out1, z1)
-  if (z0 && nt) RH_SMP(true, true); else if (z0) RH_SMP(true, false); else if (nt) RH_SMP(false, true); else RH_SMP(false, false);
-#undef RH_SMP
+  rh_with_flag(z0 != nullptr, [&](auto ADD) { rh_with_flag(nt, [&](auto NT) {
+    ntt_fwd_tile_submul_asm<ADD(), NT()><<<rows << S1, 256, 0, st>>>(buf, r->d_twk_fwd, r->d_consts, Lrows, r->logN, 2 * npoly, y0, y_rows, out0, out_rows, sh, z0, z_rows, npoly, y1, out1, z1); }); });
   return rh_launch_ok("ntt_fwd_tile_submul_asm (pair)");
 }
 int rh_std_ntt_submul_launch(rh_ring* r, u64* buf, int npoly, int Lrows, int limb0, const u64* y, int y_rows, u64* out, int out_rows,
@@ -838,29 +808,21 @@ int rh_std_ntt_submul_launch(rh_ring* r, u64* buf, int npoly, int Lrows, int lim
   const unsigned rows = (unsigned)npoly * (unsigned)Lrows;
   if (rows == 0) return RH_OK;
   const int S1 = r->logN - LT;
-  if (S1 > 0 && !cols_done) if (int rc = rh_std_ntt_launch(r, buf, buf, npoly, Lrows, limb0, false, false, 1)) return rc;   // column stages only
   (void)hipGetLastError();
-  const size_t toff = (size_t)limb0 * r->N;
-  if (r->asm_tile) {                                   // MRed by the limb's scalar = Shoup multiply by s * 2^-64 mod q
-    LimbShoup sh; memset(&sh, 0, sizeof(sh));
-    for (int i = 0; i < Lrows; ++i) {
-      const u64 q = r->moduli[limb0 + i];
-      sh.w[i] = rh::imform(scalars_host[i] % q, q); sh.wp[i] = rh::shoup_quotient(sh.w[i], q);
-    }
-    const bool nt = rh_stream_grid(r, rows).nt;
-    if (z && nt) ntt_fwd_tile_submul_asm<true, true><<<rows << S1, 256, 0, rh_stream(r)>>>(buf, r->d_twk_fwd + toff, r->d_consts + limb0, Lrows, r->logN, npoly, y, y_rows,
-                                                                                               out, out_rows, sh, z, z_rows);
-    else if (z) ntt_fwd_tile_submul_asm<true, false><<<rows << S1, 256, 0, rh_stream(r)>>>(buf, r->d_twk_fwd + toff, r->d_consts + limb0, Lrows, r->logN, npoly, y, y_rows,
-                                                                                               out, out_rows, sh, z, z_rows);
-    else if (nt) ntt_fwd_tile_submul_asm<false, true><<<rows << S1, 256, 0, rh_stream(r)>>>(buf, r->d_twk_fwd + toff, r->d_consts + limb0, Lrows, r->logN, npoly, y, y_rows,
-                                                                                                out, out_rows, sh, nullptr, 0);
-    else ntt_fwd_tile_submul_asm<false, false><<<rows << S1, 256, 0, rh_stream(r)>>>(buf, r->d_twk_fwd + toff, r->d_consts + limb0, Lrows, r->logN, npoly, y, y_rows,
-                                                                                         out, out_rows, sh, nullptr, 0);
+  if (S1 > 0 && !cols_done) {
+    span_fwd_cols(r, NttRows{buf, buf, npoly, Lrows, 0, 0}, limb0, false);
+    if (int rc = rh_launch_ok("ntt")) return rc;
+  }
+  const NttTabs t = ntt_tabs(r, limb0);
+  hipStream_t st = rh_stream(r);
+  if (r->asm_tile) {
+    const LimbShoup sh = limb_shoup_pack(r, limb0, Lrows, scalars_host);
+    rh_with_flag(z != nullptr, [&](auto ADD) { rh_with_flag(rh_nt_rows(r, rows), [&](auto NT) {
+      ntt_fwd_tile_submul_asm<ADD(), NT()><<<rows << S1, 256, 0, st>>>(buf, t.twk_fwd, t.c, Lrows, r->logN, npoly, y, y_rows, out, out_rows, sh, z, ADD() ? z_rows : 0); }); });
     return rh_launch_ok("ntt_fwd_tile_submul_asm");
   }
   LimbScalars sc; memset(&sc, 0, sizeof(sc)); memcpy(sc.s, scalars_host, (size_t)Lrows * 8);
-  ntt_fwd_tile_submul<<<rows << S1, 256, 0, rh_stream(r)>>>(buf, r->d_twk_fwd + toff, r->d_consts + limb0, Lrows, r->logN, npoly, y, y_rows,
-                                                         out, out_rows, sc, z, z_rows);
+  ntt_fwd_tile_submul<<<rows << S1, 256, 0, st>>>(buf, t.twk_fwd, t.c, Lrows, r->logN, npoly, y, y_rows, out, out_rows, sc, z, z_rows);
   return rh_launch_ok("ntt_fwd_tile_submul");
 }
 
@@ -900,54 +862,47 @@ static int ci_ntt_launch(rh_ring* r, const u64* in, u64* out, int npoly, int Lro
   if (r->asm_tile && r->asm_cols && r->fuse_ci && S1 >= 2 && S1 <= 4) {
     // the fold rides in the column stages (a thread owns the column pair (c, 4096 - c) the fold couples; column 0 apart): no pass of its own
     hipStream_t st = rh_stream(r);
-    const size_t toff = (size_t)limb0 * r->N;
+    const NttTabs t = ntt_tabs(r, limb0);
     const CiFoldTw* cf = reinterpret_cast<const CiFoldTw*>(r->d_cifold + limb0);
-    const LimbConsts* c = r->d_consts + limb0;
     // large batches: the software pipeline of the standard ring's fused launches (spans of ~2048 rows): forward launch j = fold + column stages of
     // span j with the tile stages of span j-1; inverse launch j = tile stages of span j with the column stages + fold of span j-1 (round 3)
-    int chunk = r->chunk_polys;
-    if (chunk < 0) { const int c0 = r->auto_span_rows / Lrows > 0 ? r->auto_span_rows / Lrows : 1; chunk = npoly > c0 ? c0 : 0; }
-    if (chunk > 0 && npoly > chunk && r->inv_scale) {
-      const int nspans = (npoly + chunk - 1) / chunk;
+    if (const int chunk = rh_span_polys(r, Lrows, npoly); chunk && r->inv_scale) {
+      const SpanWalk w(npoly, chunk);
       const size_t stride = (size_t)Lrows * r->N;
-      const bool ntp = r->nt_streams != 0;
-      auto span = [&](int j, int* n) { const int p0 = j * chunk; *n = (j < 0 || j >= nspans) ? 0 : (npoly - p0 < chunk ? npoly - p0 : chunk); return (size_t)(j < 0 ? 0 : p0) * stride; };
-      for (int j = 0; j <= nspans; ++j) {
-        int p1, p2;
-        const size_t o1 = span(j, &p1), o2 = span(j - 1, &p2);
-        const unsigned rows1 = (unsigned)p1 * Lrows, rows2 = (unsigned)p2 * Lrows;
-        if (!inverse) {
-          const unsigned n1 = rows1 * 8, n2 = rows2 << S1, grid = n1 > n2 ? n1 : n2;
-#define RH_CIF(S) do { if (rows1) ci_col0_kernel<S, false><<<(rows1 + 63) / 64, 64, 0, st>>>(in + o1, out + o1, r->d_tw_fwd + toff, nullptr, cf, c, Lrows, rows1);                 \
-                       if (ntp) ntt_ci_fwd_fused_asm<S, true><<<grid, 256, 0, st>>>(in + o1, out + o1, n1, out + o2, n2, p2, r->d_tw_fwd + toff, r->d_twk_fwd + toff, cf, c, Lrows);   \
-                       else ntt_ci_fwd_fused_asm<S, false><<<grid, 256, 0, st>>>(in + o1, out + o1, n1, out + o2, n2, p2, r->d_tw_fwd + toff, r->d_twk_fwd + toff, cf, c, Lrows); } while (0)
-          if (S1 == 4) RH_CIF(4); else if (S1 == 3) RH_CIF(3); else RH_CIF(2);
-#undef RH_CIF
-        } else {
-          const unsigned n1 = rows1 << S1, n2 = rows2 * 8, grid = n1 > n2 ? n1 : n2;
-#define RH_CII(S) do { if (ntp) ntt_ci_inv_fused_asm<S, true><<<grid, 256, 0, st>>>(in + o1, out + o1, n1, p1, out + o2, n2, r->d_twk_inv + toff, r->d_tw_inv + toff, r->d_lastw + limb0, cf, c, Lrows);  \
-                       else ntt_ci_inv_fused_asm<S, false><<<grid, 256, 0, st>>>(in + o1, out + o1, n1, p1, out + o2, n2, r->d_twk_inv + toff, r->d_tw_inv + toff, r->d_lastw + limb0, cf, c, Lrows); \
-                       if (rows2) ci_col0_kernel<S, true><<<(rows2 + 63) / 64, 64, 0, st>>>(out + o2, out + o2, r->d_tw_inv + toff, r->d_lastw + limb0, cf, c, Lrows, rows2); } while (0)
-          if (S1 == 4) RH_CII(4); else if (S1 == 3) RH_CII(3); else RH_CII(2);
-#undef RH_CII
-        }
+      for (int j = 0; j <= w.count(); ++j) {
+        const Span s1 = w(j), s2 = w(j - 1);
+        const size_t o1 = (size_t)s1.p0 * stride, o2 = (size_t)s2.p0 * stride;
+        const unsigned rows1 = (unsigned)s1.polys * Lrows, rows2 = (unsigned)s2.polys * Lrows;
+        rh_with_s1<2, 4>(S1, [&](auto S) { rh_with_flag(rh_nt_key(r), [&](auto NT) {
+          if (!inverse) {
+            const unsigned n1 = rows1 * 8, n2 = rows2 << S1, grid = n1 > n2 ? n1 : n2;
+            if (rows1) ci_col0_kernel<S(), false><<<(rows1 + 63) / 64, 64, 0, st>>>(in + o1, out + o1, t.tw_fwd, nullptr, cf, t.c, Lrows, rows1);
+            ntt_ci_fwd_fused_asm<S(), NT()><<<grid, 256, 0, st>>>(in + o1, out + o1, n1, out + o2, n2, s2.polys, t.tw_fwd, t.twk_fwd, cf, t.c, Lrows);
+          } else {
+            const unsigned n1 = rows1 << S1, n2 = rows2 * 8, grid = n1 > n2 ? n1 : n2;
+            ntt_ci_inv_fused_asm<S(), NT()><<<grid, 256, 0, st>>>(in + o1, out + o1, n1, s1.polys, out + o2, n2, t.twk_inv, t.tw_inv, t.lastw, cf, t.c, Lrows);
+            if (rows2) ci_col0_kernel<S(), true><<<(rows2 + 63) / 64, 64, 0, st>>>(out + o2, out + o2, t.tw_inv, t.lastw, cf, t.c, Lrows, rows2);
+          }
+        }); });
       }
       return rh_launch_ok("conjugate-invariant transform (pipelined)");
     }
-    const unsigned g8 = rows * 8, g0 = (rows + 63) / 64;
-#define RH_CI(S, INV, SRC, TW, LW) do { ntt_cols_ci_asm<S, INV><<<g8, 256, 0, st>>>(SRC, out, TW, LW, cf, c, Lrows);  \
-                                        ci_col0_kernel<S, INV><<<g0, 64, 0, st>>>(SRC, out, TW, LW, cf, c, Lrows, rows); } while (0)
+    const NttRows x{inverse ? in : out, out, npoly, Lrows, 0, 0};          // the tile stages: forward in place after the column stages, inverse in -> out before them
+    auto cols = [&](auto INV, const u64* src, const tw2* tw, const tw2* lw) {
+      rh_with_s1<2, 4>(S1, [&](auto S) {
+        ntt_cols_ci_asm<S(), INV()><<<rows * 8, 256, 0, st>>>(src, out, tw, lw, cf, t.c, Lrows);
+        ci_col0_kernel<S(), INV()><<<(rows + 63) / 64, 64, 0, st>>>(src, out, tw, lw, cf, t.c, Lrows, rows);
+      });
+      return rh_launch_ok("ntt_cols_ci_asm");
+    };
     if (!inverse) {
-      if (S1 == 4) RH_CI(4, false, in, r->d_tw_fwd + toff, nullptr); else if (S1 == 3) RH_CI(3, false, in, r->d_tw_fwd + toff, nullptr);
-      else RH_CI(2, false, in, r->d_tw_fwd + toff, nullptr);
-      if (int rc = rh_launch_ok("ntt_cols_ci_asm")) return rc;
-      return rh_std_ntt_launch(r, out, out, npoly, Lrows, limb0, false, false, 2);          // tile stages
+      if (int rc = cols(std::false_type{}, in, t.tw_fwd, nullptr)) return rc;
+      span_fwd_tile(r, x, limb0, false);
+      return rh_launch_ok("ntt");
     }
-    if (int rc = rh_std_ntt_launch(r, in, out, npoly, Lrows, limb0, true, false, 2)) return rc;   // tile stages
-    if (S1 == 4) RH_CI(4, true, out, r->d_tw_inv + toff, r->d_lastw + limb0); else if (S1 == 3) RH_CI(3, true, out, r->d_tw_inv + toff, r->d_lastw + limb0);
-    else RH_CI(2, true, out, r->d_tw_inv + toff, r->d_lastw + limb0);
-#undef RH_CI
-    return rh_launch_ok("ntt_cols_ci_asm");
+    span_inv_tile(r, x, limb0);
+    if (int rc = rh_launch_ok("ntt")) return rc;
+    return cols(std::true_type{}, out, t.tw_inv, t.lastw);
   }
   if (!inverse) {
     ci_fold_kernel<<<dim3(rows, chunks), 256, 0, rh_stream(r)>>>(in, out, r->logN, r->d_cifold + limb0, r->d_consts + limb0, Lrows, 0);
@@ -968,7 +923,7 @@ int rh_ring_ntt_any(rh_ring* r, const u64* in, u64* out, int npoly, int Lrows, i
   return rh_std_ntt_launch(r, in, out, npoly, Lrows, limb0, inverse, false, 0);
 }
 
-static int ntt_batch(rh_ring* r, const uint64_t* in, uint64_t* out, int npoly, int level, bool inverse, bool lazy, int phase = 0) {
+static int ntt_batch(rh_ring* r, const uint64_t* in, uint64_t* out, int npoly, int level, bool inverse, bool lazy, int phase = 0) {   // phase: rh_ring_ntt_phase's way to rh_std_ntt_launch, nothing else
   if (!r || !in || !out) return rh_fail(RH_ERR_ARG, "ntt: null argument");
   if (level < 0 || level >= r->L) return rh_fail(RH_ERR_ARG, "ntt: level %d out of range [0,%d)", level, r->L);
   if (npoly < 0) return rh_fail(RH_ERR_ARG, "ntt: npoly < 0");
@@ -994,9 +949,8 @@ extern "C" int rh_ring_ntt_many(rh_ring* r, const uint64_t* const* in, uint64_t*
   }
   (void)hipSetDevice(r->device);
   const int Lrows = level + 1;
-  int chunk = r->chunk_polys;
-  if (chunk < 0) chunk = r->auto_span_rows / Lrows > 0 ? r->auto_span_rows / Lrows : 1;
-  if (r->kind == RH_RING_STANDARD && r->logN > LT && !one_pass_ok(r) && chunk > 0 && total > chunk) {
+  const int chunk = rh_span_polys(r, Lrows, total);          // (the blocks' polys together: the pipeline runs through the block boundaries)
+  if (r->kind == RH_RING_STANDARD && r->logN > LT && !one_pass_ok(r) && chunk) {
     std::vector<NttSeg> segs;
     for (int k = 0; k < nblocks; ++k) if (npoly[k] > 0) segs.push_back(NttSeg{in[k], out[k], npoly[k]});
     return std_ntt_fwd_pipelined_segs(r, segs.data(), (int)segs.size(), Lrows, 0, chunk);
@@ -1021,7 +975,7 @@ static int ntt_rows(rh_ring* r, const uint64_t* in, int in_rows, uint64_t* out, 
   // exception is the non-canonical BackwardLazy of N = 8, which compacts like the other ring types
   if (r->kind == RH_RING_STANDARD && !(inverse && lazy && r->logN < 4)) {
     ++r->stats_rows_direct;
-    return std_ntt_launch_span(r, in, out, npoly, level + 1, 0, inverse, lazy, 0, in_rows, out_rows);
+    return std_ntt_launch_span(r, in, out, npoly, level + 1, 0, inverse, lazy, in_rows, out_rows);
   }
   // conjugate-invariant and 3N rings: still ONE batched transform -- the leading limbs are compacted with a strided copy on the way in and / or
   // expanded on the way out (round 3; these shapes ran poly by poly before)
@@ -1099,17 +1053,11 @@ static int std_intt_mul_launch(rh_ring* r, const u64* a, const u64* b, u64* out,
   if (S1 > 0 && r->asm_tile) {
     // large batches: the software pipeline of std_ntt_inv_pipelined (tile stages of span j with the column stages of span j-1).
     // The output may alias an input: a span's tiles read (a, b) of that span only, before its column stages write them.
-    int chunk = r->chunk_polys;
-    if (chunk < 0) { const int c = r->auto_span_rows / Lrows > 0 ? r->auto_span_rows / Lrows : 1; chunk = npoly > c ? c : 0; }
-    if (chunk > 0 && npoly > chunk) return std_ntt_inv_pipelined(r, a, out, npoly, Lrows, 0, chunk, b);
+    if (const int chunk = rh_span_polys(r, Lrows, npoly)) return std_ntt_inv_pipelined(r, a, out, npoly, Lrows, 0, chunk, b);
     ntt_inv_tile_mul_asm<<<rows << S1, 256, 0, st>>>(a, b, out, r->d_twk_inv, r->d_consts_r, Lrows, logN, npoly);
   } else
-  ntt_inv_tile_mul<<<rows << S1, 256, 0, st>>>(a, b, out, r->d_twk_inv, r->d_consts_r, Lrows, logN, S1 == 0 ? 1 : 0, npoly);
-  if (S1 >= 2 && S1 <= 4 && r->asm_cols && r->asm_tile) {
-    if (S1 == 4) ntt_inv_cols_asm<4><<<dim3(rows * 16), 256, 0, st>>>(out, r->d_tw_inv, r->d_lastw_r, r->d_consts_r, Lrows, 0);
-    else if (S1 == 3) ntt_inv_cols_asm<3><<<dim3(rows * 16), 256, 0, st>>>(out, r->d_tw_inv, r->d_lastw_r, r->d_consts_r, Lrows, 0);
-    else ntt_inv_cols_asm<2><<<dim3(rows * 16), 256, 0, st>>>(out, r->d_tw_inv, r->d_lastw_r, r->d_consts_r, Lrows, 0);
-  } else if (S1 > 0) launch_inv_cols(S1, dim3(rows * 16), st, out, r->d_tw_inv, r->d_lastw_r, r->d_consts_r, Lrows, logN, 1);
+  ntt_inv_tile_mul<<<rows << S1, 256, 0, st>>>(a, b, out, r->d_twk_inv, r->d_consts_r, Lrows, logN, logN == LT ? 1 : 0, npoly);
+  launch_inv_cols(ntt_tabs(r, 0, true), st, logN, NttRows{out, out, npoly, Lrows, 0, 0}, r->asm_cols && r->asm_tile ? BODY_ASM : BODY_CPP, RH_NT_NEVER, 1);
   return rh_launch_ok("intt_mul");
 }
 extern "C" int rh_ring_intt_mul(rh_ring* r, const uint64_t* a, const uint64_t* b, uint64_t* out, int npoly, int level) {
@@ -1143,42 +1091,31 @@ extern "C" int rh_ring_polymul(rh_ring* r, uint64_t* a, uint64_t* b, uint64_t* o
   if (rows == 0) return RH_OK;
   (void)hipSetDevice(r->device);
   hipStream_t st = rh_stream(r);
-  int chunk = r->chunk_polys;
-  if (chunk < 0) { const int c = r->auto_span_rows / Lrows > 0 ? r->auto_span_rows / Lrows : 1; chunk = npoly > c ? c : 0; }
-  if (chunk > 0 && npoly > chunk) {
+  const NttTabs t = ntt_tabs(r, 0, true);
+  (void)hipGetLastError();
+  if (const int chunk = rh_span_polys(r, Lrows, npoly)) {
     // large batches: ONE stream of launches, launch j = column stages of span j + tile middle of span j-1 + inverse column stages of span j-2
-    (void)hipGetLastError();
-    const int nspans = (npoly + chunk - 1) / chunk;
+    const SpanWalk w(npoly, chunk);
     const size_t stride = (size_t)Lrows * r->N;
-    const bool nt = r->nt_streams != 0;                    // a pipelined batch is always far beyond the Infinity Cache (three blocks of >= 2048 rows)
-    auto span = [&](int j, int* n) { const int p0 = j * chunk; *n = (j < 0 || j >= nspans) ? 0 : (npoly - p0 < chunk ? npoly - p0 : chunk); return (size_t)(j < 0 ? 0 : p0) * stride; };
-    for (int j = 0; j < nspans + 2; ++j) {
-      int p1, p2, p3;
-      const size_t o1 = span(j, &p1), o2 = span(j - 1, &p2), o3 = span(j - 2, &p3);
-      const unsigned n1 = (unsigned)p1 * Lrows * 16, n2 = ((unsigned)p2 * Lrows) << S1, n3 = (unsigned)p3 * Lrows * 16;
+    for (int j = 0; j < w.count() + 2; ++j) {
+      const Span s1 = w(j), s2 = w(j - 1), s3 = w(j - 2);
+      const size_t o1 = (size_t)s1.p0 * stride, o2 = (size_t)s2.p0 * stride, o3 = (size_t)s3.p0 * stride;
+      const unsigned n1 = (unsigned)s1.polys * Lrows * 16, n2 = ((unsigned)s2.polys * Lrows) << S1, n3 = (unsigned)s3.polys * Lrows * 16;
       const unsigned grid = n1 > n2 ? (n1 > n3 ? n1 : n3) : (n2 > n3 ? n2 : n3);
       if (!grid) continue;
-#define RH_PM_FUSED(S) do { if (nt) ntt_polymul_fused_asm<S, true><<<grid, 256, 0, st>>>(a + o1, b + o1, n1, a + o2, b + o2, out + o2, n2, p2, out + o3, n3, r->d_tw_fwd, r->d_twk_fwd, \
-                                                                                          r->d_twk_inv, r->d_tw_inv, r->d_lastw_r, r->d_consts_r, Lrows, r->logN);                          \
-                            else ntt_polymul_fused_asm<S, false><<<grid, 256, 0, st>>>(a + o1, b + o1, n1, a + o2, b + o2, out + o2, n2, p2, out + o3, n3, r->d_tw_fwd, r->d_twk_fwd,      \
-                                                                                       r->d_twk_inv, r->d_tw_inv, r->d_lastw_r, r->d_consts_r, Lrows, r->logN); } while (0)
-      switch (S1) { case 1: RH_PM_FUSED(1); break; case 2: RH_PM_FUSED(2); break; case 3: RH_PM_FUSED(3); break; case 4: RH_PM_FUSED(4); break; default: RH_PM_FUSED(5); break; }
-#undef RH_PM_FUSED
+      rh_with_s1<1, 5>(S1, [&](auto S) { rh_with_flag(rh_nt_key(r), [&](auto NT) {     // (three blocks of >= 2048 rows)
+        ntt_polymul_fused_asm<S(), NT()><<<grid, 256, 0, st>>>(a + o1, b + o1, n1, a + o2, b + o2, out + o2, n2, s2.polys, out + o3, n3, t.tw_fwd, t.twk_fwd,
+                                                               t.twk_inv, t.tw_inv, t.lastw, t.c, Lrows, r->logN); }); });
     }
     return rh_launch_ok("polymul (pipelined)");
   }
-  if (int rc = std_ntt_launch_span(r, a, a, npoly, Lrows, 0, false, false, 1)) return rc;       // column stages only (phase 1), in place
-  if (int rc = std_ntt_launch_span(r, b, b, npoly, Lrows, 0, false, false, 1)) return rc;
-  (void)hipGetLastError();
-  if (rh_stream_grid(r, rows).nt) ntt_polymul_tile_asm<true><<<rows << S1, 256, 0, st>>>(a, b, out, r->d_twk_fwd, r->d_twk_inv, r->d_consts_r, Lrows, r->logN, npoly);
-  else ntt_polymul_tile_asm<false><<<rows << S1, 256, 0, st>>>(a, b, out, r->d_twk_fwd, r->d_twk_inv, r->d_consts_r, Lrows, r->logN, npoly);
-  const bool nt = rh_stream_grid(r, rows).nt;
-  if (S1 >= 2 && S1 <= 4 && r->asm_cols) {
-#define RH_PM_COLS(S) do { if (nt) ntt_inv_cols_asm<S, true><<<dim3(rows * 16), 256, 0, st>>>(out, r->d_tw_inv, r->d_lastw_r, r->d_consts_r, Lrows, 0); \
-                           else ntt_inv_cols_asm<S, false><<<dim3(rows * 16), 256, 0, st>>>(out, r->d_tw_inv, r->d_lastw_r, r->d_consts_r, Lrows, 0); } while (0)
-    if (S1 == 4) RH_PM_COLS(4); else if (S1 == 3) RH_PM_COLS(3); else RH_PM_COLS(2);
-#undef RH_PM_COLS
-  } else launch_inv_cols(S1, dim3(rows * 16), st, out, r->d_tw_inv, r->d_lastw_r, r->d_consts_r, Lrows, r->logN, 1);
+  for (u64* p : {a, b}) {                               // forward column stages, in place
+    span_fwd_cols(r, NttRows{p, p, npoly, Lrows, 0, 0}, 0, false);
+    if (int rc = rh_launch_ok("ntt")) return rc;
+  }
+  const bool nt = rh_nt_rows(r, rows);
+  rh_with_flag(nt, [&](auto NT) { ntt_polymul_tile_asm<NT()><<<rows << S1, 256, 0, st>>>(a, b, out, t.twk_fwd, t.twk_inv, t.c, Lrows, r->logN, npoly); });
+  launch_inv_cols(t, st, r->logN, NttRows{out, out, npoly, Lrows, 0, 0}, r->asm_cols ? BODY_ASM : BODY_CPP, nt, 1);
   return rh_launch_ok("polymul");
 }
 

@@ -5,6 +5,7 @@
 #include <mutex>
 #include <atomic>
 #include <cstdint>
+#include <type_traits>
 #include "../../include/ringhip.h"
 #include "ring_types.hip.hpp"
 
@@ -15,6 +16,18 @@ int rh_fail(int code, const char* fmt, ...);
 // The one cache-policy decision of every launch site (tuning nt_streams: 0 never, 1 by working set, 2 always): non-temporal data streams
 // once the bytes a launch moves reach the site's threshold.
 inline bool rh_nt_policy(int nt_streams, size_t bytes, size_t threshold) { return nt_streams == 2 || (nt_streams == 1 && bytes >= threshold); }
+// (each launch site's rule by name: rh_nt_rows and the lines after it, below rh_stream_grid)
+
+// A run-time value as a template argument: f(std::integral_constant<int, S1>{}) for Lo <= S1 <= Hi, else false -- nothing is instantiated outside
+// [Lo, Hi], so a range names exactly the kernels that exist -- and f(std::true_type{}) / f(std::false_type{}).  Inside f: kernel<S(), NT()><<<...>>>(...).
+template <int Lo, int Hi, class F> inline bool rh_with_s1(int S1, F&& f) {
+  if constexpr (Lo > Hi) return false;
+  else {
+    if (S1 == Lo) { f(std::integral_constant<int, Lo>{}); return true; }
+    return rh_with_s1<Lo + 1, Hi>(S1, f);
+  }
+}
+template <class F> inline void rh_with_flag(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
 
 struct rh_ring3n_state;   // ntt3n.hip
 struct CiFold { tw2 f, b; };   // conjugate-invariant fold twiddles roots_fwd[1], roots_bwd[1] (Shoup pairs)
@@ -79,6 +92,21 @@ int rh_launch_ok(const char* what);                          // RH_OK, or "<what
 struct RhStreamGrid { dim3 grid; int nt; };
 unsigned rh_stream_chunks(const rh_ring* r);                 // blockIdx.y extent alone (a launch with rows of its own: gadget_mac_all_kernel)
 RhStreamGrid rh_stream_grid(const rh_ring* r, unsigned rows);
+// ---- cache policy of the NTT launch sites (engine.hip, ntt3n.hip): non-temporal data streams when ...
+// span transforms (every stage, one-pass), expand + column stages, subtract-multiply, the unpipelined polymul: the rows' bytes reach 512 MiB
+inline bool rh_nt_rows(const rh_ring* r, unsigned rows) { return rh_stream_grid(r, rows).nt != 0; }
+// pipelined launches with hand-scheduled columns (forward / inverse fused, conjugate-invariant pair, polymul fused): the key alone -- a pipelined
+// batch (several spans of ~2048 rows) is always far beyond the Infinity Cache
+inline bool rh_nt_key(const rh_ring* r) { return r->nt_streams != 0; }
+// pipelined launches with the compiled column stages (ntt_fwd_fused_asm<S, false>, ntt_inv_fused_asm<S, false, ...>) and the product-on-load inverse
+// (MUL) arms: the kernels' template default, whatever the key says (nt_streams = 0 does not reach their default-policy form)
+constexpr bool RH_NT_FUSED_DEFAULT = true;
+// digit blocks (rh_std_ntt_fwd_blocks): a block's bytes reach 256 MiB, the Infinity Cache itself -- the next launch's tile stages re-read the block
+inline bool rh_nt_gap(const rh_ring* r, int npoly, int Ls) { return rh_nt_policy(r->nt_streams, (size_t)npoly * (size_t)Ls * (size_t)r->N * 8, (size_t)256 << 20); }
+// small-batch blocks, the strided inverse transforms (limb, rows) and rh_ring_intt_mul's unpipelined launches: default policy always (nt_streams = 2
+// does not reach the non-temporal forms that exist for their tile and column kernels)
+constexpr bool RH_NT_NEVER = false;
+// (the 3N layer counts its own bytes: rh_3n_launch_layer)
 inline RhStreamGrid rh_stream_begin(const rh_ring* r, unsigned rows) {   // ... on the ring's device, any stale error of an earlier call dropped
   (void)hipSetDevice(r->device);
   (void)hipGetLastError();

@@ -504,17 +504,13 @@ static int ensure_tmp(rh_ring3n_state* s, size_t words) {
 static void launch_pre_cols_fwd(rh_ring* r, int S1sub, dim3 g, hipStream_t st, const u64* in, u64* out, int N, const tw2* r3, int r3_stride,
                                 const Limb3N* l3, const LimbConsts* c, int Lrows, const tw2* stw, int log_n2) {
   if (r->asm_tile) { rh_3n_launch_layer(false, S1sub, g.x, st, in, out, N3Layer{r3, r3_stride, l3, c, Lrows, stw, N}, r->nt_streams); return; }
-  if (S1sub == 1) ntt3n_pre_cols_fwd<1><<<g, 256, 0, st>>>(in, out, N, r3, r3_stride, l3, c, Lrows, stw, log_n2);
-  else if (S1sub == 2) ntt3n_pre_cols_fwd<2><<<g, 256, 0, st>>>(in, out, N, r3, r3_stride, l3, c, Lrows, stw, log_n2);
-  else ntt3n_pre_cols_fwd<3><<<g, 256, 0, st>>>(in, out, N, r3, r3_stride, l3, c, Lrows, stw, log_n2);
+  rh_with_s1<1, 3>(S1sub, [&](auto S) { ntt3n_pre_cols_fwd<S()><<<g, 256, 0, st>>>(in, out, N, r3, r3_stride, l3, c, Lrows, stw, log_n2); });
 }
 
 static void launch_cols_post_inv(rh_ring* r, int S1sub, dim3 g, hipStream_t st, const u64* in, u64* out, int N, const tw2* r3, int r3_stride,
                                  const Limb3N* l3, const LimbConsts* c, int Lrows, const tw2* stw, int log_n2) {
   if (r->asm_tile) { rh_3n_launch_layer(true, S1sub, g.x, st, in, out, N3Layer{r3, r3_stride, l3, c, Lrows, stw, N}, r->nt_streams); return; }   // hand-scheduled body (tuning asm_tile = 0: the compiled kernel)
-  if (S1sub == 1) ntt3n_cols_post_inv<1><<<g, 256, 0, st>>>(in, out, N, r3, r3_stride, l3, c, Lrows, stw, log_n2);
-  else if (S1sub == 2) ntt3n_cols_post_inv<2><<<g, 256, 0, st>>>(in, out, N, r3, r3_stride, l3, c, Lrows, stw, log_n2);
-  else ntt3n_cols_post_inv<3><<<g, 256, 0, st>>>(in, out, N, r3, r3_stride, l3, c, Lrows, stw, log_n2);
+  rh_with_s1<1, 3>(S1sub, [&](auto S) { ntt3n_cols_post_inv<S()><<<g, 256, 0, st>>>(in, out, N, r3, r3_stride, l3, c, Lrows, stw, log_n2); });
 }
 
 bool rh_ring3n_block_order_ok(const rh_ring* r) { const rh_ring3n_state* s = r->s3n; return s && s->b == 1 && s->sub && s->log_n2 >= LT; }

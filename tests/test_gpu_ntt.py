@@ -273,6 +273,67 @@ def test_fused_pipeline_spans_give_identical_results(rh, oracle, logN, chunk):
     ring.close()
 
 
+_SPAN_REF = {}
+
+
+def _span_reference(rh, oracle):
+    """operands and oracle values of test_span_boundaries for 4 polys, computed once; a case takes the leading npoly polys (block() puts
+    the all-(q - 1) poly and the poly that is zero at even indices first)"""
+    if not _SPAN_REF:
+        from oracle import primes
+        from test_gpu_cache_policy import _products, block, fwd_all
+        N, mods = 1 << 13, QI60[:2]
+        srs = [oracle.SubRingConsts(N, q) for q in mods]
+        rng = np.random.default_rng(4242)
+        a, b = block(rng, mods, 4, N), block(rng, mods, 4, N)
+        _SPAN_REF["std"] = (N, mods, a, b, fwd_all(oracle, a, srs), _products(oracle, rh, a, b, mods, srs, False), _products(oracle, rh, a, b, mods, srs, True))
+        Nc = 1 << 14
+        cmods = [int(q) for q in primes.gen_moduli(16, [50, 40], [])[0]]            # NthRoot = 4N
+        csrs = [oracle.SubRingConsts(Nc, q, nthroot=4 * Nc) for q in cmods]
+        ac = block(rng, cmods, 4, Nc)
+        _SPAN_REF["ci"] = (Nc, cmods, ac, fwd_all(oracle, ac, csrs, oracle.ntt_ci))
+    return _SPAN_REF
+
+
+@pytest.mark.parametrize("npoly,chunk", [(2, 1), (3, 1), (3, 2), (4, 2), (2, 2)])
+def test_span_boundaries(rh, oracle, npoly, chunk):
+    """every software pipeline with a span boundary at each place a span walker can be off by one: a last span of one poly, an exact
+    multiple, spans of one poly, and npoly == chunk (no pipeline).  Every output whole against the oracle"""
+    ref = _span_reference(rh, oracle)
+    N, mods, a, b, y, want_im, want_pm = ref["std"]
+    a, b, y, want_im, want_pm = a[:npoly], b[:npoly], y[:npoly], want_im[:npoly], want_pm[:npoly]
+    ring = rh.Ring(N, mods)
+    ring.set_tuning("one_pass", 0)
+    ring.set_tuning("chunk_polys", chunk)
+    p, o = rh.DevicePoly.from_numpy(ring, a), ring.NewPoly(npoly)
+    ring.NTT(p, o)
+    assert np.array_equal(o.numpy(), y), "NTT"
+    assert np.array_equal(p.numpy(), a), "NTT input"
+    ring.INTT(o, p)
+    assert np.array_equal(p.numpy(), a), "INTT"
+    ring.INTT(o, o)
+    assert np.array_equal(o.numpy(), a), "INTT in place"
+    ring.INTTMul(rh.DevicePoly.from_numpy(ring, a), rh.DevicePoly.from_numpy(ring, b), o)
+    assert np.array_equal(o.numpy(), want_im), "INTTMul"
+    ring.PolyMul(rh.DevicePoly.from_numpy(ring, a), rh.DevicePoly.from_numpy(ring, b), o)       # (its operands are consumed)
+    assert np.array_equal(o.numpy(), want_pm), "PolyMul"
+    ps = [rh.DevicePoly.from_numpy(ring, a[:1]), rh.DevicePoly.from_numpy(ring, a[1:])]         # two blocks: 1 poly, the rest
+    outs = [ps[0], ring.NewPoly(npoly - 1)]                                                       # in place, out of place
+    ring.NTTMany(list(zip(ps, outs)))
+    assert np.array_equal(outs[0].numpy(), y[:1]) and np.array_equal(outs[1].numpy(), y[1:]), "NTTMany"
+    ring.close()
+    Nc, cmods, ac, yc = ref["ci"]
+    ac, yc = ac[:npoly], yc[:npoly]
+    ring = rh.Ring(Nc, cmods, kind=rh.ConjugateInvariant)
+    ring.set_tuning("chunk_polys", chunk)
+    p, o = rh.DevicePoly.from_numpy(ring, ac), ring.NewPoly(npoly)
+    ring.NTT(p, o)
+    assert np.array_equal(o.numpy(), yc), "conjugate-invariant NTT"
+    ring.INTT(o, p)
+    assert np.array_equal(p.numpy(), ac), "conjugate-invariant INTT"
+    ring.close()
+
+
 @pytest.mark.parametrize("logN,chunk", [(10, -1), (13, 2), (15, 3), (16, -1)])
 def test_ntt_many_blocks_equal_separate_calls(rh, oracle, logN, chunk):
     # rh_ring_ntt_many: one software pipeline through several blocks (in place and out of place) == one Ring.NTT per block == oracle

@@ -4,8 +4,11 @@
     rocprofv3 --kernel-trace --stats -d DIR -o NAME --output-format csv -- python -m pytest tests/test_gpu_cache_policy.py -m gpu
     python tools/kernel_coverage.py matrix-fhe-lattigo_amd/lib/libringhip.so DIR/**/NAME_kernel_trace.csv > profiles/cache_policy_kernel_coverage.txt
 
+    python tools/kernel_coverage.py --multiset DIR/**/NAME_kernel_trace.csv > profiles/ntt_launch_multiset.txt
+
 Lists the kernels of the library's gfx950 code objects (the .hip_fatbin section's offload bundles, symbols with a kernel descriptor) and
-counts each one's launches in the trace.  NT_ARG names, per kernel family, the template argument that selects non-temporal data streams."""
+counts each one's launches in the trace.  --multiset: the sorted multiset of (kernel, grid, workgroup, LDS bytes) with its count, to compare
+the launches of two builds over the same tests.  NT_ARG names, per kernel family, the template argument that selects non-temporal data streams."""
 import collections
 import csv
 import os
@@ -74,6 +77,17 @@ def trace_counts(paths):
     return n
 
 
+def launch_multiset(paths):
+    """Counter of (kernel, grid, workgroup, LDS bytes); grid and workgroup as the trace gives them (one column, or _X/_Y/_Z)"""
+    n = collections.Counter()
+    for p in paths:
+        with open(p, newline="") as f:
+            for row in csv.DictReader(f):
+                dims = lambda key: "x".join(row[c] for c in sorted(row) if c.startswith(key))
+                n[(short(row.get("Kernel_Name") or row.get("Name") or ""), dims("Grid_Size"), dims("Workgroup_Size"), row.get("LDS_Block_Size", ""))] += 1
+    return n
+
+
 def nt_of(kernel):
     fam, _, rest = kernel.partition("<")
     if fam not in NT_ARG or not rest:
@@ -83,6 +97,10 @@ def nt_of(kernel):
 
 
 def main():
+    if sys.argv[1] == "--multiset":
+        for (k, g, w, lds), c in sorted(launch_multiset(sys.argv[2:]).items()):
+            print("%-64s grid %-16s workgroup %-10s lds %-7s x %d" % (k, g, w, lds, c))
+        return
     lib, traces = sys.argv[1], sys.argv[2:]
     kernels, seen = library_kernels(lib), trace_counts(traces)
     nt = [k for k in kernels if nt_of(k)[1] is True]
