@@ -598,6 +598,39 @@ size_t rh_ckks_linear_combination_table_words(int nterms, int level);
 int rh_ckks_linear_combination_chunk(void);
 int rh_ckks_linear_combination_width(void);
 
+/* ---- homomorphic DFT (circuits/ckks/dft/dft.go) ---------------------------------------------------------------------------------------
+ * The real / imaginary split after CoeffsToSlots and the merge before SlotsToCoeffs, each ONE launch over both components of a batch
+ * (standard rings; blocks (npoly, level + 1, N), NTT domain; z, zc, re, im, out: HOST arrays of the two components' device blocks):
+ *   rh_ckks_split_real_imag  re = zc + z, im = (z - zc) (-i): Sub, Mul(-1i), Add of dft.go:267-278 (zc = Conjugate(z))
+ *   rh_ckks_merge_real_imag  out = im i + re: Mul(1i), Add of :324-330
+ * s0 / s1: the double RNS scalar of -i / i as rh_ckks_scalar takes it.  An output may BE an input block (out = im, out = re, re = zc ...);
+ * partial overlaps are refused.
+ * GenMatrices (:644-773) on the device, float64: values are complex128 (re, im interleaved); a factor is one (ndiag, dslots) block with
+ * dslots = slots or 2 slots (sparse RepackImagAsReal).  The ring handle gives the device and the stream.
+ *   rh_ckks_dft_level_vectors  abc_dev (3, dslots) = a, b, c of fftPlainVec (decode != 0) / ifftPlainVec at fft_level in [1, log_slots]
+ *                            (a[logSlots - fftLevel] of :362-490), the second copy for dslots = 2 slots, every block of `slots` values
+ *                            bit-reversed when bit_reversed.  roots_dev: the 4 slots + 1 complex doubles of GetRootsComplex128(4 slots);
+ *                            pow5_dev: 5^j mod 4 slots as 64-bit words, at least slots / 2 of them.
+ *   rh_ckks_dft_merge_level  out_dev (nout, dslots): per output diagonal d the sum of up to three contributions, FIRST COPIED, THEN ADDED IN
+ *                            THE ORDER GIVEN.  program: HOST array of nout * 3 (source, kind) int pairs; source -2: none, -1: the level's
+ *                            vector itself (genFFTDiagMatrix :775-804), else row `source` of vec_dev (nin, dslots) times the vector
+ *                            (multiplyFFTMatrixWithNextFFTLevel :831-862); kind 0: a and the source as it is, 1: b and the source rotated by
+ *                            rot, 2: c and the source rotated by -rot, modulo dslots.  A complex product is four rounded products, one
+ *                            rounded difference and one rounded sum.  table_dev: device scratch of the caller, 3 nout words.
+ *   rh_ckks_dft_finish       out[d][x] = in[d][(x + rots[d]) mod dslots] * scaling on both parts (rots: HOST array or NULL: no rotation, and
+ *                            out_dev may be in_dev), slots [dslots / 2, dslots) of the source taken as zero when zero_upper (:733-740).
+ *                            table_dev: device scratch of ndiag words when rots is given. */
+int rh_ckks_split_real_imag(rh_ring* r, int level, const uint64_t* const* z_dev, const uint64_t* const* zc_dev, uint64_t* const* re_dev,
+                            uint64_t* const* im_dev, int npoly, const uint64_t* s0, const uint64_t* s1);
+int rh_ckks_merge_real_imag(rh_ring* r, int level, const uint64_t* const* re_dev, const uint64_t* const* im_dev, uint64_t* const* out_dev,
+                            int npoly, const uint64_t* s0, const uint64_t* s1);
+int rh_ckks_dft_level_vectors(rh_ring* r, int decode, int log_slots, unsigned dslots, int fft_level, int bit_reversed, const double* roots_dev,
+                              size_t nroots, const uint64_t* pow5_dev, size_t npow5, double* abc_dev);
+int rh_ckks_dft_merge_level(rh_ring* r, unsigned dslots, int rot, const double* abc_dev, const double* vec_dev, int nin, const int* program,
+                            int nout, double* out_dev, uint64_t* table_dev, size_t table_words);
+int rh_ckks_dft_finish(rh_ring* r, unsigned dslots, int ndiag, const double* in_dev, double* out_dev, double scaling, int zero_upper,
+                       const int* rots, uint64_t* table_dev, size_t table_words);
+
 /* ---- CKKS encoder: the float64 path of schemes/ckks/encoder.go on device batches of nvec vectors ------------------------------------
  * A handle on a STANDARD ring.  Refused by name (RH_ERR_UNSUPPORTED): conjugate-invariant rings, 3N rings, prec > 53 (the *big.Float /
  * *bignum.Complex encoder), rh_ckks_decode with batched = 0 at a level that is neither 0 nor the ring's top level.  Values are IEEE doubles, complex values interleaved (re, im); a block of

@@ -15,3 +15,4 @@ from . import blindrot  # noqa: F401,E402
 from . import bgv  # noqa: F401,E402
 from . import polynomial  # noqa: F401,E402
 from . import lintrans  # noqa: F401,E402
+from . import dft  # noqa: F401,E402

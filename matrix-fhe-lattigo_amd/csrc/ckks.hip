@@ -152,6 +152,38 @@ ckks_scale_then_add_kernel(CkksComps p, unsigned n, const LimbConsts* __restrict
   }
 }
 
+// ---- real / imaginary split and merge of the homomorphic DFT (circuits/ckks/dft/dft.go) -----------------------------------------------------
+struct CkksPair { const u64* a[2]; const u64* b[2]; u64* o0[2]; u64* o1[2]; };
+
+// SPLIT: a = z, b = zc = Conjugate(z); o0 = re = CRed(zc + z) (Add, :276), o1 = im = MRed(CRed(z + q - zc), MForm(-i)) (Sub :267, Mul :271).
+// else:  a = re, b = im; o0 = out = CRed(MRed(im, MForm(i)) + re) (Mul :324, Add :328).  The scalar as ckks_scalar_kernel takes it: s.a on
+// coefficients [0, N/2), s.b on [N/2, N), in Montgomery form.  Both components in one launch; 5 reads and 3 writes of a row become 2 and 2.
+template <bool SPLIT>
+__global__ void __launch_bounds__(256)
+ckks_real_imag_kernel(CkksPair p, unsigned n, const LimbConsts* __restrict__ consts, int L, RhScalars s, int nt) {
+  const StreamRow row(consts, L, n);
+  const LimbConsts& c = row.c;
+  const u64 sa = s.a[row.limb], sb = s.b[row.limb];
+  const unsigned half = n >> 2;
+  RH_FOR_EACH_PAIR(i, 0, n >> 1) {
+    const size_t o = row.ro + 2 * (size_t)i;
+    const u64 sc = i < half ? sa : sb;
+    ulonglong2 x[2], y[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) { x[j] = rh_ld2(p.a[j] + o, nt); y[j] = rh_ld2(p.b[j] + o, nt); }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      if (SPLIT) {
+        const ulonglong2 re = make_ulonglong2(cred(y[j].x + x[j].x, c.q), cred(y[j].y + x[j].y, c.q));
+        const ulonglong2 im = make_ulonglong2(mred(cred(x[j].x + c.q - y[j].x, c.q), sc, c.q, c.qinv), mred(cred(x[j].y + c.q - y[j].y, c.q), sc, c.q, c.qinv));
+        rh_st2(p.o0[j] + o, re, nt); rh_st2(p.o1[j] + o, im, nt);
+      } else {
+        rh_st2(p.o0[j] + o, make_ulonglong2(cred(mred(y[j].x, sc, c.q, c.qinv) + x[j].x, c.q), cred(mred(y[j].y, sc, c.q, c.qinv) + x[j].y, c.q)), nt);
+      }
+    }
+  }
+}
+
 // ---- linear combination ---------------------------------------------------------------------------------------------------------------
 // The 128-bit accumulate-then-reduce, its chunk bound (LC_CHUNK, LC_WIDTH, LC_MODULUS_BITS) and lc_reduce: lc_reduce.hip.hpp, shared with lintrans.hip.
 // The device table of a call, in words: the constant's scalars a[L], b[L] (coefficients [0, N/2), [N/2, N)), then per term
@@ -312,6 +344,61 @@ extern "C" int rh_ckks_scale_then_add(rh_ring* r, int level, const uint64_t* a0,
   const CkksComps p{{a0, a1, a2}, {b0, b1, b2}, {out0, out1, out2}};
   ckks_scale_then_add_kernel<<<g.grid, 256, 0, rh_stream(r)>>>(p, n, r->d_consts, level + 1, s, ratio ? 1 : 0, sub ? 1 : 0, scaled_is_b ? 1 : 0, g.nt);
   return rh_launch_ok("ckks_scale_then_add_kernel");
+}
+
+// every output block is an input block or apart from it (element-wise kernels: a thread reads its words of every input before it writes), and
+// the outputs are apart from each other
+static int real_imag_blocks(const u64* const* in, int nin, u64* const* out, int nout, size_t words, const char* who) {
+  RhBlock w[4];
+  for (int i = 0; i < nout; ++i) {
+    w[i] = {out[i], words};
+    if ((uintptr_t)out[i] & 15) return rh_fail(RH_ERR_ARG, "%s: every block must be 16-byte aligned", who);
+    for (int j = 0; j < nin; ++j) {
+      if ((uintptr_t)in[j] & 15) return rh_fail(RH_ERR_ARG, "%s: every block must be 16-byte aligned", who);
+      if (out[i] != in[j] && rh_overlap(w[i], RhBlock{in[j], words})) return rh_fail(RH_ERR_ARG, "%s: an output overlaps an input without being that input", who);
+    }
+  }
+  return rh_blocks_disjoint(w, nout, who, "two outputs overlap");
+}
+
+static int real_imag_launch(rh_ring* r, int level, const CkksPair& p, int npoly, const u64* s0, const u64* s1, bool split, const char* who) {
+  RhScalars s;                                                          // Mul(ct, -+i, ct) -> MulDoubleRNSScalar: MForm(scalar)
+  if (int rc = rh_pack_scalars(r, level, s0, s1, true, &s, who)) return rc;
+  const unsigned rows = (unsigned)npoly * (unsigned)(level + 1), n = (unsigned)r->N;
+  if (rows == 0) return RH_OK;
+  const RhStreamGrid g = rh_stream_begin(r, rows);
+  hipStream_t st = rh_stream(r);
+  if (split) ckks_real_imag_kernel<true><<<g.grid, 256, 0, st>>>(p, n, r->d_consts, level + 1, s, g.nt);
+  else ckks_real_imag_kernel<false><<<g.grid, 256, 0, st>>>(p, n, r->d_consts, level + 1, s, g.nt);
+  return rh_launch_ok("ckks_real_imag_kernel");
+}
+
+extern "C" int rh_ckks_split_real_imag(rh_ring* r, int level, const uint64_t* const* z, const uint64_t* const* zc, uint64_t* const* re,
+                                       uint64_t* const* im, int npoly, const uint64_t* s0, const uint64_t* s1) {
+  const char* who = "rh_ckks_split_real_imag";
+  if (int rc = rh_scheme_args(r, level, npoly, CKKS_RINGS, 4, who)) return rc;
+  if (r->kind != RH_RING_STANDARD) return rh_fail(RH_ERR_UNSUPPORTED, "%s: standard rings only (the homomorphic DFT is not defined on conjugate-invariant rings)", who);
+  if (!z || !zc || !re || !im || !s0 || !s1) return rh_fail(RH_ERR_ARG, "%s: null argument", who);
+  for (int j = 0; j < 2; ++j) if (!z[j] || !zc[j] || !re[j] || !im[j]) return rh_fail(RH_ERR_ARG, "%s: null argument", who);
+  const u64* in[4] = {z[0], z[1], zc[0], zc[1]};
+  u64* out[4] = {re[0], re[1], im[0], im[1]};
+  if (int rc = real_imag_blocks(in, 4, out, 4, (size_t)npoly * (level + 1) * (size_t)r->N, who)) return rc;
+  const CkksPair p{{z[0], z[1]}, {zc[0], zc[1]}, {re[0], re[1]}, {im[0], im[1]}};
+  return real_imag_launch(r, level, p, npoly, s0, s1, true, who);
+}
+
+extern "C" int rh_ckks_merge_real_imag(rh_ring* r, int level, const uint64_t* const* re, const uint64_t* const* im, uint64_t* const* out,
+                                       int npoly, const uint64_t* s0, const uint64_t* s1) {
+  const char* who = "rh_ckks_merge_real_imag";
+  if (int rc = rh_scheme_args(r, level, npoly, CKKS_RINGS, 4, who)) return rc;
+  if (r->kind != RH_RING_STANDARD) return rh_fail(RH_ERR_UNSUPPORTED, "%s: standard rings only (the homomorphic DFT is not defined on conjugate-invariant rings)", who);
+  if (!re || !im || !out || !s0 || !s1) return rh_fail(RH_ERR_ARG, "%s: null argument", who);
+  for (int j = 0; j < 2; ++j) if (!re[j] || !im[j] || !out[j]) return rh_fail(RH_ERR_ARG, "%s: null argument", who);
+  const u64* in[4] = {re[0], re[1], im[0], im[1]};
+  u64* outs[2] = {out[0], out[1]};
+  if (int rc = real_imag_blocks(in, 4, outs, 2, (size_t)npoly * (level + 1) * (size_t)r->N, who)) return rc;
+  const CkksPair p{{re[0], re[1]}, {im[0], im[1]}, {out[0], out[1]}, {nullptr, nullptr}};
+  return real_imag_launch(r, level, p, npoly, s0, s1, false, who);
 }
 
 extern "C" size_t rh_ckks_linear_combination_table_words(int nterms, int level) { return nterms < 0 || level < 0 ? 0 : lc_table_words(nterms, level + 1); }

@@ -3,7 +3,7 @@ circuits/common/lintrans/lintrans_evaluator.go and circuits/ckks/lintrans/lintra
 
   Parameters, Diagonals (At :97-122, Evaluate ckks/lintrans:24-56), Permutation / PermutationMapping (GetDiagonals ckks/lintrans:78-100)
   BSGSIndex :344-367     FindBestBSGSRatio :321-341     GaloisElements :297-318
-  LinearTransformation, NewTransformation :148-201     Encode :205-292
+  LinearTransformation, NewTransformation :148-201     Encode :205-292     (NewTransformationFromBlock: both for a whole device block, dft.py)
   Evaluator: EvaluateMany lintrans_evaluator.go:18-68, PreRotatedCiphertextForDiagonalMatrixMultiplication :71-99, EvaluateSequential :102-124,
              MultiplyByDiagMatrix :131-250, MultiplyByDiagMatrixBSGS :256-433
 
@@ -244,6 +244,33 @@ def Encode(encoder, diagonals, allocated):
 def _view(p, k):
     """poly k of a batch as a batch of its own"""
     return DevicePoly(p.ring, 1, p.limbs, ptr=p.ptr + k * p.limbs * p.ring.N * 8, owner=p)
+
+
+def NewTransformationFromBlock(ringQ, ringP, ltparams, encoder, index, block):
+    """NewTransformation and Encode in the block form (dft.NewMatrixFromLiteral): `block`, a ckks.DeviceValues of shape (len(index), cols) whose
+    row k holds diagonal index[k] of ltparams.DiagonalsIndexList ALREADY rotated as Encode rotates it (:246-262), goes through ONE Encoder.Embed
+    into ONE contiguous rlwe.PolyQP of len(index) polys; the entries of Vec are one-poly views that keep the block alive."""
+    if encoder.Prec() > 53:
+        raise RingHipError("cannot Encode: encoder precision %d > 53 needs the *big.Float / *bignum.Complex encoder, which stays with the reference" % encoder.Prec())
+    cols = 1 << ltparams.LogDimensions
+    levelQ, levelP = ltparams.LevelQ, ltparams.LevelP
+    if ringP is None:
+        raise RingHipError("cannot NewTransformation: a linear transformation is encoded modulo QP and needs ringP")
+    if not (0 <= levelQ < ringQ.L and 0 <= levelP < ringP.L):
+        raise RingHipError("cannot NewTransformation: LevelQ = %d, LevelP = %d out of range" % (levelQ, levelP))
+    index = [int(i) for i in index]
+    if sorted(i & (cols - 1) for i in ltparams.DiagonalsIndexList) != sorted(index) or len(set(index)) != len(index):
+        raise RingHipError("cannot NewTransformation: the block's rows are not the diagonals of DiagonalsIndexList")
+    if block.nvec != len(index) or block.n != cols or not block.complex:
+        raise RingHipError("cannot NewTransformation: the block must be complex128 of shape (%d, %d)" % (len(index), cols))
+    N1 = 0 if ltparams.LogBabyStepGiantStepRatio < 0 else FindBestBSGSRatio(index, cols, ltparams.LogBabyStepGiantStepRatio)
+    scale = ltparams.Scale if isinstance(ltparams.Scale, Scale) else Scale(ltparams.Scale)
+    rq, rp = ringQ.AtLevel(levelQ), ringP.AtLevel(levelP)
+    qp = rlwe.PolyQP(DevicePoly(rq, len(index), levelQ + 1), DevicePoly(rp, len(index), levelP + 1))
+    lt = LinearTransformation(ltparams.LogBabyStepGiantStepRatio, N1, levelQ, levelP, {}, scale, ltparams.LogDimensions)
+    encoder.Embed(block, lt, qp)
+    lt.Vec = {k: rlwe.PolyQP(_view(qp.Q, row), _view(qp.P, row)) for row, k in enumerate(index)}
+    return lt
 
 
 class Evaluator:

@@ -159,6 +159,10 @@ def lib():
         "rh_ckks_scalar": (i, [vp, i, i] + [vp] * 6 + [i, U64P, U64P]), "rh_ckks_scale_then_add": (i, [vp, i] + [vp] * 9 + [i, U64P, i, i]),
         "rh_ckks_linear_combination": (i, [vp, i, i, C.POINTER(vp), C.POINTER(i), U64P, U64P, U64P, U64P, vp, vp, vp, i, vp, sz]),
         "rh_ckks_linear_combination_table_words": (sz, [i, i]), "rh_ckks_linear_combination_chunk": (i, []), "rh_ckks_linear_combination_width": (i, []),
+        "rh_ckks_split_real_imag": (i, [vp, i] + [C.POINTER(vp)] * 4 + [i, U64P, U64P]), "rh_ckks_merge_real_imag": (i, [vp, i] + [C.POINTER(vp)] * 3 + [i, U64P, U64P]),
+        "rh_ckks_dft_level_vectors": (i, [vp, i, i, C.c_uint, i, i, vp, sz, vp, sz, vp]),
+        "rh_ckks_dft_merge_level": (i, [vp, C.c_uint, i, vp, vp, i, C.POINTER(i), i, vp, vp, sz]),
+        "rh_ckks_dft_finish": (i, [vp, C.c_uint, i, vp, vp, C.c_double, i, C.POINTER(i), vp, sz]),
         "rh_ckks_encoder_create": (i, [C.POINTER(vp), vp, C.POINTER(C.c_double), sz, C.c_uint]), "rh_ckks_encoder_destroy": (None, [vp]),
         "rh_ckks_encoder_reserve": (i, [vp, i]), "rh_ckks_encoder_set_tuning": (i, [vp, C.c_char_p, C.c_long]),
         "rh_ckks_special_ifft": (i, [vp, vp, i, i]), "rh_ckks_special_fft": (i, [vp, vp, i, i]),

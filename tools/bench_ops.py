@@ -16,7 +16,9 @@ config 5 ring and at N = 2^12, fused against composed, batched against per-ciphe
 K = 7, 15, 31: rh_ckks_linear_combination against the composed sequence of MulThenAdd calls) and writes profiles/ckks_polynomial.json;
 `bench_ops.py lintrans [OUT.json]` the linear transformations (lintrans.Evaluator.Evaluate at the config 5 ring, batches of 1 and 8: the reference
 test's nine diagonals with and without BSGS and a dense 64-diagonal matrix, each kernel of csrc/lintrans.hip alone against the ring calls it
-replaces and inside the whole Evaluate) and writes profiles/lintrans.json; `bench_ops.py blindrot [OUT.json [BASELINE.json]]` the blind rotation's
+replaces and inside the whole Evaluate) and writes profiles/lintrans.json; `bench_ops.py dft [OUT.json]` the homomorphic DFT (matrix generation and encoding on the
+device against host diagonals through the per-diagonal Encode, the real / imaginary split and merge kernels alone and inside CoeffsToSlots /
+SlotsToCoeffs at the config 5 ring, LogSlots 15, batches of 1 and 8) and writes profiles/dft.json; `bench_ops.py blindrot [OUT.json [BASELINE.json]]` the blind rotation's
 accumulator loop at the reference test's parameters (N = 2^10 / 2^9, Q = 0x7fff801, pw2 = 7) with 16, 64 and 256 accumulators, the kernel against
 the composed calls, and writes profiles/blindrot.json; `bench_ops.py blindrot_baseline [OUT.json]` one ExternalProduct and one key-switched
 automorphism at npoly = 1 through calls that predate the kernel (run it on the parent commit: BASELINE.json above)."""
@@ -880,6 +882,119 @@ def lintrans_group(out_path):
     rq.close(); rp.close()
 
 
+def dft_group(out_path):
+    """The config 5 ring of lintrans_group: N = 2^16, 24 limbs of Qi60, 6 of Pi60; LogSlots 15 (full packing), CoeffsToSlots with Levels [1,1,1,1] and
+    SlotsToCoeffs with Levels [1,1,1] (16 + 31 + 31 + 15 and 63 + 63 + 32 diagonals of 32768 values), RepackImagAsReal, BSGS ratio 0, batches of 1 and 8.
+    (a) NewMatrixFromLiteral's two halves on the device -- the diagonals generated in HBM, one Embed per factor -- against numpy diagonals generated on
+    the host and pushed through the per-diagonal lintrans.Encode; host wall clock, the device drained before and after, best of 3.  (b) each kernel of
+    dft.Evaluator.FUSED_DFT alone against the evaluator calls it replaces, and inside the whole circuit; (c) the whole circuits per ciphertext.  Both
+    sides of (b) and (c) are timed HERE in alternating windows, as in lintrans_group, whose rule `fused_default` follows.  Keys hold uniform residues."""
+    import statistics
+    N, LQ, LP, rounds, reps = 1 << 16, 24, 6, 5, 3
+    Q, P = QI60[:LQ], PI60[:LP]
+    rq, rp = rh.Ring(N, Q), rh.Ring(N, P); rq.set_stream(stream.cuda_stream); rp.set_stream(stream.cuda_stream)
+    digits = (LQ + LP - 1) // LP
+    level, levelP, ls = LQ - 1, LP - 1, 15
+    D, lt_ = rh.dft, rh.lintrans
+    ecd = rh.ckks.Encoder(rq, ringP=rp)
+    lits = {"CoeffsToSlots": D.MatrixLiteral(D.HomomorphicEncode, ls, level, levelP, [1, 1, 1, 1], D.RepackImagAsReal),
+            "SlotsToCoeffs": D.MatrixLiteral(D.HomomorphicDecode, ls, level, levelP, [1, 1, 1], D.RepackImagAsReal)}
+
+    def wall(fn):
+        best, keep = None, None
+        for _ in range(3):
+            keep = None
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            keep = fn()
+            torch.cuda.synchronize(); ms = (time.perf_counter() - t0) * 1e3
+            best = ms if best is None else min(best, ms)
+        return round(best, 3), keep
+
+    def host_encode(lit, diags):
+        out = []
+        for i, dg in enumerate(diags):
+            lt = lt_.NewTransformation(rq, rp, lt_.Parameters(sorted(dg), level, levelP, Q[level - i], ls, lit.LogBSGSRatio))
+            lt_.Encode(ecd, dg, lt)
+            out.append(lt)
+        return out
+
+    def device_encode(lit, blocks):
+        return [lt_.NewTransformationFromBlock(rq, rp, lt_.Parameters(b.Index, level, levelP, Q[level - i], ls, lit.LogBSGSRatio), ecd, b.Index, b.Block)
+                for i, b in enumerate(blocks)]
+    generation, mats = [], {}
+    for name, lit in lits.items():
+        rots = lambda f, index: D._bsgs_rotations(index, 1 << ls, lit.LogBSGSRatio)
+        gen_dev, blocks = wall(lambda: D._gen_device(lit, 16, None, rq, rots))
+        enc_dev, dev_lts = wall(lambda: device_encode(lit, blocks))
+        gen_host, diags = wall(lambda: lit.GenMatrices(16, device=False))
+        enc_host, host_lts = wall(lambda: host_encode(lit, diags))
+        k = sorted(dev_lts[0].Vec)[1]                          # same bits, at the timed shape: one diagonal of the first factor
+        assert np.array_equal(dev_lts[0].Vec[k].Q.numpy(), host_lts[0].Vec[k].Q.numpy()) and np.array_equal(dev_lts[0].Vec[k].P.numpy(), host_lts[0].Vec[k].P.numpy())
+        generation.append({"matrix": name, "factors": len(blocks), "diagonals": [len(b.Index) for b in blocks],
+                           "device": {"generate_ms": gen_dev, "encode_ms": enc_dev}, "host_per_diagonal": {"generate_ms": gen_host, "encode_ms": enc_host},
+                           "ratio_host_over_device": {"generate": round(gen_host / gen_dev, 2), "encode": round(enc_host / enc_dev, 2),
+                                                      "both": round((gen_host + enc_host) / (gen_dev + enc_dev), 2)}})
+        del blocks, diags, host_lts, dev_lts
+        mats[name] = D.NewMatrixFromLiteral(rq, rp, lit, ecd)
+
+    def key():
+        k = rh.rlwe.GadgetCiphertext.__new__(rh.rlwe.GadgetCiphertext)
+        k.digits, k.levelQ, k.levelP, k.BaseTwoDecomposition, k.digits_per_limb = digits, level, levelP, 0, None
+        k.Q, k.P = rh.DevicePoly.from_torch(rq, rand_block(2 * digits, Q, N)), rh.DevicePoly.from_torch(rp, rand_block(2 * digits, P, N))
+        return k
+    galEls = sorted({g for lit in lits.values() for g in lit.GaloisElements(N) if g != 1} | {2 * N - 1})
+    cev = rh.ckks.Evaluator(rq, rp, galois_keys={g: key() for g in galEls})
+    dev = D.Evaluator(cev)
+    stat = lambda v: {"ms_median": round(statistics.median(v), 4), "ms_min": round(min(v), 4), "ms_max": round(max(v), 4)}
+    results = []
+
+    def measure(name, B, fn, kernel, reps=reps):
+        tf, tc = [], []
+        for _ in range(rounds):
+            tf.append(timed(lambda: fn(True), reps=reps)); tc.append(timed(lambda: fn(False), reps=reps))
+        f, c = stat(tf), stat(tc)
+        spread = round(c["ms_max"] - c["ms_min"], 4)
+        results.append({"op": name, "batch": B, "kernel": kernel, "fused": f, "composed": c, "ratio_composed_over_fused": round(c["ms_median"] / f["ms_median"], 3),
+                        "fused_ms_per_ciphertext": round(f["ms_median"] / B, 4), "composed_ms_per_ciphertext": round(c["ms_median"] / B, 4),
+                        "composed_run_to_run_spread_ms": spread, "fused_default": bool(f["ms_median"] <= c["ms_median"] + spread)})
+    for B in (1, 8):
+        def new(lv=level):
+            ct = rh.Ciphertext([rh.DevicePoly.from_torch(rq.AtLevel(lv), rand_block(B, Q[:lv + 1], N)) for _ in (0, 1)], is_ntt=True)
+            ct.Scale, ct.LogDimensions = rh.ckks.Scale(1 << 40), ls
+            return ct
+        ct, re, im, out = new(), new(), new(), new()
+        res = []
+        for fused in (True, False):                            # same bits first, at the timed shape
+            r, i = dev.CoeffsToSlotsNew(ct, mats["CoeffsToSlots"], fused=fused)
+            o = dev.SlotsToCoeffsNew(re, im, mats["SlotsToCoeffs"], fused=fused)
+            res.append([v.numpy() for x in (r, i, o) for v in x.Value])
+        assert all(np.array_equal(x, y) for x, y in zip(*res)), "fused and composed circuits differ"
+        del res, r, i, o
+        low = level - 4                                        # the split runs after four rescalings, the merge at LevelQ
+        z, zc, tmp = new(low), new(low), new(low)
+
+        def split(f):
+            dev._split(z, zc, tmp, f)
+        measure("real / imaginary split at level %d, the kernel alone" % low, B, split, "split", reps=50)
+        measure("real / imaginary merge at level %d, the kernel alone" % level, B, lambda f: dev._merge_parts(re, im, out, f), "merge", reps=50)
+        cre, cim = new(), new()
+        measure("CoeffsToSlots, Levels [1,1,1,1]", B, lambda f: dev.CoeffsToSlots(ct, mats["CoeffsToSlots"], cre, cim, fused=f), "split")
+        measure("SlotsToCoeffs, Levels [1,1,1]", B, lambda f: dev.SlotsToCoeffs(re, im, mats["SlotsToCoeffs"], out, fused=f), "merge")
+    defaults = {k: bool(all(e["fused_default"] for e in results if e["kernel"] == k)) for k in D.Evaluator.FUSED_DFT}
+    from bench import csrc_tree_hash
+    res = {"device": torch.cuda.get_device_name(0), "csrc_tree": csrc_tree_hash(), "shape": {"N": N, "limbs_Q": LQ, "limbs_P": LP, "batches": [1, 8], "log_slots": ls},
+           "method": "circuits and kernels: %d alternating windows of %d calls each (50 for a kernel alone), device events, 2 warm-up calls per window; "
+                     "matrix generation and encoding: host wall clock around one call, the device drained before and after, best of 3; clocks left to the "
+                     "driver's default governor" % (rounds, reps),
+           "matrix_generation": generation, "fused_dft_default": defaults, "results": results}
+    with open(out_path, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(res, indent=1))
+    ecd.close(); cev.close()
+    rq.close(); rp.close()
+
+
 def _wall_ms(fn, sync, reps, warm=1):
     """host wall clock around `reps` calls, the device drained before and after: what a caller waits for"""
     for _ in range(warm):
@@ -981,6 +1096,11 @@ if sys.argv[1:2] == ["blindrot_baseline"]:
 
 if sys.argv[1:2] == ["blindrot"]:
     blindrot_group(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "blindrot.json"), sys.argv[3] if len(sys.argv) > 3 else None)
+    sys.exit(0)
+
+
+if sys.argv[1:2] == ["dft"]:
+    dft_group(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "dft.json"))
     sys.exit(0)
 
 
