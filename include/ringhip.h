@@ -631,6 +631,24 @@ int rh_ckks_dft_merge_level(rh_ring* r, unsigned dslots, int rot, const double* 
 int rh_ckks_dft_finish(rh_ring* r, unsigned dslots, int ndiag, const double* in_dev, double* out_dev, double scaling, int zero_upper,
                        const int* rots, uint64_t* table_dev, size_t table_words);
 
+/* ---- CKKS bootstrapping (circuits/ckks/bootstrapping/evaluator.go, circuits/ckks/mod1/mod1_evaluator.go) ------------------------------
+ *   rh_ckks_bootstrap_modup  Evaluator.ModUp's lift of the level-0 residues, centred around q0, to every limb of Q (:678-696, :762-775) and,
+ *                            with ringP (sparse-secret encapsulation, :703-722), of component 1 to every limb of Q and of P; ONE launch over
+ *                            both components of a batch.  in0 / in1: limb 0 in the COEFFICIENT domain, blocks of in_rows limbs per poly of
+ *                            which row 0 is read.  out0 (and out1 without ringP): blocks (npoly, levelQ + 1, N); with ringP component 1 goes
+ *                            to c1Q (npoly, levelQ + 1, N) and c1P (npoly, levelP + 1, N) and out1 is NULL.  Every limb of the outputs is
+ *                            written; an output that overlaps an input is refused (the lift is not computed in place).  The comparison is coeff >= q0 >> 1, and
+ *                            coeff > q0 >> 1 for the encapsulated component 1, as the reference writes them.  Where a modulus divides
+ *                            |coeff| of a negative coefficient the canonical 0 is written (the reference's (Q[i] - tmp) * neg gives Q[i]).
+ *                            scalarQ / scalarP: HOST residues per limb of uint64(round(scale)) (:735-750, :781-789) or NULL: every limb
+ *                            written, limb 0 included, is multiplied by it -- the bits of MulScalar after the NTT.
+ *   rh_ckks_double_angle     c0 <- (c0 + c0) + k, c1 <- c1 + c1 (mod1_evaluator.go:108-114: Add(res, res, res), Add(res, -sqrt2pi, res)), in
+ *                            place, one launch; k: the double RNS scalar as rh_ckks_scalar takes it (s0 on coefficients [0, N/2), s1 above). */
+int rh_ckks_bootstrap_modup(rh_ring* rQ, rh_ring* rP, int levelQ, int levelP, const uint64_t* in0_dev, const uint64_t* in1_dev, int in_rows,
+                            uint64_t* out0_dev, uint64_t* out1_dev, uint64_t* c1Q_dev, uint64_t* c1P_dev, int npoly, const uint64_t* scalarQ,
+                            const uint64_t* scalarP);
+int rh_ckks_double_angle(rh_ring* r, int level, uint64_t* c0_dev, uint64_t* c1_dev, int npoly, const uint64_t* s0, const uint64_t* s1);
+
 /* ---- CKKS encoder: the float64 path of schemes/ckks/encoder.go on device batches of nvec vectors ------------------------------------
  * A handle on a STANDARD ring.  Refused by name (RH_ERR_UNSUPPORTED): conjugate-invariant rings, 3N rings, prec > 53 (the *big.Float /
  * *bignum.Complex encoder), rh_ckks_decode with batched = 0 at a level that is neither 0 nor the ring's top level.  Values are IEEE doubles, complex values interleaved (re, im); a block of

@@ -16,3 +16,5 @@ from . import bgv  # noqa: F401,E402
 from . import polynomial  # noqa: F401,E402
 from . import lintrans  # noqa: F401,E402
 from . import dft  # noqa: F401,E402
+from . import mod1  # noqa: F401,E402
+from . import bootstrapping  # noqa: F401,E402

@@ -20,7 +20,9 @@ replaces and inside the whole Evaluate) and writes profiles/lintrans.json; `benc
 device against host diagonals through the per-diagonal Encode, the real / imaginary split and merge kernels alone and inside CoeffsToSlots /
 SlotsToCoeffs at the config 5 ring, LogSlots 15, batches of 1 and 8) and writes profiles/dft.json; `bench_ops.py blindrot [OUT.json [BASELINE.json]]` the blind rotation's
 accumulator loop at the reference test's parameters (N = 2^10 / 2^9, Q = 0x7fff801, pw2 = 7) with 16, 64 and 256 accumulators, the kernel against
-the composed calls, and writes profiles/blindrot.json; `bench_ops.py blindrot_baseline [OUT.json]` one ExternalProduct and one key-switched
+the composed calls, and writes profiles/blindrot.json; `bench_ops.py bootstrap [OUT.json]` CKKS bootstrapping at the N16QP1546H192H32 chain shape (N = 2^16, 25 + 5
+limbs, LogSlots 15, batches of 1 and 8: the ModUp kernel alone against its write volume, EvalMod alone, the whole Evaluate split by stage, FUSED_BOOTSTRAP
+on and off) and writes profiles/bootstrap.json; `bench_ops.py blindrot_baseline [OUT.json]` one ExternalProduct and one key-switched
 automorphism at npoly = 1 through calls that predate the kernel (run it on the parent commit: BASELINE.json above)."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -995,6 +997,132 @@ def dft_group(out_path):
     rq.close(); rp.close()
 
 
+def bootstrap_group(out_path):
+    """CKKS bootstrapping at the N16QP1546H192H32 chain shape: N = 2^16, 10 residual + 3 (SlotsToCoeffs, 39 bits) + 8 (EvalMod, 60) + 4 (CoeffsToSlots, 56)
+    limbs of Q and 5 of P, scale 2^40, LogSlots 15, CosDiscrete K = 16 / degree 30 / r = 3, sparse-secret encapsulation; batches of 1 and 8.
+    (a) rh_ckks_bootstrap_modup alone, dense and encapsulated, without and with the folded scalar, as bytes per second against its WRITE volume;
+    (b) the lift, the transforms and the message scaling with the scalar folded into the kernel against MulScalar after the NTT;
+    (c) EvalMod alone (on 2 B ciphertexts: ctReal and ctImag as one batch) with rh_ckks_double_angle against the two Adds;
+    (d) the whole Evaluate split by stage, FUSED_BOOTSTRAP on and off.  Both sides of (b), (c), (d) are timed HERE in alternating windows.
+    Keys and ciphertexts hold uniform residues: the timings do not depend on the values."""
+    import statistics
+    from oracle import primes
+    N, ls, rounds, reps = 1 << 16, 15, 3, 3
+    Q, P = primes.gen_moduli(17, [60] + [40] * 9 + [39] * 3 + [60] * 8 + [56] * 4, [61] * 5)
+    Q, P = [int(q) for q in Q], [int(p) for p in P]
+    LQ, LP = len(Q), len(P)
+    rq, rp = rh.Ring(N, Q), rh.Ring(N, P); rq.set_stream(stream.cuda_stream); rp.set_stream(stream.cuda_stream)
+    rq0, rp0 = rh.Ring(N, Q[:1]), rh.Ring(N, P[:1]); rq0.set_stream(stream.cuda_stream); rp0.set_stream(stream.cuda_stream)
+    B_, D, M = rh.bootstrapping, rh.dft, rh.mod1
+    res_level, s2c_level, mod1_level, top = 9, 12, 20, 24
+    digits = (LQ + LP - 1) // LP
+
+    def key(ringq=rq, ringp=rp, mq=Q, mp=P, rows=digits):
+        k = rh.rlwe.GadgetCiphertext.__new__(rh.rlwe.GadgetCiphertext)
+        k.digits, k.levelQ, k.levelP, k.BaseTwoDecomposition, k.digits_per_limb = rows, len(mq) - 1, len(mp) - 1, 0, None
+        k.Q, k.P = rh.DevicePoly.from_torch(ringq, rand_block(2 * rows, mq, N)), rh.DevicePoly.from_torch(ringp, rand_block(2 * rows, mp, N))
+        return k
+    s2c = D.MatrixLiteral(D.HomomorphicDecode, ls, s2c_level, LP - 1, [1, 1, 1], D.RepackImagAsReal, LogBSGSRatio=1)
+    c2s = D.MatrixLiteral(D.HomomorphicEncode, ls, top, LP - 1, [1, 1, 1, 1], D.RepackImagAsReal, LogBSGSRatio=1)
+    m1 = M.ParametersLiteral(LevelQ=mod1_level, LogScale=60, Mod1Type=M.CosDiscrete, LogMessageRatio=8, K=16, Mod1Degree=30, DoubleAngle=3)
+    params = B_.Parameters(rq, rp, res_level, 1 << 40, s2c, m1, c2s, EphemeralSecretWeight=32)
+    keys = B_.EvaluationKeys(key(), {g: key() for g in params.GaloisElements() if g != 1}, key(rq0, rp0, Q[:1], P[:1], 1), key())
+    evs = {f: B_.Evaluator(params, keys, fused=f) for f in (True, False)}
+    stat = lambda v: {"ms_median": round(statistics.median(v), 4), "ms_min": round(min(v), 4), "ms_max": round(max(v), 4)}
+    kernel, results = [], []
+
+    def measure(name, B, fn, choice, reps=reps):
+        """choice: the FUSED_BOOTSTRAP key the two sides differ in, or None where both run the same code (a stage the flags do not reach: its two
+        columns are two samples of one thing).  A side whose slowest window is more than 1.5 times its fastest is marked bimodal; a row decides a
+        default only when it has a choice and neither side is bimodal, else the row says why not."""
+        tf, tc = [], []
+        for _ in range(rounds):
+            tf.append(timed(lambda: fn(True), reps=reps)); tc.append(timed(lambda: fn(False), reps=reps))
+        f, c = stat(tf), stat(tc)
+        spread = round(c["ms_max"] - c["ms_min"], 4)
+        bimodal = [side for side, v in (("fused", f), ("composed", c)) if v["ms_max"] > 1.5 * v["ms_min"]]
+        e = {"op": name, "batch": B, "choice": choice, "fused": f, "composed": c, "fused_ms_per_ciphertext": round(f["ms_median"] / B, 4),
+             "composed_ms_per_ciphertext": round(c["ms_median"] / B, 4), "composed_run_to_run_spread_ms": spread, "bimodal_windows": bimodal}
+        if choice is not None:
+            e["ratio_composed_over_fused"] = round(c["ms_median"] / f["ms_median"], 3)
+            if bimodal:
+                e["fused_default"] = None
+                e["undecided"] = "windows of one side differ by more than 1.5x: the medians do not decide"
+            else:
+                e["fused_default"] = bool(f["ms_median"] <= c["ms_median"] + spread)
+                e["difference_within_spread"] = bool(abs(f["ms_median"] - c["ms_median"]) <= spread)
+        results.append(e)
+    scalar = (1 << 20) + 12345
+    for B in (1, 8, 48):                                          # 48: 1.26 / 1.38 GB written per call, beyond the 256 MiB Infinity Cache and the 512 MiB non-temporal threshold; the kernel alone
+        blk = lambda ring, mods: rh.DevicePoly.from_torch(ring, rand_block(B, mods, N))
+        i0, i1 = blk(rq.AtLevel(0), Q[:1]), blk(rq.AtLevel(0), Q[:1])
+        o0, o1, eQ, eP = rq.NewPoly(B), rq.NewPoly(B), rq.NewPoly(B), rp.NewPoly(B)
+        for arm, call, rows in (("dense", lambda sc: B_.modup_lift(rq, None, LQ - 1, 0, i0, i1, o0, o1, scalar=sc), 2 * LQ),
+                                ("encapsulated", lambda sc: B_.modup_lift(rq, rp, LQ - 1, LP - 1, i0, i1, o0, c1Q=eQ, c1P=eP, scalar=sc), 2 * LQ + LP)):
+            for sc in (None, scalar):
+                ms = timed(lambda: call(sc), reps=50)
+                wr = 8.0 * N * B * rows
+                e = {"op": "rh_ckks_bootstrap_modup, %s%s" % (arm, ", scalar folded" if sc else ""), "batch": B, "ms": round(ms, 4), "bytes_written": wr,
+                     "bytes_read": 16.0 * N * B, "write_GBps": round(wr / (ms * 1e-3) / 1e9, 1)}
+                if wr > (512 << 20):                            # only there is the store rate a rate of HBM: below, the 50 calls of a window rewrite blocks the Infinity Cache holds
+                    e["frac_of_8TBps_hbm"] = round(wr / (ms * 1e-3) / 1e9 / PEAK, 3)
+                else:
+                    e["note"] = "the blocks written fit the 256 MiB Infinity Cache and the window rewrites them: a cache-assisted store rate, not a share of HBM peak"
+                kernel.append(e)
+        if B > 8:
+            del i0, i1, o0, o1, eQ, eP
+            continue
+
+        def lift_and_scale(fold):                               # the encapsulated arm's lift, three transforms and the scaling (:703-750)
+            B_.modup_lift(rq, rp, LQ - 1, LP - 1, i0, i1, o0, c1Q=eQ, c1P=eP, scalar=scalar if fold else None)
+            rq.NTT(eQ, eQ); rp.NTT(eP, eP); rq.NTT(o0, o0)
+            if not fold:
+                rq.MulScalar(eQ, scalar, eQ); rp.MulScalar(eP, scalar, eP); rq.MulScalar(o0, scalar, o0)
+        measure("ModUp's lift, transforms and message scaling (encapsulated arm, scalar forced)", B, lift_and_scale, "modup_scale", reps=20)
+        ct = rh.Ciphertext([i0, i1], is_ntt=True)
+        ct.Scale, ct.LogDimensions = rh.ckks.Scale(1 << 40), ls
+        st = {}
+        for f in (True, False):                                 # same bits first, at the timed shape
+            ev = evs[f]
+            down, _ = ev.ScaleDown(ct)
+            up = ev.ModUp(down)
+            re, im = ev.CoeffsToSlots(up)
+            a, b = ev._eval_mod_pair(re, im)
+            out = ev.SlotsToCoeffs(a, b)
+            st[f] = (down, up, re, im, a, b, out)
+        assert all(np.array_equal(x.numpy(), y.numpy()) for x, y in zip(st[True][-1].Value, st[False][-1].Value)), "FUSED_BOOTSTRAP on and off differ"
+        down, up, re, im, a, b, out = st[True]
+        measure("EvalMod alone on ctReal and ctImag as one batch (2 B ciphertexts)", B, lambda f: evs[f]._eval_mod_pair(re, im), "double_angle")
+        measure("Evaluate: ScaleDown", B, lambda f: evs[f].ScaleDown(ct), None)
+        applies = (evs[True].Mod1Parameters.ScalingFactor().Float64() / evs[True].Mod1Parameters.MessageRatio()) / down.Scale.Float64() > 1     # :735
+        measure("Evaluate: ModUp (key switches, lift, Trace)%s" % ("" if applies else "; no message scalar in this setting: both sides run the same code"), B,
+                lambda f: evs[f].ModUp(down), "modup_scale" if applies else None)
+        measure("Evaluate: CoeffsToSlots", B, lambda f: evs[f].CoeffsToSlots(up), None)
+        measure("Evaluate: EvalMod", B, lambda f: evs[f]._eval_mod_pair(re, im), "double_angle")
+        measure("Evaluate: SlotsToCoeffs", B, lambda f: evs[f].SlotsToCoeffs(a, b), None)
+        measure("Evaluate, whole", B, lambda f: evs[f].Evaluate(ct), None, reps=2)
+        del st
+    # a default follows the rows that decide (a choice, no bimodal side): the kernel unless one of them finds it slower beyond the spread
+    deciding = {k: [e for e in results if e["choice"] == k and e.get("fused_default") is not None] for k in M.Evaluator.FUSED_BOOTSTRAP}
+    defaults = {k: bool(all(e["fused_default"] for e in v)) for k, v in deciding.items()}
+    from bench import csrc_tree_hash
+    res = {"device": torch.cuda.get_device_name(0), "csrc_tree": csrc_tree_hash(),
+           "shape": {"N": N, "limbs_Q": LQ, "limbs_P": LP, "log_q": [60] + [40] * 9 + [39] * 3 + [60] * 8 + [56] * 4, "batches": [1, 8], "kernel_alone_batches": [1, 8, 48], "log_slots": ls,
+                     "message_scalar_of_the_setting": "about 1: EvalMod's scale 2^60 / MessageRatio is Q0 / MessageRatio, so ModUp of this chain multiplies by no scalar; (b) forces one"},
+           "method": "%d alternating windows of %d calls each (50 for the kernel alone, 20 for (b), 2 for the whole Evaluate), device events, 2 warm-up calls per "
+                     "window; clocks left to the driver's default governor" % (rounds, reps),
+           "modup_kernel": kernel, "fused_bootstrap_default": defaults,
+           "fused_bootstrap_default_rests_on": {k: [(e["op"], e["batch"]) for e in v] for k, v in deciding.items()}, "results": results}
+    with open(out_path, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(res, indent=1))
+    for ev in evs.values():
+        ev.close()
+    for r in (rq, rp, rq0, rp0):
+        r.close()
+
+
 def _wall_ms(fn, sync, reps, warm=1):
     """host wall clock around `reps` calls, the device drained before and after: what a caller waits for"""
     for _ in range(warm):
@@ -1098,6 +1226,10 @@ if sys.argv[1:2] == ["blindrot"]:
     blindrot_group(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "blindrot.json"), sys.argv[3] if len(sys.argv) > 3 else None)
     sys.exit(0)
 
+
+if sys.argv[1:2] == ["bootstrap"]:
+    bootstrap_group(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "bootstrap.json"))
+    sys.exit(0)
 
 if sys.argv[1:2] == ["dft"]:
     dft_group(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "dft.json"))
