@@ -788,6 +788,52 @@ int rh_kshard_set_exchange(rh_kshard* ks, uint64_t* arena_dev, size_t words);
 int rh_kshard_gadget_product(rh_kshard* ks, const uint64_t* cx_loc, const uint64_t* evkQ_loc, const uint64_t* evkP_loc,
                              uint64_t* ct0_loc, uint64_t* ct1_loc, int npoly, rh_allgather_fn allgather, void* ctx, int chunks);
 
+/* ---- keys and ciphertexts made on the device (csrc/keygen.hip) -------------------------------------------------------------------------
+ * The samplers' stream.  Block t of substream (call, poly, row, group) is the 64-byte BLAKE2b digest, keyed with the PRNG's key and
+ * personalised with "ringhip-sampler\0", of the five little-endian words (call, poly, row, group, t), read as eight little-endian words;
+ * coefficient i uses word i % 8 of blocks t = 0, 1, ... of group i / 8.  `state`: the eight chaining words after the padded key block
+ * (the host computes them once per key), so a block costs one compression.  call: the PRNG's read counter; poly0: the index of the first
+ * poly written (a batch sampled in sub-blocks gives the same polys); row: row0 + limb for uniform polys (Q limbs first, then P), 0 for
+ * the small-norm samplers.  Everything is enqueued on the ring's stream.
+ *   rh_sample_uniform   UniformSampler.Read (ring/sampler_uniform.go:46-106): candidate = word & Mask, accepted when < q.  Limbs 0..level of
+ *                       npoly polys; row (poly, limb) goes to out + (poly * out_rows + limb) * N (out_rows >= level + 1: a write at a row
+ *                       stride into a larger block, e.g. component 1 of a key table).
+ *   rh_sample_gaussian  the distribution of GaussianSampler.Read (ring/sampler_gaussian.go:159-172) from the cumulative table
+ *                       table_dev[k] = floor(P(|x| <= k) 2^63), k < table_len <= 1024, table[table_len - 1] = 2^63 (the host builds it up to the largest magnitude the law reaches): |x| = #{k: table[k] <= word & (2^63 - 1)}, negative when
+ *                       bit 63 is set.  out: int32 (npoly, N).  Zero is the canonical 0 (the reference writes q for a zero of sign 0).
+ *   rh_sample_ternary   TernarySampler.Read with a density P (ring/sampler_ternary.go): non-zero when (word >> 1) < threshold = floor(P 2^63),
+ *                       negative when bit 0 is set.  out: int32 (npoly, N).
+ *   rh_small_lift       int32 (npoly, N) -> residues under limbs 0..levelQ of ringQ and 0..levelP of ringP (NULL: Q alone): x >= 0 ? x : q - |x|,
+ *                       what Read + ExtendBasisSmallNormAndCenter produce; accumulate: ReadAndAdd, out = CRed(out + lift).  q_rows / p_rows:
+ *                       limbs per poly of the output blocks. */
+int rh_sample_uniform(rh_ring* r, int level, const uint64_t* state, uint64_t call, uint64_t poly0, uint64_t row0, uint64_t* out_dev, int out_rows, int npoly);
+int rh_sample_gaussian(rh_ring* r, const uint64_t* state, uint64_t call, uint64_t poly0, const uint64_t* table_dev, int table_len, int32_t* out_dev, int npoly);
+int rh_sample_ternary(rh_ring* r, const uint64_t* state, uint64_t call, uint64_t poly0, uint64_t threshold, int32_t* out_dev, int npoly);
+int rh_small_lift(rh_ring* ringQ, rh_ring* ringP, int levelQ, int levelP, const int32_t* in_dev, uint64_t* outQ_dev, int q_rows, uint64_t* outP_dev, int p_rows,
+                  int npoly, int accumulate);
+/* Every row of one or many gadget ciphertexts in one launch (per row: MForm, MulCoeffsMontgomeryThenSub, core/rlwe/encryptor.go:449-452, and the
+ * MulScalarMontgomery + Add per digit limb of AddPolyTimesGadgetVectorToGadgetCiphertext, core/rlwe/gadgetciphertext.go:172-241, as
+ * genEvaluationKey sequences them, core/rlwe/keygenerator.go:297-315):
+ *   tab[r][0] = MForm(e_r) - tab[r][1] * skOut[key_r] [+ skIn[key_r] * s_r on the Q limbs where s_r != 0]
+ * eQ / eP: the NTT of the lifted errors, (rows, limbs, N); tabQ / tabP: (rows, 2, limbs, N), component 1 already holding the uniform a;
+ * skOutQ / skOutP: (nkeys, limbs, N) and skInQ: (skin_keys, levelQ + 1, N), skin_keys = nkeys or 1 (one input key for all), NTT domain, Montgomery form.  rowtab (HOST): rows x (levelQ + 2) words:
+ * key_r, then s_r per limb of Q -- P 2^(j pw2) in Montgomery form on the limbs of the row's digit, 0 elsewhere.  table_dev: device scratch of
+ * at least rh_rlwe_gadget_encrypt_table_words(levelQ, rows) words the row table is staged into.  ringP NULL: no P (eP, tabP, skOutP NULL). */
+size_t rh_rlwe_gadget_encrypt_table_words(int levelQ, int rows);
+int rh_rlwe_gadget_encrypt(rh_ring* ringQ, rh_ring* ringP, int levelQ, int levelP, const uint64_t* eQ, const uint64_t* eP, uint64_t* tabQ, uint64_t* tabP,
+                           const uint64_t* skOutQ, const uint64_t* skOutP, const uint64_t* skInQ, int nkeys, int skin_keys, const uint64_t* rowtab, int rows,
+                           uint64_t* table_dev, size_t table_words);
+/* encryptZeroSkFromC1 with addPtToCt folded in (core/rlwe/encryptor.go:398-424, :512-530), NTT domain: c0 = -c1 sk + e [+ pt], canonical.
+ * sk: (level + 1, N), NTT domain, Montgomery form; e: the NTT of the lifted error; pt: NULL or an NTT-domain plaintext batch.  e NULL: only
+ * -c1 sk (a coefficient-domain ciphertext adds its error and plaintext after the inverse transform, :415-420). */
+int rh_rlwe_encrypt_sk(rh_ring* r, int level, const uint64_t* c1, const uint64_t* sk, const uint64_t* e, const uint64_t* pt, uint64_t* c0, int npoly);
+/* ct0 = u * pk0, ct1 = u * pk1 (MulCoeffsMontgomery, core/rlwe/encryptor.go:259-260, :324-326) in one launch that reads u once.
+ * u: (npoly, level + 1, N); pk0, pk1: (level + 1, N) shared by the batch. */
+int rh_rlwe_mul_pk(rh_ring* r, int level, const uint64_t* u, const uint64_t* pk0, const uint64_t* pk1, uint64_t* ct0, uint64_t* ct1, int npoly);
+/* Decryptor.Decrypt's Horner sum c0 + s (c1 + s c2) (core/rlwe/decryptor.go:51-92), NTT domain, canonical, every component read once.
+ * c2 NULL: degree 1.  out may be c0. */
+int rh_rlwe_decrypt(rh_ring* r, int level, const uint64_t* c0, const uint64_t* c1, const uint64_t* c2, const uint64_t* sk, uint64_t* out, int npoly);
+
 #ifdef __cplusplus
 }
 #endif

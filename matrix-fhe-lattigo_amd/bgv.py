@@ -1003,3 +1003,18 @@ class Encoder:
         if self._ring_of(pQ, "RingQ2T") is not self.ringQ or pQ.limbs != level + 1 or pQ.npoly != pT.npoly:
             raise RingHipError("cannot RingQ2T: pQ must be a block of %d polys of ringQ with level + 1 = %d limbs" % (pT.npoly, level + 1))
         _check(lib().rh_bgv_ring_q2t(self._h, int(level), pQ.ptr, pT.ptr, pT.npoly))
+
+
+# ---- bgv.NewEncryptor / NewDecryptor (schemes/bgv/bgv.go): rlwe's, carrying the Plaintext metadata ---------------------------------------------------
+class Encryptor(rlwe.Encryptor):
+    """bgv.Encryptor: rlwe.Encryptor on bgv.Plaintext batches; the ciphertext takes the plaintext's Scale and IsBatched"""
+
+
+class Decryptor(rlwe.Decryptor):
+    """bgv.Decryptor: rlwe.Decryptor; DecryptNew returns a bgv.Plaintext with the ciphertext's Scale and IsBatched"""
+
+    def DecryptNew(self, ct, fused=None):
+        poly = self.ringQ.AtLevel(ct.Level()).NewPoly(ct.Value[0].npoly)
+        pt = Plaintext(poly, getattr(ct, "Scale", 1), ct.IsNTT, getattr(ct, "IsMontgomery", False), getattr(ct, "IsBatched", True))
+        self.Decrypt(ct, pt, fused)
+        return pt

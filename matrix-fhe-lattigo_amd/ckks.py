@@ -1108,3 +1108,18 @@ class Encoder:
 
     def FFT(self, values, logN):
         return self._transform(values, logN, lib().rh_ckks_special_fft, "FFT")
+
+
+# ---- ckks.NewEncryptor / NewDecryptor (schemes/ckks/ckks.go): rlwe's, carrying the Plaintext metadata ------------------------------------------------
+class Encryptor(rlwe.Encryptor):
+    """ckks.Encryptor: rlwe.Encryptor on ckks.Plaintext batches; the ciphertext takes the plaintext's Scale, LogDimensions and IsBatched"""
+
+
+class Decryptor(rlwe.Decryptor):
+    """ckks.Decryptor: rlwe.Decryptor; DecryptNew returns a ckks.Plaintext with the ciphertext's Scale, LogDimensions and IsBatched"""
+
+    def DecryptNew(self, ct, fused=None):
+        poly = self.ringQ.AtLevel(ct.Level()).NewPoly(ct.Value[0].npoly)
+        pt = Plaintext(poly, ct.Scale, ct.LogDimensions, ct.IsNTT, getattr(ct, "IsMontgomery", False), getattr(ct, "IsBatched", True))
+        self.Decrypt(ct, pt, fused)
+        return pt

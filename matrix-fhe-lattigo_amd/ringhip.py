@@ -174,6 +174,14 @@ def lib():
         "rh_bgv_encode": (i, [vp, vp, i, C.c_uint64, vp, i, i, i, vp, i, i, i, i]), "rh_bgv_decode": (i, [vp, i, C.c_uint64, vp, i, vp, i, i, i, i]),
         "rh_bgv_encode_ring_t": (i, [vp, C.c_uint64, vp, i, i, i, vp]), "rh_bgv_decode_ring_t": (i, [vp, C.c_uint64, vp, i, vp, i, i]),
         "rh_bgv_ring_t2q": (i, [vp, vp, i, i, vp, vp, i]), "rh_bgv_ring_q2t": (i, [vp, i, vp, vp, i]),
+        "rh_sample_uniform": (i, [vp, i, U64P, C.c_uint64, C.c_uint64, C.c_uint64, vp, i, i]),
+        "rh_sample_gaussian": (i, [vp, U64P, C.c_uint64, C.c_uint64, vp, i, vp, i]),
+        "rh_sample_ternary": (i, [vp, U64P, C.c_uint64, C.c_uint64, C.c_uint64, vp, i]),
+        "rh_small_lift": (i, [vp, vp, i, i, vp, vp, i, vp, i, i, i]),
+        "rh_rlwe_gadget_encrypt_table_words": (sz, [i, i]),
+        "rh_rlwe_gadget_encrypt": (i, [vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp, i, i, U64P, i, vp, sz]),
+        "rh_rlwe_encrypt_sk": (i, [vp, i, vp, vp, vp, vp, vp, i]), "rh_rlwe_mul_pk": (i, [vp, i, vp, vp, vp, vp, vp, i]),
+        "rh_rlwe_decrypt": (i, [vp, i, vp, vp, vp, vp, vp, i]),
         "rh_kshard_create": (i, [C.POINTER(vp), vp, vp, U64P, i, U64P, i, C.POINTER(i), i, C.POINTER(i), i]),
         "rh_kshard_destroy": (None, [vp]), "rh_kshard_num_digits": (i, [vp]),
         "rh_kshard_digit_range": (i, [vp, i, C.POINTER(i), C.POINTER(i)]),

@@ -1,6 +1,6 @@
 """Host-side mirror of the key-switch callers in core/rlwe: the evaluator methods that
 sequence the ring hot path for rotations and relinearisation, on device-resident batches.  Every step is a call into
-the HIP library; no key generation, no encoders (those stay with the reference).
+the HIP library.  Key generation, encryption and decryption: keygen.py and sampling.py, re-exported at the end of this module.
 
   GadgetProduct          core/rlwe/evaluator_gadget_product.go:16-30
   DecomposeNTT           :431-453        GadgetProductHoisted   :326-349
@@ -116,6 +116,23 @@ class GadgetCiphertext:
         self.digits_per_limb = list(digits_per_limb) if digits_per_limb is not None else None
         if self.BaseTwoDecomposition and (self.levelP > 0 or self.digits_per_limb is None or sum(self.digits_per_limb) != self.digits):
             raise RingHipError("GadgetCiphertext: BaseTwoDecomposition needs at most one P modulus and digits_per_limb summing to the row count")
+
+    @classmethod
+    def from_device(cls, ringQ, ringP, Q, P, BaseTwoDecomposition=0, digits_per_limb=None):
+        """a gadget ciphertext over tables that are already on the device (keygen.KeyGenerator): Q a DevicePoly of (rows * 2, limbs of ringQ, N),
+        P likewise under ringP or None; nothing is copied"""
+        if Q.npoly % 2 or Q.limbs != ringQ.level + 1:
+            raise RingHipError("GadgetCiphertext: expected a (rows * 2, limbs of ringQ, N) device block for Q")
+        if (ringP is None) != (P is None) or (P is not None and (P.npoly != Q.npoly or P.limbs != ringP.level + 1)):
+            raise RingHipError("GadgetCiphertext: expected a (rows * 2, limbs of ringP, N) device block for P")
+        self = object.__new__(cls)
+        self.digits, self.Q, self.P = Q.npoly // 2, Q, P
+        self.levelQ, self.levelP = Q.limbs - 1, (P.limbs - 1 if P is not None else -1)
+        self.BaseTwoDecomposition = int(BaseTwoDecomposition)
+        self.digits_per_limb = list(digits_per_limb) if digits_per_limb is not None else None
+        if self.BaseTwoDecomposition and (self.levelP > 0 or self.digits_per_limb is None or sum(self.digits_per_limb) != self.digits):
+            raise RingHipError("GadgetCiphertext: BaseTwoDecomposition needs at most one P modulus and digits_per_limb summing to the row count")
+        return self
 
     def LevelQ(self):
         return self.levelQ
@@ -1275,3 +1292,12 @@ class RingPackingEvaluator:
         res = Ciphertext([_view(batch.Value[c], slot, 1) for c in (0, 1)], is_ntt=True)
         Evaluator._copy_metadata(batch, res)
         return res
+
+
+# ---- keys and ciphertexts made on the device: the samplers (sampling.py) and core/rlwe/keygenerator.go, encryptor.go, decryptor.go (keygen.py) --------
+from .sampling import (  # noqa: E402,F401
+    KeyedPRNG, NewPRNG, UniformSampler, GaussianSampler, TernarySampler, SmallPoly, lift_small, gaussian_table,
+)
+from .keygen import (  # noqa: E402,F401
+    SecretKey, PublicKey, EvaluationKey, RelinearizationKey, GaloisKey, MemEvaluationKeySet, KeyGenerator, Encryptor, Decryptor, Plaintext,
+)

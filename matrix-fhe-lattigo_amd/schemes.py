@@ -1,6 +1,6 @@
 """Scheme-level callers of the ring hot path for BASELINE configs 3 and 4: the *sequences* of ring calls the reference's
 evaluators issue, on device-resident batches.  Nothing here computes: every step is a Ring method (HIP kernels behind
-the C ABI).  No key material, encoders or encryptors -- those stay with the reference.
+the C ABI).  Key material, encryptors and decryptors: keygen.py; encoders: ckks.py, bgv.py.
 
 * ``MatrixCKKSEvaluator.Mul``  schemes/matrix_ckks/evaluator.go:114-192   (config 4, 3N ring)
 * ``ckks_tensor_degree1``      schemes/ckks/evaluator.go:821-834          (config 3 / first half of MulRelin)
