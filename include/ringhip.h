@@ -834,6 +834,45 @@ int rh_rlwe_mul_pk(rh_ring* r, int level, const uint64_t* u, const uint64_t* pk0
  * c2 NULL: degree 1.  out may be c0. */
 int rh_rlwe_decrypt(rh_ring* r, int level, const uint64_t* c0, const uint64_t* c1, const uint64_t* c2, const uint64_t* sk, uint64_t* out, int npoly);
 
+/* ---- the multiparty protocols' hot paths (csrc/multiparty.hip; multiparty/ of the reference) ---------------------------------------------
+ * Standard rings, canonical residues in and out, everything enqueued on the ring's stream.
+ *   rh_mp_aggregate        out = sum over k < nshares of shares[k] mod q on blocks of (npoly, level + 1, N): AggregateShares of every protocol
+ *                          (keygen_cpk.go:86-88, keygen_evk.go:213-242, keyswitch_sk.go:154-161) over many shares at once.  Every share is read
+ *                          once and the sum written once; one conditional subtraction per addend, so the result is that of the pairwise ring.Add
+ *                          calls, word for word.  shares (HOST): nshares device block addresses, staged into table_dev (device scratch of at
+ *                          least rh_mp_aggregate_table_words(nshares) words).  out may be one of the shares; it may overlap none otherwise.
+ *   rh_mp_gadget_share     every row of one party's evaluation-key, Galois-key or public-key shares for one or many keys in one launch
+ *                          (keygen_evk.go:115-210, keygen_gal.go:57-78, keygen_cpk.go:70-83):
+ *                            share[r] = MForm(e_r) + skIn[key_r] * s_r (on the Q limbs where s_r != 0) - crp[r] * skOut[key_r]
+ *                          eQ / eP: the NTT of the lifted errors; crpQ / crpP: the common reference rows; shareQ / shareP: the output; all
+ *                          (rows, limbs, N).  skOutQ / skOutP: (nkeys, limbs, N), skInQ: (skin_keys, levelQ + 1, N), skin_keys = nkeys or 1, NTT
+ *                          domain, Montgomery form.  rowtab (HOST) and table_dev: as rh_rlwe_gadget_encrypt's (rh_mp_gadget_share_table_words).
+ *                          A public-key share is one row whose scalars are all 0.  ringP NULL: no P (eP, crpP, shareP, skOutP NULL).
+ *   rh_mp_relin_round_one  both components of every row of a party's round-one relinearisation share, the CRP read once (keygen_relin.go:130-222):
+ *                            share[r][0] = e0_r + skI * s_r (on the Q limbs where s_r != 0) - u * crp[r],   share[r][1] = e1_r + sk * crp[r]
+ *                          e0, e1: the NTT of the lifted errors, NOT in Montgomery form; crp: (rows, limbs, N); share: (rows, 2, limbs, N); u, sk:
+ *                          (limbs, N), NTT domain, Montgomery form; skIQ = IMForm(sk) on Q.  s_r = MForm(P 2^(j pw2)), so skI * s_r is the plain
+ *                          residue of P 2^(j pw2) sk.  rowtab / table_dev: as rh_mp_gadget_share's (the key index is not read).
+ *   rh_mp_relin_round_two  out[r] = r1[r][0] * sk + e_r + (u - sk) * r1[r][1] (keygen_relin.go:231-270): r1 the aggregated round-one share
+ *                          (rows, 2, limbs, N), both components read once; e and out: (rows, limbs, N).
+ *   rh_mp_keyswitch_share  out = [acc +] c1 * (skA [- skB]) [+ e] on a batch of npoly ciphertexts (keyswitch_sk.go:118-149; with acc and
+ *                          without skB the secret-key term of keyswitch_pk.go).  c1: row (poly, limb) at (poly * c1_rows + limb) * N, c1_rows >=
+ *                          level + 1 (a ciphertext above the share's level); skA, skB: (level + 1, N), NTT domain, Montgomery form; acc, e, out:
+ *                          (npoly, level + 1, N), e the NTT of the lifted error.  skB, acc and e may be NULL; out may be acc or e. */
+size_t rh_mp_aggregate_table_words(int nshares);
+int rh_mp_aggregate(rh_ring* r, int level, const uint64_t* const* shares, int nshares, uint64_t* out, int npoly, uint64_t* table_dev, size_t table_words);
+size_t rh_mp_gadget_share_table_words(int levelQ, int rows);
+int rh_mp_gadget_share(rh_ring* ringQ, rh_ring* ringP, int levelQ, int levelP, const uint64_t* eQ, const uint64_t* eP, const uint64_t* crpQ, const uint64_t* crpP,
+                       uint64_t* shareQ, uint64_t* shareP, const uint64_t* skOutQ, const uint64_t* skOutP, const uint64_t* skInQ, int nkeys, int skin_keys,
+                       const uint64_t* rowtab, int rows, uint64_t* table_dev, size_t table_words);
+int rh_mp_relin_round_one(rh_ring* ringQ, rh_ring* ringP, int levelQ, int levelP, const uint64_t* e0Q, const uint64_t* e0P, const uint64_t* e1Q, const uint64_t* e1P,
+                          const uint64_t* crpQ, const uint64_t* crpP, uint64_t* shareQ, uint64_t* shareP, const uint64_t* uQ, const uint64_t* uP,
+                          const uint64_t* skQ, const uint64_t* skP, const uint64_t* skIQ, const uint64_t* rowtab, int rows, uint64_t* table_dev, size_t table_words);
+int rh_mp_relin_round_two(rh_ring* ringQ, rh_ring* ringP, int levelQ, int levelP, const uint64_t* eQ, const uint64_t* eP, const uint64_t* r1Q, const uint64_t* r1P,
+                          uint64_t* outQ, uint64_t* outP, const uint64_t* uQ, const uint64_t* uP, const uint64_t* skQ, const uint64_t* skP, int rows);
+int rh_mp_keyswitch_share(rh_ring* r, int level, const uint64_t* c1, int c1_rows, const uint64_t* skA, const uint64_t* skB, const uint64_t* acc,
+                          const uint64_t* e, uint64_t* out, int npoly);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,3 +18,4 @@ from . import lintrans  # noqa: F401,E402
 from . import dft  # noqa: F401,E402
 from . import mod1  # noqa: F401,E402
 from . import bootstrapping  # noqa: F401,E402
+from . import multiparty  # noqa: F401,E402

@@ -182,6 +182,11 @@ def lib():
         "rh_rlwe_gadget_encrypt": (i, [vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp, i, i, U64P, i, vp, sz]),
         "rh_rlwe_encrypt_sk": (i, [vp, i, vp, vp, vp, vp, vp, i]), "rh_rlwe_mul_pk": (i, [vp, i, vp, vp, vp, vp, vp, i]),
         "rh_rlwe_decrypt": (i, [vp, i, vp, vp, vp, vp, vp, i]),
+        "rh_mp_aggregate_table_words": (sz, [i]), "rh_mp_aggregate": (i, [vp, i, C.POINTER(vp), i, vp, i, vp, sz]),
+        "rh_mp_gadget_share_table_words": (sz, [i, i]),
+        "rh_mp_gadget_share": (i, [vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, U64P, i, vp, sz]),
+        "rh_mp_keyswitch_share": (i, [vp, i, vp, i, vp, vp, vp, vp, vp, i]),
+        "rh_mp_relin_round_one": (i, [vp, vp, i, i] + [vp] * 13 + [U64P, i, vp, sz]), "rh_mp_relin_round_two": (i, [vp, vp, i, i] + [vp] * 10 + [i]),
         "rh_kshard_create": (i, [C.POINTER(vp), vp, vp, U64P, i, U64P, i, C.POINTER(i), i, C.POINTER(i), i]),
         "rh_kshard_destroy": (None, [vp]), "rh_kshard_num_digits": (i, [vp]),
         "rh_kshard_digit_range": (i, [vp, i, C.POINTER(i), C.POINTER(i)]),
