@@ -873,6 +873,41 @@ int rh_mp_relin_round_two(rh_ring* ringQ, rh_ring* ringP, int levelQ, int levelP
 int rh_mp_keyswitch_share(rh_ring* r, int level, const uint64_t* c1, int c1_rows, const uint64_t* skA, const uint64_t* skB, const uint64_t* acc,
                           const uint64_t* e, uint64_t* out, int npoly);
 
+/* ---- the share conversion of the collective refresh (csrc/mp_refresh.hip; multiparty/mpckks of the reference) ------------------------------
+ * Multiword integers per coefficient on the device, where the reference walks []*big.Int on the host.  A big-integer BLOCK holds npoly * n
+ * values of W 64-bit words each (1 <= W <= 8), little-endian, two's complement, word-major in memory: word w of value i of poly p is at
+ * blk[(p * W + w) * n + i].  n: a power of two, 2 <= n <= N (n = 2 * slots on a standard ring); value i belongs to coefficient i * gap,
+ * gap = N / n.  Standard rings; polys are COEFFICIENT-domain, canonical residues; everything is enqueued on the ring's stream (the target
+ * ring's for rh_mp_refresh_recode).  The reference's non-NTT sparse branch (core/rlwe/utils.go:235-240) is not reproduced.
+ *   rh_mp_big_sample      the mask law of mpckks/sharing.go:120-129: RandInt(prng, 2^logBound), then - 2^logBound when >= 2^(logBound - 1),
+ *                         which is logBound uniform bits sign-extended from bit logBound - 1; no rejection.  Word w of value i of poly p is word
+ *                         i % 8 of block t = 0 of substream (call, poly0 + p, row = w, group = i / 8) of the samplers' stream (above);
+ *                         1 <= logBound <= 64 W - 1.  The ring gives the device and the stream alone.
+ *   rh_mp_big_to_rns      SetCoefficientsBigint (ring/ring.go:433-447) with the spread of NTTSparseAndMontgomery (core/rlwe/utils.go:187-245):
+ *                         limb k <= level of coefficient i * gap is value_i mod q_k, Euclidean and canonical as big.Int.Mod gives, zero
+ *                         elsewhere.  out: dense (npoly, level + 1, N).  accumulate = +1 / -1: added to / subtracted from what is there instead
+ *                         (the Sub of mpckks/sharing.go:140 and the Add of :259), the coefficients between left as they are.
+ *   rh_mp_big_from_rns    PolyToBigintCentered(p, gap, .) (ring/ring.go:503-543): v = CRT(limbs 0..level of coefficient i * gap) in [0, Q),
+ *                         value_i = v - Q when v >= floor(Q / 2) (note the >=), else v.  in: row (poly, limb) at (poly * in_rows + limb) * N.
+ *                         accumulate != 0: added to the value that is there (the Add of mpckks/sharing.go:172-178), modulo 2^(64 W).
+ *                         RH_ERR_UNSUPPORTED when Q_level >= 2^511, the most eight words centre, or the level has more than 16 limbs;
+ *                         RH_ERR_ARG when the caller's W is too small for Q_level.
+ *   rh_mp_big_muldiv      out = Quo(x * m, d) per value, truncated TOWARD ZERO like big.Int.Quo (mpckks/transform.go:363-376).  m: mwords <= 2
+ *                         words, d > 0: dwords <= 4 words (HOST, little-endian).  The product is held in W + 2 words; a quotient that does
+ *                         not fit W words is the caller's error.  out may be blk.  The ring gives the device and the stream alone.
+ *   rh_mp_refresh_recode  from-RNS at levelIn of ringIn, muldiv, to-RNS at levelOut of ringOut in ONE kernel, no block in memory: the bits of
+ *                         the three calls.  Source: `in` (with ringIn, in_rows; blk NULL), the Transform of mpckks/transform.go:300-376, or
+ *                         `blk` (in and ringIn NULL), the second half of its GenShare.  W: the words a value is held in, enough for the
+ *                         centred source and for the quotient.  ringOut may have another degree, n <= N_out.  The launch goes to ringOut's
+ *                         stream and orders nothing against ringIn's: two handles must be on ONE stream (rh_ring_set_stream), as every
+ *                         protocol of multiparty_refresh.py that takes two rings requires of its caller. */
+int rh_mp_big_sample(rh_ring* r, const uint64_t* state, uint64_t call, uint64_t poly0, int logBound, uint64_t* blk_dev, int n, int W, int npoly);
+int rh_mp_big_to_rns(rh_ring* r, int level, const uint64_t* blk_dev, int n, int W, uint64_t* out_dev, int npoly, int accumulate);
+int rh_mp_big_from_rns(rh_ring* r, int level, const uint64_t* in_dev, int in_rows, uint64_t* blk_dev, int n, int W, int npoly, int accumulate);
+int rh_mp_big_muldiv(rh_ring* r, const uint64_t* blk_dev, uint64_t* out_dev, int n, int W, int npoly, const uint64_t* m, int mwords, const uint64_t* d, int dwords);
+int rh_mp_refresh_recode(rh_ring* ringIn, int levelIn, const uint64_t* in_dev, int in_rows, const uint64_t* blk_dev, int n, int W, rh_ring* ringOut,
+                         int levelOut, uint64_t* out_dev, int npoly, const uint64_t* m, int mwords, const uint64_t* d, int dwords, int accumulate);
+
 #ifdef __cplusplus
 }
 #endif

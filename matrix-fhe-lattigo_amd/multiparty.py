@@ -26,7 +26,10 @@ Every arithmetic entry takes `samples=` in place of its PRNG (the exact keys are
 tests/multiparty_restatement.py.  FUSED_MULTIPARTY selects, per family, the kernels of csrc/multiparty.hip or the composed ring calls of the
 reference: the same bits either way; `fused=` overrides per call.
 
-Not built, refused by name or absent: RefreshProtocol, multiparty/mpckks and mpbgv, binary serialisation of shares, ShallowCopy (nothing here is
+The collective refresh of multiparty/mpckks -- big-integer shares on the device, EncToShare, ShareToEnc, the masked transform and Refresh -- is
+multiparty_refresh.py, imported below: rh.multiparty.mpckks and the names beside it; multiparty/mpbgv, composed from existing calls, is there too.
+
+Not built, refused by name or absent: a non-nil CKKS transform function, binary serialisation of shares, ShallowCopy (nothing here is
 shared mutable state), compressed shares, conjugate-invariant and 3N rings, a flooding law that is not a discrete Gaussian, a flooding bound
 with floor(bound) >= 1024."""
 import ctypes as C
@@ -1007,3 +1010,8 @@ class Combiner:
         if self.ringP is not None:
             self.ringP.MulRNSScalarMontgomery(ownShare.P, scal[LQ:], skOut.Value.P)
         skOut.coeffs = None
+
+
+# ---- the collective refresh (multiparty_refresh.py; at the end: it builds on the classes above) ---------------------------------------------------
+from .multiparty_refresh import (FUSED_REFRESH, AdditiveShare, AdditiveShareBigint, GetMinimumLevelForRefresh, NewAdditiveShare, NewAdditiveShareBigint,  # noqa: E402,F401
+                                 MaskedTransformFunc, RefreshShare, big_from_rns, big_muldiv, big_sample, big_to_rns, mpbgv, mpckks, refresh_recode)

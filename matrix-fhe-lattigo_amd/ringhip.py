@@ -187,6 +187,9 @@ def lib():
         "rh_mp_gadget_share": (i, [vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, U64P, i, vp, sz]),
         "rh_mp_keyswitch_share": (i, [vp, i, vp, i, vp, vp, vp, vp, vp, i]),
         "rh_mp_relin_round_one": (i, [vp, vp, i, i] + [vp] * 13 + [U64P, i, vp, sz]), "rh_mp_relin_round_two": (i, [vp, vp, i, i] + [vp] * 10 + [i]),
+        "rh_mp_big_sample": (i, [vp, U64P, C.c_uint64, C.c_uint64, i, vp, i, i, i]), "rh_mp_big_to_rns": (i, [vp, i, vp, i, i, vp, i, i]),
+        "rh_mp_big_from_rns": (i, [vp, i, vp, i, vp, i, i, i, i]), "rh_mp_big_muldiv": (i, [vp, vp, vp, i, i, i, U64P, i, U64P, i]),
+        "rh_mp_refresh_recode": (i, [vp, i, vp, i, vp, i, i, vp, i, vp, i, U64P, i, U64P, i, i]),
         "rh_kshard_create": (i, [C.POINTER(vp), vp, vp, U64P, i, U64P, i, C.POINTER(i), i, C.POINTER(i), i]),
         "rh_kshard_destroy": (None, [vp]), "rh_kshard_num_digits": (i, [vp]),
         "rh_kshard_digit_range": (i, [vp, i, C.POINTER(i), C.POINTER(i)]),
