@@ -833,6 +833,22 @@ int rh_rlwe_mul_pk(rh_ring* r, int level, const uint64_t* u, const uint64_t* pk0
 /* Decryptor.Decrypt's Horner sum c0 + s (c1 + s c2) (core/rlwe/decryptor.go:51-92), NTT domain, canonical, every component read once.
  * c2 NULL: degree 1.  out may be c0. */
 int rh_rlwe_decrypt(rh_ring* r, int level, const uint64_t* c0, const uint64_t* c1, const uint64_t* c2, const uint64_t* sk, uint64_t* out, int npoly);
+/* The entries of this section take standard rings and 3N rings whose degree is a multiple of 8 (a sampler lane serves a group of eight
+ * coefficients); ringQ and ringP of the same kind; every kernel addresses row r at r * N words.  Conjugate-invariant rings are refused. */
+
+/* ---- the Matrix CKKS encoder (csrc/matrix_ckks.hip; schemes/matrix_ckks/encoder.go) --------------------------------------------------------
+ * 3N rings.  Values are (nvec, nvals) blocks on the device: vtype 0 = uint64, 1 = float64, 2 = complex128 (interleaved; real parts only,
+ * encoder.go:237-241).  nvals > N: "too many values: %d > %d" (:182-184).  Enqueued on the ring's stream.
+ *   rh_matrix_ckks_encode  Encode (:163-257) through SingleFloat64ToFixedPointCRT (:384-426) into a dense (nvec, level + 1, N) block, coefficient
+ *                          domain, coefficients i >= nvals zero: uint64 through float64(val); the sign onto the scale; the product truncated;
+ *                          from 2^64 on the low 64 bits of the integer the float is, no sign applied; below, a negative value gives -c modulo
+ *                          2^64.  The reference stores CRed(word, q_i) (it can stay >= q_i); this entry stores that word's canonical residue.
+ *                          negatives_signed != 0: a negative value stores q_i - (|c| mod q_i) instead, which Decode gives back.
+ *   rh_matrix_ckks_decode  polyToFloatNoCRT (:430-445) on limb 0 of a coefficient-domain block with pt_rows limbs per poly:
+ *                          c >= q_0 >> 1 ? -float64(q_0 - c) / scale : float64(c) / scale, the first nvals coefficients, into float64, complex128
+ *                          (imaginary part 0) or uint64 (truncated, :299-302; a negative value's word is not defined there: 0). */
+int rh_matrix_ckks_encode(rh_ring* r, int level, double scale, const void* values_dev, int vtype, int nvals, int nvec, int negatives_signed, uint64_t* pt_dev);
+int rh_matrix_ckks_decode(rh_ring* r, double scale, const uint64_t* pt_dev, int pt_rows, int nvec, int nvals, int vtype, void* values_dev);
 
 /* ---- the multiparty protocols' hot paths (csrc/multiparty.hip; multiparty/ of the reference) ---------------------------------------------
  * Standard rings, canonical residues in and out, everything enqueued on the ring's stream.

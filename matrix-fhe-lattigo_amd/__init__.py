@@ -19,3 +19,4 @@ from . import dft  # noqa: F401,E402
 from . import mod1  # noqa: F401,E402
 from . import bootstrapping  # noqa: F401,E402
 from . import multiparty  # noqa: F401,E402
+from . import matrix_ckks  # noqa: F401,E402

@@ -16,9 +16,24 @@
 #include "qp_rows_host.hpp"
 #include "keygen_kernels.hip.hpp"
 
-// the samplers' common checks: a standard ring whose rows split into groups of eight coefficients
+// The rings of this file: standard rings, and 3N rings whose rows split into groups of eight coefficients (every kernel here addresses row r at
+// r * N words).  Conjugate-invariant rings are refused.  The other checks are those of the row-streaming entries: level, limb and row counts.
+static int kg_ring_ok(const rh_ring* r, int level, int count, const char* who, const char* negative = "negative count") {
+  if (!r) return rh_fail(RH_ERR_ARG, "%s: null ring handle", who);
+  if (r->kind == RH_RING_CI) return rh_fail(RH_ERR_UNSUPPORTED, "%s: conjugate-invariant rings are not supported", who);
+  if (r->kind != RH_RING_STANDARD && (r->N & 7))
+    return rh_fail(RH_ERR_UNSUPPORTED, "%s: a 3N ring of degree %d: the samplers serve groups of eight coefficients (N %% 8 must be 0)", who, r->N);
+  if (level < 0 || level >= r->L) return rh_fail(RH_ERR_ARG, "%s: level %d out of range [0,%d)", who, level, r->L);
+  if (level + 1 > RH_MAX_LIMBS) return rh_fail(RH_ERR_ARG, "%s: at most %d limbs", who, RH_MAX_LIMBS);
+  if (r->N < 4) return rh_fail(RH_ERR_ARG, "%s: N < 4", who);
+  if (count < 0) return rh_fail(RH_ERR_ARG, "%s: %s", who, negative);
+  if ((size_t)count * 2 * (size_t)(level + 1) > 0x7fffffffu) return rh_fail(RH_ERR_ARG, "%s: too many rows for one launch", who);
+  return RH_OK;
+}
+
+// the samplers' common checks: rows that split into groups of eight coefficients
 static int samp_ok(const rh_ring* r, int level, int npoly, const uint64_t* state, const void* out, const char* who) {
-  if (int rc = rh_ring_ok(r, level, npoly, who, "npoly < 0")) return rc;
+  if (int rc = kg_ring_ok(r, level, npoly, who, "npoly < 0")) return rc;
   if (r->N < 8) return rh_fail(RH_ERR_ARG, "%s: N < 8 (a lane serves a group of eight coefficients)", who);
   if (!state || !out) return rh_fail(RH_ERR_ARG, "%s: null argument", who);
   if ((uintptr_t)out & 15) return rh_fail(RH_ERR_ARG, "%s: every block must be 16-byte aligned", who);
@@ -75,9 +90,9 @@ extern "C" int rh_sample_ternary(rh_ring* r, const uint64_t* state, uint64_t cal
 
 // ringP may be NULL (levelP ignored, outP NULL): the residues under Q alone
 static int qp_pair_ok(const rh_ring* rQ, const rh_ring* rP, int levelQ, int levelP, int count, const char* who) {
-  if (int rc = rh_ring_ok(rQ, levelQ, count, who)) return rc;
+  if (int rc = kg_ring_ok(rQ, levelQ, count, who)) return rc;
   if (!rP) return RH_OK;
-  if (rP->kind != RH_RING_STANDARD) return rh_fail(RH_ERR_UNSUPPORTED, "%s: standard rings only (3N and conjugate-invariant rings are not supported)", who);
+  if (rP->kind != rQ->kind) return rh_fail(RH_ERR_UNSUPPORTED, "%s: ringQ and ringP must be of the same kind", who);
   if (rP->N != rQ->N || rP->device != rQ->device) return rh_fail(RH_ERR_ARG, "%s: ringQ and ringP differ in degree or device", who);
   if (levelP < 0 || levelP >= rP->L || levelP + 1 > RH_MAX_LIMBS) return rh_fail(RH_ERR_ARG, "%s: levelP %d out of range [0,%d)", who, levelP, rP->L);
   return RH_OK;
@@ -136,14 +151,14 @@ extern "C" int rh_rlwe_gadget_encrypt(rh_ring* rQ, rh_ring* rP, int levelQ, int 
   memcpy(stage->h, rowtab, words * 8);
   if (int rc = rh_stage_upload(stage, table_dev, words, st, who)) return rc;
   const GadgetEncArgs p{eQ, eP, tabQ, tabP, skOutQ, skOutP, skInQ, table_dev, skin_keys == 1 && nkeys > 1 ? 1 : 0};
-  rlwe_gadget_encrypt_kernel<<<dim3((unsigned)rows * (unsigned)(LQ + LP), g.grid.y), 256, 0, st>>>(p, (unsigned)N, rQ->logN, rQ->d_consts,
+  rlwe_gadget_encrypt_kernel<<<dim3((unsigned)rows * (unsigned)(LQ + LP), g.grid.y), 256, 0, st>>>(p, (unsigned)N, rQ->d_consts,
                                                                                                     rP ? rP->d_consts : rQ->d_consts, LQ, LP, g.nt);
   return rh_launch_ok("rlwe_gadget_encrypt_kernel");
 }
 
 // blocks of (npoly, level + 1, N) words each, 16-byte aligned; `out` may be one of the per-poly inputs (every lane reads its words before it writes them)
 static int rows_ok(const rh_ring* r, int level, int npoly, const char* who) {
-  if (int rc = rh_ring_ok(r, level, npoly, who, "npoly < 0")) return rc;
+  if (int rc = kg_ring_ok(r, level, npoly, who, "npoly < 0")) return rc;
   return RH_OK;
 }
 static bool misaligned(std::initializer_list<const void*> ps) {

@@ -108,18 +108,18 @@ small_lift_kernel(const int* __restrict__ in, u64* outQ, int q_rows, u64* outP, 
 struct GadgetEncArgs { const u64* eQ; const u64* eP; u64* tabQ; u64* tabP; const u64* soQ; const u64* soP; const u64* siQ; const u64* rowtab; int si_shared; };
 
 __global__ void __launch_bounds__(256)
-rlwe_gadget_encrypt_kernel(GadgetEncArgs p, unsigned n, int logN, const LimbConsts* __restrict__ constsQ, const LimbConsts* __restrict__ constsP,
+rlwe_gadget_encrypt_kernel(GadgetEncArgs p, unsigned n, const LimbConsts* __restrict__ constsQ, const LimbConsts* __restrict__ constsP,
                            int LQ, int LP, int nt) {
-  const StreamRowQP r(blockIdx.x, constsQ, constsP, LQ, LP, logN);
+  const StreamRowQP r(blockIdx.x, constsQ, constsP, LQ, LP, StreamRowQP::RowLen{n});       // rows of n words: n = 3 * 2^k on 3N rings
   const u64* rt = p.rowtab + (size_t)r.poly * (size_t)(1 + LQ);
   const size_t key = (size_t)rt[0];
   const u64 s = r.inQ ? rt[1 + r.l] : 0;
   const int Lr = r.inQ ? LQ : LP;
   const u64* e = (r.inQ ? p.eQ : p.eP) + r.ro;
-  u64* tab = (r.inQ ? p.tabQ : p.tabP) + (((size_t)r.poly * 2 * Lr + r.l) << logN);
-  const u64* a = tab + ((size_t)Lr << logN);
-  const u64* so = (r.inQ ? p.soQ : p.soP) + ((key * Lr + r.l) << logN);
-  const u64* si = s ? p.siQ + (((p.si_shared ? 0 : key) * LQ + r.l) << logN) : nullptr;
+  u64* tab = (r.inQ ? p.tabQ : p.tabP) + ((size_t)r.poly * 2 * Lr + r.l) * n;
+  const u64* a = tab + (size_t)Lr * n;
+  const u64* so = (r.inQ ? p.soQ : p.soP) + (key * Lr + r.l) * n;
+  const u64* si = s ? p.siQ + ((p.si_shared ? 0 : key) * LQ + r.l) * n : nullptr;
   const LimbConsts c = r.c;
   RH_FOR_EACH_PAIR(i, 0, n >> 1) {
     const ulonglong2 ev = rh_ld2(e + 2 * (size_t)i, nt), av = rh_ld2(a + 2 * (size_t)i, nt), sv = rh_ld2(so + 2 * (size_t)i, false);

@@ -53,6 +53,18 @@ struct StreamRowQP {
     po = (size_t)l << logN;
     ro = ((size_t)poly * (inQ ? LQ : LP) + l) << logN;
   }
+  // ... on rows of `len.n` words, for rings whose degree is no power of two (3N rings: logN is rounded up there).  The offsets are products of
+  // wave-uniform values (blockIdx.x and kernel arguments), formed once per workgroup before the pair loop.
+  struct RowLen { unsigned n; };
+  RH_DEV StreamRowQP(u32 row, const LimbConsts* __restrict__ constsQ, const LimbConsts* __restrict__ constsP, int LQ, int LP, RowLen len) {
+    const u32 LT_ = (u32)(LQ + LP);
+    poly = row / LT_; l = row % LT_;
+    inQ = l < (u32)LQ;
+    if (!inQ) l -= (u32)LQ;
+    c = inQ ? constsQ[l] : constsP[l];
+    po = (size_t)l * len.n;
+    ro = ((size_t)poly * (inQ ? LQ : LP) + l) * len.n;
+  }
   // this row of component `comp` of a pack
   RH_DEV u64* of(const RhQP& a, u32 comp) const { return (inQ ? a.q[comp] : a.p[comp]) + ro; }
   RH_DEV const u64* of(const RhQPc& a, u32 comp) const { return (inQ ? a.q[comp] : a.p[comp]) + ro; }

@@ -11,13 +11,25 @@ Every arithmetic entry takes `samples=` in place of the PRNG: the uniform block(
 how it is pinned bit for bit (tests/keygen_restatement.py).  FUSED_KEYGEN selects the kernels of csrc/keygen.hip (rh_rlwe_gadget_encrypt,
 rh_rlwe_encrypt_sk, rh_rlwe_mul_pk, rh_rlwe_decrypt) or the composed ring calls of the reference: the same bits either way.
 
+Rings: standard rings, and 3N rings (kind Matrix3N) whose degree is a multiple of 8; ringQ and ringP of the same kind.  On a 3N ring every
+NTT-domain block this module stores or hands out -- SecretKey.Value, public and evaluation keys, the ciphertexts Encrypt writes -- is in the
+REFERENCE's order (ring/ntt_3n.go:82-109), which is what the key-switch kernels read, whatever Ring.ntt3n_layout says: the transforms of this
+module run with the ring's layout switched to the reference's order (reference_order below), a block-order plaintext or ciphertext that comes in
+is converted with Ring.ToReferenceOrder first, and every block written carries the tag of what it holds (DevicePoly.layout = None).
+
+The error law: xe = (sigma, bound), the discrete Gaussian, or ("P", density) / ("H", weight), a ternary law through TernarySampler (the
+reference's Matrix CKKS test parameters use Xe = ring.Ternary{H: 1}; ring.NewSampler takes any law).
+
 Not built, refused by name: compressed (seeded) keys, evaluation keys between ring degrees, GenEvaluationKeysForRingSwapNew,
-conjugate-invariant and 3N rings, the big-norm Gaussian, a plaintext and a ciphertext in different domains or allocated at different levels."""
+conjugate-invariant rings, 3N degrees that are no multiple of 8, Galois keys on 3N rings, the big-norm Gaussian, a plaintext and a ciphertext in
+different domains or allocated at different levels."""
+import functools
+
 import numpy as np
 
-from .ringhip import BasisExtender, DevicePoly, RingHipError, Standard, U64P, _check, lib
+from .ringhip import BasisExtender, DevicePoly, Matrix3N, RingHipError, Standard, U64P, _check, lib
 from .rlwe import ElementQP, GadgetCiphertext, PolyQP
-from .sampling import GaussianSampler, NewPRNG, SmallPoly, TernarySampler, UniformSampler, lift_small
+from .sampling import GaussianSampler, NewPRNG, SmallPoly, TernarySampler, UniformSampler, lift_small, rings_ok
 from .schemes import Ciphertext
 
 FUSED_KEYGEN = True          # the kernels of csrc/keygen.hip (True) or the composed ring calls (False); the measured choice: profiles/keygen.json
@@ -38,6 +50,31 @@ def _standard(*rings):
     for r in rings:
         if r is not None and r.kind != Standard:
             raise RingHipError("keygen: standard rings only (3N and conjugate-invariant rings are not supported)")
+
+
+def reference_order(method):
+    """3N rings: run `method` of an object with ringQ (and ringP) with Ring.NTT writing the reference's order, and put the rings' layout back"""
+    @functools.wraps(method)
+    def run(self, *args, **kw):
+        rings = [r for r in (self.ringQ, getattr(self, "ringP", None)) if r is not None and r.kind == Matrix3N and r.ntt3n_layout is not None]
+        saved = [r.ntt3n_layout for r in rings]
+        for r in rings:
+            r.ntt3n_layout = None
+        try:
+            return method(self, *args, **kw)
+        finally:
+            for r, lay in zip(rings, saved):
+                r.ntt3n_layout = lay
+    return run
+
+
+def error_sampler(prng, ring, xe):
+    """the sampler of the error law xe: (sigma, bound), or ("P", density) / ("H", weight)"""
+    if isinstance(xe[0], str):
+        if xe[0] not in ("P", "H") or len(xe) != 2:
+            raise RingHipError("the error law is (sigma, bound), (\"P\", density) or (\"H\", weight)")
+        return TernarySampler(prng, ring, **{xe[0]: xe[1]})
+    return GaussianSampler(prng, ring, *xe)
 
 
 class Plaintext:
@@ -163,17 +200,18 @@ class KeyGenerator:
     """rlwe.KeyGenerator over (ringQ, ringP): ringP None for parameters without P.  xs: ("P", density) or ("H", weight); xe: (sigma, bound)."""
 
     def __init__(self, ringQ, ringP=None, xs=("P", 2 / 3), xe=(3.2, 19), prng=None):
-        _standard(ringQ, ringP)
+        rings_ok("KeyGenerator", ringQ, ringP)
         if ringP is not None and ringP.N != ringQ.N:
             raise RingHipError("KeyGenerator: ringQ and ringP differ in degree")
         self.ringQ, self.ringP = ringQ, ringP
         self.prng = NewPRNG() if prng is None else prng
         self.xs, self.xe = tuple(xs), tuple(xe)
         self.uniform = UniformSampler(self.prng, ringQ, ringP)
-        self.gauss = GaussianSampler(self.prng, ringQ, *self.xe)
+        self.gauss = error_sampler(self.prng, ringQ, self.xe)
         self.Q, self.P = [int(q) for q in ringQ.moduli], [int(p) for p in ringP.moduli] if ringP is not None else []
 
     # ---- secret keys ------------------------------------------------------------------------------------------------------------------------
+    @reference_order
     def _secret_from(self, small):
         """genSecretKeyFromSampler (:60-72): lift under QP, NTT, MForm"""
         rq, rp = self.ringQ, self.ringP
@@ -214,6 +252,7 @@ class KeyGenerator:
             raise RingHipError("evaluation key parameters: levelQ %d or levelP %d out of range" % (levelQ, levelP))
         return levelQ, levelP, int(BaseTwoDecomposition)
 
+    @reference_order
     def gadget_rows(self, skIn, skOutQ, skOutP, levelQ, levelP, pw2, nkeys, plaintext=True, samples=None, fused=None, dpl=None):
         """`nkeys` gadget ciphertexts at (levelQ, levelP) in one launch sequence (genEvaluationKey :276-316 for each): one uniform Read for every a,
         written straight into component 1 of the tables; one Gaussian Read, one lift and one NTT over every error row; one rh_rlwe_gadget_encrypt
@@ -357,6 +396,8 @@ class KeyGenerator:
     def GenGaloisKeysNew(self, galEls, sk, levelQ=None, levelP=None, BaseTwoDecomposition=0, compressed=False, samples=None, fused=None):
         """(:195-205) as ONE launch sequence over all keys: skOut_k = the NTT automorphism of ModInvGaloisElement(g_k) on sk (:150-170), skIn = sk"""
         galEls = [int(g) for g in galEls]
+        if self.ringQ.kind == Matrix3N:
+            raise RingHipError("cannot GenGaloisKey: 3N rings have no automorphism (ring/automorphism.go:14-20: N must be a power of two)")
         levelQ, levelP, pw2 = self._levels(levelQ, levelP, BaseTwoDecomposition, compressed)
         if not galEls:
             return []
@@ -407,7 +448,7 @@ class Encryptor:
     Read per batch, the ciphertext's index within the batch in the substream id."""
 
     def __init__(self, ringQ, ringP=None, key=None, prng=None, xs=("P", 2 / 3), xe=(3.2, 19)):
-        _standard(ringQ, ringP)
+        rings_ok("Encryptor", ringQ, ringP)
         self.ringQ, self.ringP, self.key = ringQ, ringP, key
         self.xs, self.xe = tuple(xs), tuple(xe)
         self._set_prng(NewPRNG() if prng is None else prng)
@@ -416,7 +457,7 @@ class Encryptor:
     def _set_prng(self, prng):
         self.prng = prng
         self.uniform = UniformSampler(prng, self.ringQ, self.ringP)
-        self.gauss = GaussianSampler(prng, self.ringQ, *self.xe)
+        self.gauss = error_sampler(prng, self.ringQ, self.xe)
         self.ternary = TernarySampler(prng, self.ringQ, **{self.xs[0]: self.xs[1]})
 
     def _copy(self):
@@ -478,11 +519,17 @@ class Encryptor:
         self.Encrypt(pt, ct, samples, fused)
         return ct
 
+    @reference_order
     def _encrypt(self, pt, ct, samples, fused):
         if self.key is None:
             raise RingHipError("cannot encrypt: Encryptor has no encryption key")
         if isinstance(ct, ElementQP):
             return self._zero_qp(ct, samples, fused)
+        if self.ringQ.kind == Matrix3N:
+            for v in ct.Value:
+                v.layout = None                                            # written whole below, in the reference's order: a stale tag must not steer an INTT
+            if pt is not None and pt.IsNTT:
+                self.ringQ.ToReferenceOrder(_pt_poly(pt))
         if ct.Degree() != 1:
             raise RingHipError("cannot encrypt: the device path takes ciphertexts of degree 1")
         level = ct.Level()
@@ -613,12 +660,20 @@ class Decryptor:
     """rlwe.Decryptor (decryptor.go:42-90): pt = c0 + s (c1 + s c2), degree <= 2, in the ciphertext's domain"""
 
     def __init__(self, ringQ, sk):
-        _standard(ringQ)
+        rings_ok("Decryptor", ringQ)
         self.ringQ, self.sk = ringQ, sk
 
+    @reference_order
     def Decrypt(self, ct, pt, fused=None):
         level = min(ct.Level(), pt.Level())
         out = _pt_poly(pt)
+        if self.ringQ.kind == Matrix3N:
+            for v in ct.Value:                                             # the secret is held in the reference's order
+                if ct.IsNTT:
+                    self.ringQ.ToReferenceOrder(v)
+                else:
+                    v.layout = None
+            out.layout = None
         if ct.Degree() not in (1, 2):
             raise RingHipError("cannot Decrypt: the device path takes ciphertexts of degree 1 or 2")
         if out.limbs != level + 1 or ct.Level() != level or out.npoly != ct.Value[0].npoly:

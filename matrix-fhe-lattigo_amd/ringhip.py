@@ -182,6 +182,7 @@ def lib():
         "rh_rlwe_gadget_encrypt": (i, [vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp, i, i, U64P, i, vp, sz]),
         "rh_rlwe_encrypt_sk": (i, [vp, i, vp, vp, vp, vp, vp, i]), "rh_rlwe_mul_pk": (i, [vp, i, vp, vp, vp, vp, vp, i]),
         "rh_rlwe_decrypt": (i, [vp, i, vp, vp, vp, vp, vp, i]),
+        "rh_matrix_ckks_encode": (i, [vp, i, C.c_double, vp, i, i, i, i, vp]), "rh_matrix_ckks_decode": (i, [vp, C.c_double, vp, i, i, i, i, vp]),
         "rh_mp_aggregate_table_words": (sz, [i]), "rh_mp_aggregate": (i, [vp, i, C.POINTER(vp), i, vp, i, vp, sz]),
         "rh_mp_gadget_share_table_words": (sz, [i, i]),
         "rh_mp_gadget_share": (i, [vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, U64P, i, vp, sz]),

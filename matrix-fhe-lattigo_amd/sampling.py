@@ -18,14 +18,16 @@ the padded key block is computed here, once per key (blake2b_key_state).
 
 Deviations from the reference, on purpose: the stream is not the Go sampler's sequential byte stream (which consumes a data-dependent number
 of bytes per coefficient); the Gaussian comes from a cumulative table exact to 2^-63; a zero is the canonical 0 whatever its sign (the
-reference writes q for a zero of sign 0).  The big-norm Gaussian (:99-153), conjugate-invariant and 3N rings are refused by name."""
+reference writes q for a zero of sign 0).  Standard rings and 3N rings whose degree is a multiple of 8 (a lane serves a group of eight
+coefficients; rows are addressed at N words, not at 2^logN).  The big-norm Gaussian (:99-153), conjugate-invariant rings and the other 3N
+degrees are refused by name."""
 import ctypes as C
 import secrets
 import struct
 
 import numpy as np
 
-from .ringhip import DevicePoly, RingHipError, Standard, U64P, _check, lib
+from .ringhip import ConjugateInvariant, DevicePoly, Matrix3N, RingHipError, U64P, _check, lib
 
 PERSON = b"ringhip-sampler\0"
 _IV = (0x6a09e667f3bcc908, 0xbb67ae8584caa73b, 0x3c6ef372fe94f82b, 0xa54ff53a5f1d36f1,
@@ -96,9 +98,17 @@ def NewPRNG():
     return KeyedPRNG(secrets.token_bytes(64))
 
 
-def _standard(ring, who):
-    if ring.kind != Standard:
-        raise RingHipError("cannot %s: standard rings only (3N and conjugate-invariant rings are not supported)" % who)
+def rings_ok(who, ring, ringP=None):
+    """the rings of the key layer: standard rings and 3N rings with N % 8 == 0, ringQ and ringP of the same kind"""
+    for r in (ring, ringP):
+        if r is None:
+            continue
+        if r.kind == ConjugateInvariant:
+            raise RingHipError("cannot %s: conjugate-invariant rings are not supported (of the power-of-two rings, standard rings only)" % who)
+        if r.kind == Matrix3N and r.N % 8:
+            raise RingHipError("cannot %s: a 3N ring of degree %d: the samplers serve groups of eight coefficients (N %% 8 must be 0)" % (who, r.N))
+    if ringP is not None and ringP.kind != ring.kind:
+        raise RingHipError("cannot %s: ringQ and ringP must be of the same kind" % who)
 
 
 class SmallPoly:
@@ -143,9 +153,7 @@ class UniformSampler:
     """ring.UniformSampler / ringqp.UniformSampler: uniform residues under the limbs of ringQ and, for QP polys, of ringP (rows LQ, LQ + 1, ...)"""
 
     def __init__(self, prng, ring, ringP=None):
-        _standard(ring, "UniformSampler")
-        if ringP is not None:
-            _standard(ringP, "UniformSampler")
+        rings_ok("UniformSampler", ring, ringP)
         self.prng, self.ring, self.ringP = prng, ring, ringP
 
     def read_rows(self, ring, ptr, out_rows, npoly, call, poly0=0, row0=0):
@@ -191,7 +199,7 @@ class GaussianSampler:
     """ring.GaussianSampler for ring.DiscreteGaussian{Sigma, Bound}: int32 (npoly, N) signed coefficients"""
 
     def __init__(self, prng, ring, sigma=3.2, bound=19):
-        _standard(ring, "GaussianSampler")
+        rings_ok("GaussianSampler", ring)
         self.prng, self.ring, self.sigma, self.bound = prng, ring, float(sigma), float(bound)
         self.table = gaussian_table(sigma, bound)
         self._table = DevicePoly(ring.AtLevel(0), (len(self.table) + ring.N - 1) // ring.N, 1)       # whole rows of N words
@@ -238,7 +246,7 @@ class TernarySampler:
     """ring.TernarySampler for ring.Ternary{P} (on the device) or ring.Ternary{H} (on the host, uploaded): int32 (npoly, N)"""
 
     def __init__(self, prng, ring, P=None, H=None):
-        _standard(ring, "TernarySampler")
+        rings_ok("TernarySampler", ring)
         if (P is None) == (H is None):
             raise RingHipError("TernarySampler: give the density P or the Hamming weight H, one of them")
         self.prng, self.ring, self.P, self.H = prng, ring, P, H
@@ -263,7 +271,7 @@ class TernarySampler:
 def lift_small(ringQ, ringP, small, outQ, outP=None, accumulate=False):
     """int32 coefficients -> residues under every limb of outQ (and of outP under ringP): x >= 0 ? x : q - |x|, what Read +
     ExtendBasisSmallNormAndCenter produce; accumulate: ReadAndAdd, out = CRed(out + lift).  outQ / outP: DevicePoly batches of small.npoly polys."""
-    _standard(ringQ, "lift_small")
+    rings_ok("lift_small", ringQ, ringP if outP is not None else None)
     if outQ.npoly != small.npoly or (outP is not None and outP.npoly != small.npoly):
         raise RingHipError("lift_small: the blocks hold different numbers of polys")
     _check(lib().rh_small_lift(ringQ._h, ringP._h if outP is not None else None, outQ.limbs - 1, outP.limbs - 1 if outP is not None else -1, small.ptr,
