@@ -580,7 +580,17 @@ int rh_bgv_axpby(rh_ring* r, int level, const uint64_t* a_dev, const uint64_t* b
  *                           the same stream.  Unlike its neighbours this entry is NOT in place: an output that overlaps a term (or the
  *                           table) is refused.  Moduli must be below 2^61: the products are summed in 128 bits and reduced once per
  *                           rh_ckks_linear_combination_chunk() = 56 terms, the most that bound allows (csrc/ckks.hip derives it);
- *                           rh_ckks_linear_combination_width() terms have their loads in flight together. */
+ *                           rh_ckks_linear_combination_width() terms have their loads in flight together.
+ *   rh_ckks_axpby           out_j = ra[i] x_j - rb[i] t_j - [j == 0] s mod q_i, the canonical residue, in ONE launch: the step that follows
+ *                           every product of the Chebyshev power basis (circuits/common/polynomial/power_basis.go:148-176: Add(X, X, X), then
+ *                           Add(X, -1, X) or the scale-matching Sub(X, T_c, X)) and, with ra = q_i - 1 and no t, the 2 - x, 1 - x and 1 - z^2 of
+ *                           the inverse circuits.  Every step of those sequences ends in CRed or MRed of exact values, so these are their
+ *                           bits -- except where t has MORE components than x (ring.Neg writes q_i for 0 there), which this entry refuses.
+ *                           ra / rb: host arrays of level + 1 residues (rb with t, NULL without); s0 / s1: the constant on coefficients
+ *                           [0, N/2) / [N/2, N) as rh_ckks_scalar takes it, or both NULL.  x has 1 to 3 components, t none or components
+ *                           0 .. k <= those of x; x_rows / t_rows >= level + 1 are the limbs per poly of the blocks x / t live in (a block at a
+ *                           higher level is read as its AtLevel view); outputs are dense at level + 1.  An output may BE an input block whose
+ *                           rows equal level + 1; any other overlap of an output with an input or another output is refused. */
 enum rh_ckks_scalar_op { RH_CKKS_ADD_SCALAR = 0, RH_CKKS_SUB_SCALAR = 1, RH_CKKS_MUL_SCALAR = 2, RH_CKKS_MUL_SCALAR_THEN_ADD = 3 };
 int rh_ckks_tensor(rh_ring* r, int level, const uint64_t* a0_dev, const uint64_t* a1_dev, const uint64_t* b0_dev, const uint64_t* b1_dev,
                    uint64_t* c0_dev, uint64_t* c1_dev, uint64_t* c2_dev, int npoly, int accumulate, int square);
@@ -594,6 +604,9 @@ int rh_ckks_scale_then_add(rh_ring* r, int level, const uint64_t* a0_dev, const 
 int rh_ckks_linear_combination(rh_ring* r, int level, int nterms, const uint64_t* const* x_dev, const int* x_rows, const uint64_t* s0,
                                const uint64_t* s1, const uint64_t* c0, const uint64_t* c1, uint64_t* out0_dev, uint64_t* out1_dev,
                                uint64_t* out2_dev, int npoly, uint64_t* table_dev, size_t table_words);
+int rh_ckks_axpby(rh_ring* r, int level, const uint64_t* x0_dev, const uint64_t* x1_dev, const uint64_t* x2_dev, int x_rows,
+                  const uint64_t* t0_dev, const uint64_t* t1_dev, const uint64_t* t2_dev, int t_rows, uint64_t* out0_dev, uint64_t* out1_dev,
+                  uint64_t* out2_dev, int npoly, const uint64_t* ra, const uint64_t* rb, const uint64_t* s0, const uint64_t* s1);
 size_t rh_ckks_linear_combination_table_words(int nterms, int level);
 int rh_ckks_linear_combination_chunk(void);
 int rh_ckks_linear_combination_width(void);

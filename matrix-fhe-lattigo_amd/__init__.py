@@ -18,5 +18,8 @@ from . import lintrans  # noqa: F401,E402
 from . import dft  # noqa: F401,E402
 from . import mod1  # noqa: F401,E402
 from . import bootstrapping  # noqa: F401,E402
+from . import minimax  # noqa: F401,E402
+from . import comparison  # noqa: F401,E402
+from . import inverse  # noqa: F401,E402
 from . import multiparty  # noqa: F401,E402
 from . import matrix_ckks  # noqa: F401,E402

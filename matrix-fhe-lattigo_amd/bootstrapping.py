@@ -6,6 +6,7 @@ rlwe.Evaluator, dft.Evaluator, mod1.Evaluator) and, for ModUp's lift, one launch
   Evaluate :345-488 (the single-iteration arm)   checkMessageRatio :541-546   bootstrap :548-587   ScaleDown :596-643   ModUp :646-794
   CoeffsToSlots :797-799   EvalMod :802-809   EvalModAndScale :813-820   SlotsToCoeffs :822-824
   parameters.go: Parameters :18-35, GaloisElements :461-484, the depths :379-397      keys.go: EvaluationKeys :33-41
+  sk_bootstrapper.go: SecretKeyBootstrapper :11-69
 
 A batch of npoly ciphertexts is one Ciphertext; all of them share level and scale.  This package takes rings, not parameter literals, so
 Parameters is built from explicit pieces.  Where the reference works in place on its input (ScaleDown, ModUp), the device path writes new
@@ -19,7 +20,7 @@ import math
 from fractions import Fraction
 
 from . import dft, mod1, polynomial, rlwe
-from .ckks import Encoder, Evaluator as CkksEvaluator, Scale, _round
+from .ckks import Decryptor, DeviceValues, Encoder, Encryptor, Evaluator as CkksEvaluator, Scale, _round
 from .ringhip import ConjugateInvariant, RingHipError, Standard, _check, _p, _u64, lib
 from .schemes import Ciphertext
 
@@ -371,3 +372,55 @@ class Evaluator:
             h.Scale, h.LogDimensions = out.Scale, out.LogDimensions
             halves.append(h)
         return halves[0], halves[1]
+
+
+class SecretKeyBootstrapper:
+    """bootstrapping.SecretKeyBootstrapper (sk_bootstrapper.go:11-69): the Bootstrapper that decrypts and re-encrypts under the secret key --
+    decrypt, decode, encode at the top level and at default_scale, encrypt, in place on the ciphertext it returns; the stand-in the
+    reference's comparison and inverse tests run their circuits with.  encoder: a ckks.Encoder over ringQ.  The device encoder is the
+    float64 path, where the reference decodes to []*bignum.Complex at the parameters' precision: the refresh is meaningful up to 53 bits.
+    Counter records the number of bootstrappings; MinLevel is what MinimumInputLevel returns.  samples=: as Encryptor.Encrypt takes them."""
+
+    def __init__(self, ringQ, sk, encoder, default_scale, prng=None):
+        if ringQ.kind != Standard:
+            raise RingHipError("cannot NewSecretKeyBootstrapper: standard rings only (the encoder is standard-only)")
+        self.ringQ, self.sk, self.Encoder = ringQ, sk, encoder
+        self.DefaultScale = Scale(default_scale)
+        self.Decryptor = Decryptor(ringQ, sk)
+        self.Encryptor = Encryptor(ringQ, None, sk, prng)
+        self.Counter, self.MinLevel = 0, 0
+        self._values = {}
+
+    def MaxLevel(self):
+        return self.ringQ.L - 1
+
+    def Bootstrap(self, ct, samples=None):
+        """:32-46"""
+        logSlots = getattr(ct, "LogDimensions", None)
+        if logSlots is None:
+            raise RingHipError("cannot Bootstrap: a ciphertext carries no LogDimensions")
+        npoly = ct.Value[0].npoly
+        key = (npoly, 1 << logSlots)
+        values = self._values.get(key)
+        if values is None:
+            values = self._values[key] = DeviceValues(self.ringQ, npoly, 1 << logSlots)
+        self.Encoder.Decode(self.Decryptor.DecryptNew(ct), values)
+        pt = self.Encoder.NewPlaintext(self.MaxLevel(), self.DefaultScale, nvec=npoly, log_slots=logSlots, is_ntt=ct.IsNTT)
+        self.Encoder.Encode(values, pt)
+        rq = self.ringQ.AtLevel(self.MaxLevel())
+        ct.Value = [rq.NewPoly(npoly), rq.NewPoly(npoly)]                              # ct.Resize(1, MaxLevel)
+        self.Counter += 1
+        self.Encryptor.Encrypt(pt, ct, samples)
+        return ct
+
+    def BootstrapMany(self, cts):
+        return [self.Bootstrap(ct) for ct in cts]
+
+    def Depth(self):
+        return 0
+
+    def MinimumInputLevel(self):
+        return self.MinLevel
+
+    def OutputLevel(self):
+        return self.MaxLevel()

@@ -12,6 +12,8 @@
 //                               [0, N/2) and one for [N/2, N), on every component given.
 //   ckks_scale_then_add_kernel  the scale-matching Add / Sub of evaluateInPlace (:246-431): Mul(ct, ratioInt, tmp) of the operand with the smaller
 //                               scale, Add / Sub on the shared components, the rest copied (:422-430) and negated under Sub (:173-177).
+//   ckks_axpby_kernel           out_j = ra x_j - rb t_j - [j == 0] s: the Chebyshev step of the power basis (power_basis.go:148-176) and the
+//                               2 - x, 1 - x, 1 - z^2 of the inverse circuits; x and t are AtLevel views like the linear combination's terms.
 //   ckks_linear_combination_kernel  a baby step of the polynomial evaluator (circuits/common/polynomial/polynomial_evaluator.go:342-355): an Add of
 //                               a constant and K calls of MulThenAdd(X[k], c_k, res), out_j = [j == 0] const + sum_k MRed(X_k,j, MForm(s_k)), as ONE pass:
 //                               K + 1 rows of traffic per component where the sequence moves 3 K, the products summed in 128 bits and reduced once
@@ -148,6 +150,43 @@ ckks_scale_then_add_kernel(CkksComps p, unsigned n, const LimbConsts* __restrict
       if (!p.out[j]) continue;
       const bool ha = p.in[j] != nullptr, hb = p.in2[j] != nullptr;
       rh_st2(p.out[j] + o, make_ulonglong2(one(x[j].x, y[j].x, ha, hb), one(x[j].y, y[j].y, ha, hb)), nt);
+    }
+  }
+}
+
+// out_j = CRed(CRed(MRed(x_j, MForm(ra)) + q - MRed(t_j, MForm(rb))) + q - [j == 0] s): the step after a product of the Chebyshev power basis
+// (circuits/common/polynomial/power_basis.go:148-176: Add(X, X, X), then Add(X, -1, X) or the scale-matching Sub(X, T_c, X)) and, with
+// ra = q - 1, the 2 - x, 1 - x and 1 - z^2 of the inverse circuits (Mul by -1, Add of a constant).  k.a / k.b: ra / rb in Montgomery form;
+// s.a / s.b: the constant on coefficients [0, N/2) / [N/2, N).  x and t are AtLevel views of blocks with x_rows / t_rows limbs per poly; a
+// component whose t is null has no second term.  4 reads and 2 writes of a row where the composed calls move up to 8 and 6.
+struct CkksAxpby { const u64* x[3]; const u64* t[3]; u64* out[3]; };
+
+template <bool HAS_T, bool HAS_S>
+__global__ void __launch_bounds__(256)
+ckks_axpby_kernel(CkksAxpby p, int x_rows, int t_rows, unsigned n, const LimbConsts* __restrict__ consts, int L, RhScalars k, RhScalars s, int nt) {
+  const StreamRow row(consts, L, n);
+  const LimbConsts& c = row.c;
+  const u64 ka = k.a[row.limb], kb = k.b[row.limb], sa = s.a[row.limb], sb = s.b[row.limb];
+  const size_t xo = row.at(x_rows, n), to = row.at(t_rows, n);
+  const unsigned half = n >> 2;
+  RH_FOR_EACH_PAIR(i, 0, n >> 1) {
+    const u64 sc = i < half ? sa : sb;
+    ulonglong2 x[3], t[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      x[j] = p.x[j] ? rh_ld2(p.x[j] + xo + 2 * (size_t)i, nt) : make_ulonglong2(0, 0);
+      t[j] = HAS_T && p.t[j] ? rh_ld2(p.t[j] + to + 2 * (size_t)i, nt) : make_ulonglong2(0, 0);
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      if (!p.out[j]) continue;
+      ulonglong2 v = make_ulonglong2(mred(x[j].x, ka, c.q, c.qinv), mred(x[j].y, ka, c.q, c.qinv));
+      if (HAS_T && p.t[j]) {
+        v.x = cred(v.x + c.q - mred(t[j].x, kb, c.q, c.qinv), c.q);
+        v.y = cred(v.y + c.q - mred(t[j].y, kb, c.q, c.qinv), c.q);
+      }
+      if (HAS_S && j == 0) { v.x = cred(v.x + c.q - sc, c.q); v.y = cred(v.y + c.q - sc, c.q); }
+      rh_st2(p.out[j] + row.ro + 2 * (size_t)i, v, nt);
     }
   }
 }
@@ -344,6 +383,56 @@ extern "C" int rh_ckks_scale_then_add(rh_ring* r, int level, const uint64_t* a0,
   const CkksComps p{{a0, a1, a2}, {b0, b1, b2}, {out0, out1, out2}};
   ckks_scale_then_add_kernel<<<g.grid, 256, 0, rh_stream(r)>>>(p, n, r->d_consts, level + 1, s, ratio ? 1 : 0, sub ? 1 : 0, scaled_is_b ? 1 : 0, g.nt);
   return rh_launch_ok("ckks_scale_then_add_kernel");
+}
+
+extern "C" int rh_ckks_axpby(rh_ring* r, int level, const uint64_t* x0, const uint64_t* x1, const uint64_t* x2, int x_rows, const uint64_t* t0,
+                             const uint64_t* t1, const uint64_t* t2, int t_rows, uint64_t* out0, uint64_t* out1, uint64_t* out2, int npoly,
+                             const uint64_t* ra, const uint64_t* rb, const uint64_t* s0, const uint64_t* s1) {
+  const char* who = "rh_ckks_axpby";
+  if (int rc = rh_scheme_args(r, level, npoly, CKKS_RINGS, 4, who)) return rc;
+  if (int rc = rh_comps3(x0, x1, x2, out0, out1, out2, who)) return rc;
+  if (!ra || (s0 == nullptr) != (s1 == nullptr) || (t0 != nullptr) != (rb != nullptr)) return rh_fail(RH_ERR_ARG, "%s: null argument", who);
+  if ((!t0 && (t1 || t2)) || (t2 && !t1) || (t1 && !x1) || (t2 && !x2))
+    return rh_fail(RH_ERR_ARG, "%s: t has components 0 .. k only, and no more components than x", who);
+  const int L = level + 1;
+  if (x_rows < L) return rh_fail(RH_ERR_ARG, "%s: x holds %d limbs per poly, fewer than level %d needs", who, x_rows, level);
+  if (t0 && t_rows < L) return rh_fail(RH_ERR_ARG, "%s: t holds %d limbs per poly, fewer than level %d needs", who, t_rows, level);
+  // an output is the dense block at this level; it may BE an input block of that same shape (each thread reads its words of every input before
+  // it writes), and is otherwise apart from every input and from the other outputs
+  const size_t N = (size_t)r->N, dense = (size_t)npoly * L * N;
+  const u64* xs[3] = {x0, x1, x2};
+  const u64* ts[3] = {t0, t1, t2};
+  u64* outs[3] = {out0, out1, out2};
+  RhBlock written[3];
+  int nw = 0;
+  for (int j = 0; j < 3; ++j) {
+    if (!outs[j]) continue;
+    written[nw++] = {outs[j], dense};
+    for (int i = 0; i < 3; ++i) {
+      const RhBlock in[2] = {{xs[i], (size_t)npoly * (size_t)x_rows * N}, {ts[i], (size_t)npoly * (size_t)t_rows * N}};
+      const int rows[2] = {x_rows, t_rows};
+      for (int b = 0; b < 2; ++b) {
+        if (!in[b].p) continue;
+        if (((uintptr_t)in[b].p | (uintptr_t)outs[j]) & 15) return rh_fail(RH_ERR_ARG, "%s: every block must be 16-byte aligned", who);
+        if (!(in[b].p == outs[j] && rows[b] == L) && rh_overlap(written[nw - 1], in[b]))
+          return rh_fail(RH_ERR_ARG, "%s: an output overlaps an input without being that input at the same level", who);
+      }
+    }
+  }
+  if (int rc = rh_blocks_disjoint(written, nw, who, "two outputs overlap")) return rc;
+  RhScalars k, s;
+  if (int rc = rh_pack_scalars(r, level, ra, rb, true, &k, who, "factor")) return rc;        // Mul(ct, int, ct) -> MulDoubleRNSScalar: MForm(scalar)
+  if (int rc = rh_pack_scalars(r, level, s0, s1, false, &s, who, "constant")) return rc;     // Add of a scalar (:82-101): the residues as they are
+  const unsigned rows = (unsigned)npoly * (unsigned)L, n = (unsigned)r->N;
+  if (rows == 0) return RH_OK;
+  const RhStreamGrid g = rh_stream_begin(r, rows);
+  hipStream_t st = rh_stream(r);
+  const CkksAxpby p{{x0, x1, x2}, {t0, t1, t2}, {out0, out1, out2}};
+#define CKKS_AX(T, S) ckks_axpby_kernel<T, S><<<g.grid, 256, 0, st>>>(p, x_rows, t0 ? t_rows : L, n, r->d_consts, L, k, s, g.nt)
+  if (t0) { if (s0) CKKS_AX(true, true); else CKKS_AX(true, false); }
+  else { if (s0) CKKS_AX(false, true); else CKKS_AX(false, false); }
+#undef CKKS_AX
+  return rh_launch_ok("ckks_axpby_kernel");
 }
 
 // every output block is an input block or apart from it (element-wise kernels: a thread reads its words of every input before it writes), and

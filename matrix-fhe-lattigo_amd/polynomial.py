@@ -341,13 +341,53 @@ def _relinearize(ev, ct):
     ct.Value = ct.Value[:2]
 
 
-class PowerBasis:
-    """power_basis.go:17-182: Value[n] = X^n (T_n(X) in the Chebyshev basis), Value[1] a copy of the ciphertext given"""
+# The step after every product of a Chebyshev power basis as ONE launch of rh_ckks_axpby, or as the reference's own calls: the same bits.
+# profiles/minimax.json (tools/bench_minimax.py, "fused_power_basis_default"): a whole GenPower(31) at N = 2^16, 25 limbs is 1.17 and 1.13
+# times faster with the kernel at batches of 1 and 8 (medians; beyond the run-to-run spread at batch 1).
+FUSED_POWER_BASIS = {"chebyshev_step": True}
 
-    def __init__(self, ct, basis):
+
+def axpby(ringQ, level, x, t, out, ra, rb=None, s0=None, s1=None):
+    """rh_ckks_axpby on lists of DevicePoly: out_j = ra x_j - rb t_j - [j == 0] s on limbs 0 .. level.  x and t (None: no second term) may
+    sit at higher levels (they are read as their AtLevel views); out is dense at `level` and may be x where x is."""
+    npoly = x[0].npoly
+    if any(p.npoly != npoly for p in list(x) + list(t or []) + list(out)) or any(p.limbs != level + 1 for p in out):
+        raise RingHipError("cannot axpby: every block holds the same number of polys, and the outputs level + 1 = %d limbs" % (level + 1))
+    if len({p.limbs for p in x}) != 1 or (t and len({p.limbs for p in t}) != 1):
+        raise RingHipError("cannot axpby: the components of an operand sit at one level")
+    ptrs = lambda polys: [p.ptr for p in polys] + [None] * (3 - len(polys))
+    _check(lib().rh_ckks_axpby(ringQ._h, level, *ptrs(x), x[0].limbs, *ptrs(t or []), t[0].limbs if t else 0, *ptrs(out), npoly,
+                               _p(_u64(ra)), _p(_u64(rb)) if t else None, _p(_u64(s0)) if s0 is not None else None,
+                               _p(_u64(s1)) if s1 is not None else None))
+
+
+def affine_minus(ev, ct, constant, fused, out=None):
+    """constant - ct: the reference's Mul(ct, -1, out) and Add(out, constant, out), or with `fused` one launch of rh_ckks_axpby with
+    ra = q - 1 and s = -constant.  out: None (a new ciphertext) or ct itself."""
+    if out is None:
+        out = ev._new(ct.Degree(), ct)
+        _copy_meta(ct, out)
+    if not fused:
+        ev.Mul(ct, -1, out)
+        ev.Add(out, constant, out)
+        return out
+    level, scale = ev._operands("Add", ct, out), ev._scale(ct, "Add")
+    qs = ev._qs(level)
+    s0, s1 = ev._rns_scalar(level, scale, to_complex(constant, ev.encoding_precision))
+    axpby(ev.ringQ, level, ct.Value, None, out.Value, [q - 1 for q in qs], None, [(q - v) % q for v, q in zip(s0, qs)], [(q - v) % q for v, q in zip(s1, qs)])
+    out.Scale, out.IsNTT = scale, True
+    return out
+
+
+class PowerBasis:
+    """power_basis.go:17-182: Value[n] = X^n (T_n(X) in the Chebyshev basis), Value[1] a copy of the ciphertext given.
+    fused: None what FUSED_POWER_BASIS says, else True / False."""
+
+    def __init__(self, ct, basis, fused=None):
         if basis not in (Monomial, Chebyshev):
             raise RingHipError("invalid basis type, allowed types are `Monomial` or `Chebyshev` but is %r" % (basis,))
         self.Basis, self.Value = basis, {1: _copy_new(ct)}
+        self.fused = None if fused is None else bool(fused)
 
     def GenPower(self, n, lazy, ev):
         """:57-78.  lazy: X^n is left at degree 2; the powers it is made of are relinearised on the way.  ev: a ckks.Evaluator"""
@@ -379,7 +419,7 @@ class PowerBasis:
         xb = xa if b == a else _at_level(ev, X[b], level)
         X[n] = ev.MulNew(xa, xb) if lazy else ev.MulRelinNew(xa, xb)              # (:125 / :143)
         _copy_meta(X[1], X[n])
-        if self.Basis == Chebyshev:                                                # T_n = 2 T_a T_b - T_|a - b| (:148-176)
+        if self.Basis == Chebyshev and not self._chebyshev_step(n, abs(a - b), lazy, ev):      # T_n = 2 T_a T_b - T_|a - b| (:148-176)
             c = abs(a - b)
             ev.Add(X[n], X[n], X[n])
             if c == 0:
@@ -395,6 +435,43 @@ class PowerBasis:
                     X[n].Value, X[n].Scale = grown.Value, grown.Scale
                 else:
                     ev.Sub(X[n], xc, X[n])
+        return True
+
+    def _chebyshev_step(self, n, c, lazy, ev):
+        """Add(X, X, X), then Add(X, -1, X) or GenPower(c) and the scale-matching Sub(X, T_c, X) (:157-176), as ONE launch of rh_ckks_axpby:
+        every step of that sequence ends in CRed or MRed of exact values, so the canonical residue of 2 k0 X - k1 T_c - s is its bits (k0 or
+        k1 the integer ratio of the scales as evaluateInPlace multiplies it in, the other 1).  False: the composed calls are to run -- the
+        switch is off, or T_c has more components than X (the reference's Sub then negates with ring.Neg, which writes q for 0)."""
+        if not (FUSED_POWER_BASIS["chebyshev_step"] if self.fused is None else self.fused):
+            return False
+        X = self.Value
+        xn, prec = X[n], ev.encoding_precision
+        scale = ev._scale(xn, "Add")
+        if c == 0:
+            level = ev._operands("Add", xn)
+            qs = ev._qs(level)
+            s0, s1 = ev._rns_scalar(level, scale, to_complex(-1, prec))              # what Add(X, -1, X) adds: its negative is subtracted
+            axpby(ev.ringQ, level, xn.Value, None, xn.Value, [2] * len(qs), None, [(q - v) % q for v, q in zip(s0, qs)], [(q - v) % q for v, q in zip(s1, qs)])
+            return True
+        self.GenPower(c, lazy, ev)
+        xc = X[c]
+        if xc.Degree() > xn.Degree():
+            return False
+        ev._operands("Sub", xn)
+        ev._operands("Sub", xc)
+        level = min(xn.Level(), xc.Level())
+        qs = ev._qs(level)
+        scalec = ev._scale(xc, "Sub")
+        cmp = scale.Cmp(scalec)
+        k = [1] * len(qs)
+        if cmp:                                                                    # Mul(ct, ratioInt, tmp) (evaluator.go:282 ...)
+            ratioInt = int((scale.Div(scalec) if cmp == 1 else scalec.Div(scale)).Value)
+            k = ev._rns_scalar(level, Scale(1), to_complex(ratioInt, prec))[0]
+        ra = [2 * v % q for v, q in zip(k, qs)] if cmp == -1 else [2] * len(qs)
+        rb = list(k) if cmp == 1 else [1] * len(qs)
+        out = xn.Value if xn.Level() == level else [ev.ringQ.AtLevel(level).NewPoly(p.npoly) for p in xn.Value]
+        axpby(ev.ringQ, level, xn.Value, xc.Value, out, ra, rb)
+        xn.Value, xn.Scale = out, scale.Max(scalec)
         return True
 
 

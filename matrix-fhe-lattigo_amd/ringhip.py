@@ -158,6 +158,7 @@ def lib():
         "rh_ckks_tensor": (i, [vp, i] + [vp] * 7 + [i, i, i]), "rh_ckks_mul_plain": (i, [vp, i] + [vp] * 7 + [i, i]),
         "rh_ckks_scalar": (i, [vp, i, i] + [vp] * 6 + [i, U64P, U64P]), "rh_ckks_scale_then_add": (i, [vp, i] + [vp] * 9 + [i, U64P, i, i]),
         "rh_ckks_linear_combination": (i, [vp, i, i, C.POINTER(vp), C.POINTER(i), U64P, U64P, U64P, U64P, vp, vp, vp, i, vp, sz]),
+        "rh_ckks_axpby": (i, [vp, i] + [vp] * 3 + [i] + [vp] * 3 + [i] + [vp] * 3 + [i, U64P, U64P, U64P, U64P]),
         "rh_ckks_linear_combination_table_words": (sz, [i, i]), "rh_ckks_linear_combination_chunk": (i, []), "rh_ckks_linear_combination_width": (i, []),
         "rh_ckks_split_real_imag": (i, [vp, i] + [C.POINTER(vp)] * 4 + [i, U64P, U64P]), "rh_ckks_merge_real_imag": (i, [vp, i] + [C.POINTER(vp)] * 3 + [i, U64P, U64P]),
         "rh_ckks_dft_level_vectors": (i, [vp, i, i, C.c_uint, i, i, vp, sz, vp, sz, vp]),
