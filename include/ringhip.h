@@ -446,6 +446,39 @@ int rh_blindrot_core(rh_ring* r, int pw2, int digits, const uint64_t* rgsw_dev, 
                      const uint64_t* galois_elements, int ngalois, const int32_t* prog_offsets_dev, const int32_t* prog_ops_dev, int nops,
                      uint64_t* c0_dev, uint64_t* c1_dev, int nacc);
 
+/* ---- the front end of blindrot.Evaluator.Evaluate (evaluator.go:46-132) on the device: from the sample ciphertexts to the programs and the X^b
+ * rows that rh_blindrot_core and the calls around it read.  No coefficient and no program crosses to the host.  Standard rings (RH_ERR_UNSUPPORTED
+ * otherwise), blind rotation ring of degree N = 2^6 .. 2^11; every count and pointer is checked on the host, every index read from device
+ * memory is range-checked in the kernel.  Asynchronous on the stream of the ring each entry takes; no state is kept in a handle.
+ *   rh_blindrot_mod_switch     modSwitchRLWETo2NLvl (:284-307) at level 0 of the LWE ring for ncts sample ciphertexts: x_dev [ct][component < 2][N_LWE],
+ *                              coefficient domain, modulus 0 (below 2^63; the inverse transform before it is rh_ring_intt) ->
+ *                              a2n_dev int32 [ct][component][N_LWE] = round(x 2N / q) mod 2N, half rounding up, 2N = 2^(logN_br + 1).  The quotient
+ *                              is taken exactly, as logN_br + 1 steps of a binary long division in 64-bit integers (never floating point); an even
+ *                              non-zero value of component 1 is made odd with ^ 1 (:301-303).  With njobs > 0 it also gathers b (:95):
+ *                              b_dev[j] = a2n[ct_j][0][index_j] for the jobs (ct, index) of jobs_dev (int32 pairs).
+ *   rh_blindrot_program_stride ops per job that rh_blindrot_program reserves: N_LWE external products, at most min(N_LWE, N - 1) + (N - 2) / 10 + 2
+ *                              automorphisms, one spare
+ *   rh_blindrot_program        one workgroup per job: the job's vector a (:62-103: the reversal a_0, -a_{n-1}, .., -a_1 of component 1, then
+ *                              mulBySmallMonomialMod2N up to X^index) read through its index map, getDiscreteLogSets (:258-280) with indices in
+ *                              ascending order inside a set, and the steps of BlindRotateCore (:134-186) / evaluateFromDiscreteLogSets (:189-229):
+ *                              the counter carried from the first half-loop into the second, the dropped look-up of set 2N, k == 1 in the second
+ *                              half only.  dlog_pos_dev: 2N int32, the step of the walk at which the set of each value of Z_2N is visited
+ *                              (getGaloisElementInverseMap :231-255, 0 and 2N - 1 in set 0), negative for an even non-zero value; slots: HOST
+ *                              array of 11 key slots, of GaloisGen^1 .. GaloisGen^10 and of 2N - GaloisGen, in rh_blindrot_core's galois table.
+ *                              Layout: a FIXED STRIDE per job, stride >= rh_blindrot_program_stride: offsets_dev[j] = j * stride (njobs + 1 int32),
+ *                              job j's ops from ops_dev[j * stride], the tail filled with 0x7fffffff, an external product with a key that no table
+ *                              holds, which rh_blindrot_core skips.  *flag_dev |= 1: an even non-zero a (the reference panics), |= 2: a program
+ *                              longer than stride, |= 4: a dlog_pos entry outside the walk; the caller zeroes it.
+ *   rh_blindrot_monomials      MForm(X^b) (:108, ring.NewMonomialXi) for every job: out_dev (njobs, level + 1, N), zero but for +-2^64 mod q_u at
+ *                              b mod N, minus for b mod 2N >= N.  The transform, the product with the test polynomial and the first
+ *                              automorphism (:109-112) stay rh_ring_ntt, the vec ops and rh_ring_automorphism_ntt. */
+int rh_blindrot_mod_switch(rh_ring* rlwe, int logN_br, const uint64_t* x_dev, int ncts, int32_t* a2n_dev, const int32_t* jobs_dev, int njobs,
+                           int32_t* b_dev);
+int rh_blindrot_program_stride(int n_br, int n_lwe);
+int rh_blindrot_program(rh_ring* rbr, int n_lwe, const int32_t* a2n_dev, int ncts, const int32_t* jobs_dev, int njobs, const int32_t* dlog_pos_dev,
+                        const int32_t* slots, int stride, int32_t* offsets_dev, int32_t* ops_dev, int32_t* flag_dev);
+int rh_blindrot_monomials(rh_ring* rbr, int level, const int32_t* b_dev, int njobs, uint64_t* out_dev);
+
 /* ---- ring packing (core/rlwe/ring_packing.go).  Standard rings (RH_ERR_UNSUPPORTED otherwise), dense blocks of level+1 limbs per poly, canonical
  * residues in and out, both components of a batch of ciphertexts in one launch; the NTT-domain index map of the Galois element (any odd number,
  * taken modulo 2N) is computed in the kernel.  Every block is 16-byte aligned and no written block may overlap a read one (RH_ERR_ARG).
@@ -836,6 +869,18 @@ size_t rh_rlwe_gadget_encrypt_table_words(int levelQ, int rows);
 int rh_rlwe_gadget_encrypt(rh_ring* ringQ, rh_ring* ringP, int levelQ, int levelP, const uint64_t* eQ, const uint64_t* eP, uint64_t* tabQ, uint64_t* tabP,
                            const uint64_t* skOutQ, const uint64_t* skOutP, const uint64_t* skInQ, int nkeys, int skin_keys, const uint64_t* rowtab, int rows,
                            uint64_t* table_dev, size_t table_words);
+/* Every row of many RGSW ciphertexts under one secret key in one launch (rgsw.Encryptor.EncryptZero and Encrypt, core/rgsw/encryptor.go:25-118: per
+ * row the encryption of zero of core/rlwe/encryptor.go:449-452, then AddPolyTimesGadgetVectorToGadgetCiphertext, core/rlwe/gadgetciphertext.go:172-241,
+ * on component 0 of Value[0] and component 1 of Value[1]):
+ *   tab[r][0] = MForm(e_r) - tab[r][1] * sk          with tab[r][1] as sampled, then on the Q limbs where s_r != 0
+ *   half_r == 0: tab[r][0] += pt[p_r] * s_r;          half_r == 1: tab[r][1] += pt[p_r] * s_r
+ * eQ / eP, tabQ / tabP: as rh_rlwe_gadget_encrypt's; skQ / skP: (limbs, N), one secret; ptQ: (npt, levelQ + 1, N) plaintexts, NTT domain, Montgomery
+ * form, named by the rows (the keys of a blind rotation set share three: X^-1, X^0, X^1).  rowtab (HOST): rows x (levelQ + 3) words: p_r, half_r,
+ * then s_r per limb of Q; table_dev: device scratch of rh_rgsw_encrypt_table_words(levelQ, rows) words.  ringP NULL: no P. */
+size_t rh_rgsw_encrypt_table_words(int levelQ, int rows);
+int rh_rgsw_encrypt(rh_ring* ringQ, rh_ring* ringP, int levelQ, int levelP, const uint64_t* eQ, const uint64_t* eP, uint64_t* tabQ, uint64_t* tabP,
+                    const uint64_t* skQ, const uint64_t* skP, const uint64_t* ptQ, int npt, const uint64_t* rowtab, int rows, uint64_t* table_dev,
+                    size_t table_words);
 /* encryptZeroSkFromC1 with addPtToCt folded in (core/rlwe/encryptor.go:398-424, :512-530), NTT domain: c0 = -c1 sk + e [+ pt], canonical.
  * sk: (level + 1, N), NTT domain, Montgomery form; e: the NTT of the lifted error; pt: NULL or an NTT-domain plaintext batch.  e NULL: only
  * -c1 sk (a coefficient-domain ciphertext adds its error and plaintext after the inverse transform, :415-420). */

@@ -1,6 +1,8 @@
 // blindrot.hip -- rh_blindrot_core: the accumulator loops of a batch of blind rotations (core/rgsw/blindrot/evaluator.go:134-229) in one launch,
 // one workgroup per accumulator (blindrot_kernels.hip.hpp).  The host derives each accumulator's program from its discrete-log sets
 // (getDiscreteLogSets :258-280, evaluateFromDiscreteLogSets :189-229) and uploads it; the key tables are uploaded once per key set.
+// rh_blindrot_mod_switch, rh_blindrot_program and rh_blindrot_monomials are the front end of Evaluate (:46-132) on the device: the programs are
+// then derived there, in the same encoding, and neither a coefficient nor a program crosses to the host.
 #include <hip/hip_runtime.h>
 #include "engine_internal.hpp"
 #include "blindrot_kernels.hip.hpp"
@@ -45,4 +47,88 @@ extern "C" int rh_blindrot_core(rh_ring* r, int pw2, int digits, const uint64_t*
     default:                br_launch<8, false>(r, nacc, c0, c1, rgsw, nkeys, galois, ge, ngalois, prog_offsets, prog_ops, nops, pw2, digits); break;
   }
   return rh_launch_ok("blindrot_core_kernel");
+}
+
+// ---- the front end of Evaluate (evaluator.go:46-132) on the device: no coefficient and no program crosses to the host ---------------------------
+static int br_front_ring(const rh_ring* r, const char* who) {
+  if (!r) return rh_fail(RH_ERR_ARG, "%s: null ring handle", who);
+  if (r->kind != RH_RING_STANDARD) return rh_fail(RH_ERR_UNSUPPORTED, "%s: standard rings only (3N and conjugate-invariant rings are not supported)", who);
+  return RH_OK;
+}
+static int br_front_logn(int logN, const char* who) {
+  if (logN < BR_MIN_LOGN || logN > BR_MAX_LOGN)
+    return rh_fail(RH_ERR_UNSUPPORTED, "%s: blind rotation ring degree 2^%d outside 2^%d .. 2^%d", who, logN, BR_MIN_LOGN, BR_MAX_LOGN);
+  return RH_OK;
+}
+
+extern "C" int rh_blindrot_mod_switch(rh_ring* rlwe, int logN_br, const uint64_t* x, int ncts, int32_t* a2n, const int32_t* jobs, int njobs, int32_t* b) {
+  const char* who = "rh_blindrot_mod_switch";
+  if (int rc = br_front_ring(rlwe, who)) return rc;
+  if (int rc = br_front_logn(logN_br, who)) return rc;
+  if (rlwe->moduli[0] >> 63) return rh_fail(RH_ERR_ARG, "%s: modulus 0 is not below 2^63", who);
+  if (ncts < 0 || njobs < 0) return rh_fail(RH_ERR_ARG, "%s: negative count", who);
+  if ((ncts && (!x || !a2n)) || (njobs && (!jobs || !b || !a2n))) return rh_fail(RH_ERR_ARG, "%s: null argument", who);
+  if ((size_t)ncts * 2 * rlwe->N >> 31) return rh_fail(RH_ERR_ARG, "%s: too many sample ciphertexts", who);
+  (void)hipSetDevice(rlwe->device);
+  (void)hipGetLastError();
+  if (ncts) {
+    const size_t total = (size_t)ncts * 2 * rlwe->N;
+    blindrot_mod_switch_kernel<<<dim3((unsigned)((total + BRP_THREADS - 1) / BRP_THREADS)), BRP_THREADS, 0, rh_stream(rlwe)>>>(
+        x, a2n, total, (u32)rlwe->N, rlwe->moduli[0], logN_br + 1);
+    if (int rc = rh_launch_ok("blindrot_mod_switch_kernel")) return rc;
+  }
+  if (njobs) {
+    blindrot_gather_b_kernel<<<dim3((unsigned)((njobs + BRP_THREADS - 1) / BRP_THREADS)), BRP_THREADS, 0, rh_stream(rlwe)>>>(a2n, ncts, rlwe->N, jobs, njobs, b);
+    return rh_launch_ok("blindrot_gather_b_kernel");
+  }
+  return RH_OK;
+}
+
+// EXT ops: n_lwe.  AUTO ops: one before each non-empty set but the first of a run (at most min(n_lwe, N - 1)), one per full window ((N - 2) / 10 at
+// most), the one of k == 1 and Automorphism(2N - g).
+extern "C" int rh_blindrot_program_stride(int n_br, int n_lwe) {
+  if (n_br < 2 || n_lwe < 0) return 0;
+  return n_lwe + (n_lwe < n_br - 1 ? n_lwe : n_br - 1) + (n_br - 2) / BR_WINDOW + 3;
+}
+
+extern "C" int rh_blindrot_program(rh_ring* rbr, int n_lwe, const int32_t* a2n, int ncts, const int32_t* jobs, int njobs, const int32_t* dlog_pos,
+                                   const int32_t* slots, int stride, int32_t* offsets, int32_t* ops, int32_t* flag) {
+  const char* who = "rh_blindrot_program";
+  if (int rc = br_front_ring(rbr, who)) return rc;
+  if (int rc = br_front_logn(rbr->logN, who)) return rc;
+  if (n_lwe < 1 || n_lwe > BRP_MAX_NLWE) return rh_fail(RH_ERR_UNSUPPORTED, "%s: LWE degree %d outside 1 .. %d, what one workgroup holds", who, n_lwe, BRP_MAX_NLWE);
+  if (ncts < 0 || njobs < 0) return rh_fail(RH_ERR_ARG, "%s: negative count", who);
+  if (stride < rh_blindrot_program_stride(rbr->N, n_lwe))
+    return rh_fail(RH_ERR_ARG, "%s: stride %d below rh_blindrot_program_stride = %d", who, stride, rh_blindrot_program_stride(rbr->N, n_lwe));
+  if (((size_t)njobs + 1) * (size_t)stride >> 31) return rh_fail(RH_ERR_ARG, "%s: %d jobs of stride %d do not fit int32 offsets", who, njobs, stride);
+  if (!slots || !offsets || !flag || (njobs && (!a2n || !jobs || !dlog_pos || !ops))) return rh_fail(RH_ERR_ARG, "%s: null argument", who);
+  BrSlots sl{};
+  for (int v = 0; v <= BR_WINDOW; ++v) {
+    if (slots[v] < 0 || slots[v] >= BR_MAX_GALOIS) return rh_fail(RH_ERR_ARG, "%s: key slot %d of Galois element %d outside 0 .. %d", who, slots[v], v, BR_MAX_GALOIS - 1);
+    if (v < BR_WINDOW) sl.pw[v + 1] = -(slots[v] + 1); else sl.mid = -(slots[v] + 1);
+  }
+  (void)hipSetDevice(rbr->device);
+  (void)hipGetLastError();
+  if (!njobs) {
+    if (hipMemsetAsync(offsets, 0, sizeof(int32_t), rh_stream(rbr)) != hipSuccess) return rh_fail(RH_ERR_DEVICE, "%s: hipMemsetAsync failed", who);
+    return RH_OK;
+  }
+  blindrot_program_kernel<<<dim3((unsigned)njobs), BRP_THREADS, 0, rh_stream(rbr)>>>(a2n, ncts, n_lwe, jobs, dlog_pos, sl, rbr->logN, stride, offsets, ops, flag);
+  return rh_launch_ok("blindrot_program_kernel");
+}
+
+extern "C" int rh_blindrot_monomials(rh_ring* rbr, int level, const int32_t* b, int njobs, uint64_t* out) {
+  const char* who = "rh_blindrot_monomials";
+  if (int rc = br_front_ring(rbr, who)) return rc;
+  if (level < 0 || level >= rbr->L) return rh_fail(RH_ERR_ARG, "%s: level %d out of range", who, level);
+  if (njobs < 0) return rh_fail(RH_ERR_ARG, "%s: negative count", who);
+  if (njobs && (!b || !out)) return rh_fail(RH_ERR_ARG, "%s: null argument", who);
+  if (!njobs) return RH_OK;
+  (void)hipSetDevice(rbr->device);
+  (void)hipGetLastError();
+  const size_t total = (size_t)njobs * (level + 1) * rbr->N;
+  if ((total + BRP_THREADS - 1) / BRP_THREADS >> 31) return rh_fail(RH_ERR_ARG, "%s: too many jobs", who);
+  blindrot_monomials_kernel<<<dim3((unsigned)((total + BRP_THREADS - 1) / BRP_THREADS)), BRP_THREADS, 0, rh_stream(rbr)>>>(b, out, total, level + 1, rbr->logN,
+                                                                                                                       rbr->d_consts);
+  return rh_launch_ok("blindrot_monomials_kernel");
 }

@@ -209,3 +209,173 @@ blindrot_core_kernel(u64* c0, u64* c1, const u64* __restrict__ rgsw, int nkeys, 
     if (j < N) { c0[base + j] = a0[k]; c1[base + j] = a1[k]; }
   }
 }
+
+// ---- the front end of Evaluate (core/rgsw/blindrot/evaluator.go:46-132): mod switch, per-job program, X^b rows ---------------------------------
+#define BRP_THREADS 256
+#define BRP_MAX_NLWE 2048                           // what the program kernel keeps in LDS: a set index per LWE coefficient
+#define BR_OP_SKIP 0x7fffffff                       // an external product with a key no table holds: blindrot_core_kernel skips it
+#define BR_WINDOW 10                                // windowSize (keys.go:12-15)
+struct BrSlots { int pw[BR_WINDOW + 1]; int mid; }; // ops of Automorphism by GaloisGen^v, 1 <= v <= windowSize (pw[0] unused), and by 2N - GaloisGen
+
+// modSwitchRLWETo2NLvl (:284-307) at level 0: round(x 2^s / q) mod 2^s, half rounding up, as s steps of a binary long division -- the remainder
+// stays below q < 2^63, so every step is exact in 64 bits.  x: [ct][component < 2][n]; component 1 is made odd (an even non-zero result ^ 1).
+__global__ void __launch_bounds__(BRP_THREADS)
+blindrot_mod_switch_kernel(const u64* __restrict__ x, int* __restrict__ out, size_t total, u32 n, u64 q, int s) {
+  const size_t i = (size_t)blockIdx.x * BRP_THREADS + threadIdx.x;
+  if (i >= total) return;
+  u64 r = x[i];
+  if (r >= q) r %= q;
+  u32 y = 0;
+  for (int k = 0; k < s; ++k) {
+    r <<= 1;
+    const u32 bit = r >= q;
+    if (bit) r -= q;
+    y = (y << 1) | bit;
+  }
+  if (2 * r >= q) ++y;
+  y &= (1u << s) - 1;
+  if (((i / n) & 1) && y != 0 && (y & 1) == 0) y ^= 1;
+  out[i] = (int)y;
+}
+
+// b of every job: b[j] = a2n[ct_j][0][index_j]; a job outside the samples reads as 0
+__global__ void __launch_bounds__(BRP_THREADS)
+blindrot_gather_b_kernel(const int* __restrict__ a2n, int ncts, int n, const int* __restrict__ jobs, int njobs, int* __restrict__ b) {
+  const int j = blockIdx.x * BRP_THREADS + threadIdx.x;
+  if (j >= njobs) return;
+  const int ct = jobs[2 * j], index = jobs[2 * j + 1];
+  b[j] = (ct >= 0 && ct < ncts && index >= 0 && index < n) ? a2n[(size_t)ct * 2 * n + index] : 0;
+}
+
+// inclusive scan of one value per thread over the workgroup; returns with s[] holding the inclusive values and a barrier passed
+template <bool MAX>
+RH_DEV int brp_scan(int* s, int v) {
+  s[threadIdx.x] = v;
+  __syncthreads();
+  for (int d = 1; d < BRP_THREADS; d <<= 1) {
+    const int t = (int)threadIdx.x >= d ? s[threadIdx.x - d] : (MAX ? -1 : 0);
+    __syncthreads();
+    v = MAX ? (v > t ? v : t) : v + t;
+    s[threadIdx.x] = v;
+    __syncthreads();
+  }
+  return v;
+}
+
+// The ops that step t of the walk issues around its external products.  The walk of BlindRotateCore visits the discrete-log sets in the order
+//   t = 0 .. h - 2: k = -(h - 1) .. -1;   t = h - 1 .. 2 h - 3: k = h - 1 .. 1;   t = 2 h - 2: k = 0        (h = N / 2, T = N - 1 steps)
+// with Automorphism(2N - g) before step h - 1 (the look-up of set 2N before it finds nothing and its counter is dropped).  The counter v of
+// evaluateFromDiscreteLogSets before step t is (t - p) mod windowSize, p the last step before t with a non-empty set (0 when there is none): a
+// non-empty set leaves v = 1, an empty one adds 1, and v = windowSize resets.  k == 1 (step T - 2) always resets, and the last step is called
+// with v = 0 and never reaches the window.
+struct BrpStep { int pre, post; };                  // the window exponent of the automorphism before / after the external products, 0: none
+RH_DEV BrpStep brp_step(int t, int p, int c, int T) {
+  BrpStep s{0, 0};
+  if (t == T - 1) return s;
+  const int vb = (t - (p > 0 ? p : 0)) % BR_WINDOW;
+  const bool k1 = t == T - 2;
+  if (c > 0) { s.pre = vb; s.post = k1 ? 1 : 0; }
+  else { const int v = vb + 1; s.post = (v == BR_WINDOW || k1) ? v : 0; }
+  return s;
+}
+
+// One workgroup per job (ct, index): the job's vector a (evaluator.go:62-103: the reversal a_0, -a_{n-1}, .., -a_1 of the switched c1, times
+// X^index modulo X^n + 1 and 2N) is read through its index map, never stored; its discrete-log sets (getDiscreteLogSets :258-280) are a histogram
+// over the walk positions; and the steps of BlindRotateCore (:134-186, evaluateFromDiscreteLogSets :189-229) are written in blindrot_core_kernel's
+// encoding into ops[job * stride ..), the tail filled with BR_OP_SKIP; off[job] = job * stride.
+//   pos: 2N int32, the walk position of the set of each value of Z_2N (0 and 2N - 1 read as set 0, like 1); negative: an even non-zero value,
+//        which raises *flag |= 1 and is filed under set 0.  *flag |= 2: a program longer than stride (the entry point sizes stride so that none is).
+__global__ void __launch_bounds__(BRP_THREADS)
+blindrot_program_kernel(const int* __restrict__ a2n, int ncts, int n, const int* __restrict__ jobs, const int* __restrict__ pos, BrSlots sl,
+                        int logN, int stride, int* __restrict__ off, int* __restrict__ ops, int* flag) {
+  __shared__ unsigned short tpos[BRP_MAX_NLWE];
+  __shared__ int cnt[1 << BR_MAX_LOGN], cur[1 << BR_MAX_LOGN], sc[BRP_THREADS];
+  const int job = blockIdx.x, tid = threadIdx.x;
+  const int N = 1 << logN, h = N >> 1, T = N - 1, mask = 2 * N - 1;
+  int* my = ops + (size_t)job * stride;
+  if (tid == 0) {
+    off[job + 1] = (job + 1) * stride;
+    if (job == 0) off[0] = 0;
+  }
+  const int ct = jobs[2 * job], index = jobs[2 * job + 1];
+  if (ct < 0 || ct >= ncts || index < 0 || index >= n) {              // uniform in the workgroup: an empty program
+    for (int j = tid; j < stride; j += BRP_THREADS) my[j] = BR_OP_SKIP;
+    return;
+  }
+  const int* a = a2n + ((size_t)ct * 2 + 1) * n;
+  for (int t = tid; t < T; t += BRP_THREADS) cnt[t] = 0;
+  __syncthreads();
+  for (int i = tid; i < n; i += BRP_THREADS) {
+    int j = i - index;
+    const bool neg = j < 0;
+    if (neg) j += n;
+    int v = j == 0 ? a[0] : -a[n - j];
+    if (neg) v = -v;
+    int p = pos[v & mask];
+    if ((unsigned)p >= (unsigned)T) { atomicOr(flag, p < 0 ? 1 : 4); p = T - 1; }
+    tpos[i] = (unsigned short)p;
+    atomicAdd(&cnt[p], 1);
+  }
+  __syncthreads();
+  const int S = (T + BRP_THREADS - 1) / BRP_THREADS, t0 = tid * S, t1 = t0 + S < T ? t0 + S : T;
+  int last = -1;
+  for (int t = t0; t < t1; ++t) if (cnt[t]) last = t;
+  brp_scan<true>(sc, last);
+  const int carry = tid ? sc[tid - 1] : -1;
+  __syncthreads();
+  int len = 0, p = carry;
+  for (int t = t0; t < t1; ++t) {
+    const int c = cnt[t];
+    const BrpStep s = brp_step(t, p, c, T);
+    len += (t == h - 1) + (s.pre != 0) + c + (s.post != 0);
+    if (c) p = t;
+  }
+  int at = brp_scan<false>(sc, len) - len;
+  const int count = sc[BRP_THREADS - 1];
+  p = carry;
+  for (int t = t0; t < t1; ++t) {
+    const int c = cnt[t];
+    const BrpStep s = brp_step(t, p, c, T);
+    if (t == h - 1) { if (at < stride) my[at] = sl.mid; ++at; }
+    if (s.pre) { if (at < stride) my[at] = sl.pw[s.pre]; ++at; }
+    cur[t] = at;
+    at += c;
+    if (s.post) { if (at < stride) my[at] = sl.pw[s.post]; ++at; }
+    if (c) p = t;
+  }
+  if (count > stride && tid == 0) atomicOr(flag, 2);
+  for (int j = count + tid; j < stride; j += BRP_THREADS) my[j] = BR_OP_SKIP;
+  __syncthreads();
+  // the external products of a set in ascending index order: chunks of 256 indices in order, ranked inside a chunk by counting
+  for (int c0 = 0; c0 < n; c0 += BRP_THREADS) {
+    const int i = c0 + tid;
+    const bool have = i < n;
+    const int q = have ? tpos[i] : 0;
+    if (have) {
+      int r = 0;
+      for (int i2 = c0; i2 < i; ++i2) r += tpos[i2] == q;
+      const int dst = cur[q] + r;
+      if (dst < stride) my[dst] = i;
+    }
+    __syncthreads();
+    if (have) atomicAdd(&cur[q], 1);
+    __syncthreads();
+  }
+}
+
+// MForm(X^b) per job and limb (evaluator.go:108, ring.NewMonomialXi): out[job][u][b mod N] = +-2^64 mod q_u, minus for b >= N, zero elsewhere
+__global__ void __launch_bounds__(BRP_THREADS)
+blindrot_monomials_kernel(const int* __restrict__ b, u64* __restrict__ out, size_t total, int L, int logN, const LimbConsts* __restrict__ consts) {
+  const size_t i = (size_t)blockIdx.x * BRP_THREADS + threadIdx.x;
+  if (i >= total) return;
+  const u32 N = 1u << logN, j = (u32)(i & (N - 1));
+  const size_t row = i >> logN;
+  const u32 bv = (u32)b[row / (size_t)L] & (2 * N - 1);
+  u64 w = 0;
+  if (j == (bv & (N - 1))) {
+    const LimbConsts c = consts[row % (size_t)L];
+    const u64 r = c.nq % c.q;
+    w = bv < N ? r : c.q - r;
+  }
+  out[i] = w;
+}

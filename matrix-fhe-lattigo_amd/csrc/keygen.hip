@@ -156,6 +156,49 @@ extern "C" int rh_rlwe_gadget_encrypt(rh_ring* rQ, rh_ring* rP, int levelQ, int 
   return rh_launch_ok("rlwe_gadget_encrypt_kernel");
 }
 
+extern "C" size_t rh_rgsw_encrypt_table_words(int levelQ, int rows) { return (size_t)(rows > 0 ? rows : 0) * (size_t)(levelQ + 3); }
+
+extern "C" int rh_rgsw_encrypt(rh_ring* rQ, rh_ring* rP, int levelQ, int levelP, const uint64_t* eQ, const uint64_t* eP, uint64_t* tabQ, uint64_t* tabP,
+                               const uint64_t* skQ, const uint64_t* skP, const uint64_t* ptQ, int npt, const uint64_t* rowtab, int rows,
+                               uint64_t* table_dev, size_t table_words) {
+  const char* who = "rh_rgsw_encrypt";
+  if (int rc = qp_pair_ok(rQ, rP, levelQ, levelP, rows, who)) return rc;
+  const int LQ = levelQ + 1, LP = rP ? levelP + 1 : 0;
+  if (!eQ || !tabQ || !skQ || !rowtab || !table_dev) return rh_fail(RH_ERR_ARG, "%s: null argument", who);
+  if ((rP != nullptr) != (eP && tabP && skP) || (!rP && (eP || tabP || skP)))
+    return rh_fail(RH_ERR_ARG, "%s: eP, tabP and skP go with ringP, all or none", who);
+  if (npt < 0 || (npt && !ptQ)) return rh_fail(RH_ERR_ARG, "%s: npt < 0, or plaintexts without their block", who);
+  const size_t words = rh_rgsw_encrypt_table_words(levelQ, rows);
+  if (table_words < words) return rh_fail(RH_ERR_ARG, "%s: the row table needs %zu words, the caller's has %zu", who, words, table_words);
+  if ((size_t)rows * (size_t)(LQ + LP) > 0x7fffffffu) return rh_fail(RH_ERR_ARG, "%s: too many rows for one launch", who);
+  for (int r = 0; r < rows; ++r) {
+    const u64* t = rowtab + (size_t)r * (size_t)(2 + LQ);
+    bool any = false;
+    for (int l = 0; l < LQ; ++l) {
+      if (t[2 + l] >= rQ->moduli[l]) return rh_fail(RH_ERR_ARG, "%s: the scalar of row %d is not a residue of limb %d", who, r, l);
+      any = any || t[2 + l];
+    }
+    if (any && t[0] >= (u64)npt) return rh_fail(RH_ERR_ARG, "%s: row %d names plaintext %llu of %d", who, r, (unsigned long long)t[0], npt);
+    if (t[1] > 1) return rh_fail(RH_ERR_ARG, "%s: row %d names half %llu of an RGSW ciphertext", who, r, (unsigned long long)t[1]);
+  }
+  const size_t N = (size_t)rQ->N, R = (size_t)rows;
+  const RhBlock wr[3] = {{tabQ, R * 2 * LQ * N}, {tabP, R * 2 * LP * N}, {table_dev, words}};
+  const RhBlock rd[5] = {{eQ, R * LQ * N}, {eP, R * LP * N}, {skQ, LQ * N}, {skP, LP * N}, {ptQ, (size_t)npt * LQ * N}};
+  if (int rc = rh_blocks_ok(wr, 3, rd, 5, who, "a key table overlaps an input")) return rc;
+  if (int rc = rh_blocks_disjoint(wr, 3, who, "two tables overlap")) return rc;
+  if (!rows) return RH_OK;
+  const RhStreamGrid g = rh_stream_begin(rQ, (unsigned)rows * (unsigned)(LQ + LP) * 3u);     // e and a read, b written
+  hipStream_t st = rh_stream(rQ);
+  RhStage* stage;
+  if (int rc = rh_stage_slot(words, &stage, who)) return rc;
+  memcpy(stage->h, rowtab, (size_t)rows * (size_t)(2 + LQ) * 8);
+  if (int rc = rh_stage_upload(stage, table_dev, words, st, who)) return rc;
+  const RgswEncArgs p{eQ, eP, tabQ, tabP, skQ, skP, ptQ, table_dev};
+  rgsw_encrypt_kernel<<<dim3((unsigned)rows * (unsigned)(LQ + LP), g.grid.y), 256, 0, st>>>(p, (unsigned)N, rQ->d_consts, rP ? rP->d_consts : rQ->d_consts,
+                                                                                             LQ, LP, g.nt);
+  return rh_launch_ok("rgsw_encrypt_kernel");
+}
+
 // blocks of (npoly, level + 1, N) words each, 16-byte aligned; `out` may be one of the per-poly inputs (every lane reads its words before it writes them)
 static int rows_ok(const rh_ring* r, int level, int npoly, const char* who) {
   if (int rc = kg_ring_ok(r, level, npoly, who, "npoly < 0")) return rc;

@@ -135,6 +135,43 @@ rlwe_gadget_encrypt_kernel(GadgetEncArgs p, unsigned n, const LimbConsts* __rest
   }
 }
 
+// ---- rh_rgsw_encrypt: every row of many RGSW ciphertexts under ONE secret (core/rgsw/encryptor.go:25-118) ---------------------------------------------
+// As rlwe_gadget_encrypt_kernel, with a plaintext index apart from the (single) output key and the row's RGSW half: rowtab: rows x (2 + LQ) words:
+// the plaintext of the row, the half k of the RGSW value it belongs to, then the scalar P 2^(j pw2) per limb of Q in Montgomery form, 0 off the
+// digit.  Every row is an encryption of zero, b = MForm(e) - a sk with a as sampled; AddPolyTimesGadgetVectorToGadgetCiphertext then adds pt s to
+// component 0 of a Value[0] row and to component 1 of a Value[1] row: there a + pt s is written over a by the lane that read it.
+// pt: (npt, LQ, N), sk: (LQ | LP, N); NTT domain, Montgomery form.  grid (rows * (LQ + LP), chunks)
+struct RgswEncArgs { const u64* eQ; const u64* eP; u64* tabQ; u64* tabP; const u64* skQ; const u64* skP; const u64* ptQ; const u64* rowtab; };
+
+__global__ void __launch_bounds__(256)
+rgsw_encrypt_kernel(RgswEncArgs p, unsigned n, const LimbConsts* __restrict__ constsQ, const LimbConsts* __restrict__ constsP, int LQ, int LP, int nt) {
+  const StreamRowQP r(blockIdx.x, constsQ, constsP, LQ, LP, StreamRowQP::RowLen{n});
+  const u64* rt = p.rowtab + (size_t)r.poly * (size_t)(2 + LQ);
+  const size_t pi = (size_t)rt[0];
+  const bool half1 = rt[1] != 0;
+  const u64 s = r.inQ ? rt[2 + r.l] : 0;
+  const int Lr = r.inQ ? LQ : LP;
+  const u64* e = (r.inQ ? p.eQ : p.eP) + r.ro;
+  u64* tab = (r.inQ ? p.tabQ : p.tabP) + ((size_t)r.poly * 2 * Lr + r.l) * n;
+  u64* a = tab + (size_t)Lr * n;
+  const u64* sk = (r.inQ ? p.skQ : p.skP) + (size_t)r.l * n;
+  const u64* pt = s ? p.ptQ + (pi * LQ + r.l) * n : nullptr;
+  const LimbConsts c = r.c;
+  RH_FOR_EACH_PAIR(i, 0, n >> 1) {
+    const ulonglong2 ev = rh_ld2(e + 2 * (size_t)i, nt), av = rh_ld2(a + 2 * (size_t)i, nt), sv = rh_ld2(sk + 2 * (size_t)i, false);
+    ulonglong2 b;
+    b.x = cred(mform(ev.x, c.q, c.bred0, c.bred1) + (c.q - mred(av.x, sv.x, c.q, c.qinv)), c.q);
+    b.y = cred(mform(ev.y, c.q, c.bred0, c.bred1) + (c.q - mred(av.y, sv.y, c.q, c.qinv)), c.q);
+    if (s) {
+      const ulonglong2 pv = rh_ld2(pt + 2 * (size_t)i, false);
+      const u64 tx = mred(pv.x, s, c.q, c.qinv), ty = mred(pv.y, s, c.q, c.qinv);
+      if (half1) rh_st2(a + 2 * (size_t)i, make_ulonglong2(cred(av.x + tx, c.q), cred(av.y + ty, c.q)), nt);
+      else { b.x = cred(b.x + tx, c.q); b.y = cred(b.y + ty, c.q); }
+    }
+    rh_st2(tab + 2 * (size_t)i, b, nt);
+  }
+}
+
 // ---- rh_rlwe_encrypt_sk: c0 = -c1 sk + NTT(e) [+ pt] in one launch (core/rlwe/encryptor.go:398-424 with addPtToCt :512-530 folded in) ------------------
 // c1: uniform, NTT domain; sk: (L, N) NTT domain, Montgomery form; e: the NTT of the lifted error; pt: NTT domain or null.
 // c0 = CRed(CRed((q - MRed(c1, sk)) + e) [+ pt]): MulCoeffsMontgomery, Neg (q - x: q for x = 0, folded by the Add's CRed), Add, Add.

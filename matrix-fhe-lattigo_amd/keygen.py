@@ -2,7 +2,7 @@
 
   SecretKey, PublicKey, EvaluationKey, RelinearizationKey, GaloisKey, MemEvaluationKeySet     core/rlwe/keys.go
   KeyGenerator    GenSecretKey(New) :39-72, GenSecretKeyWithHammingWeight(New) :43-58, GenPublicKey(New) :74-90, GenKeyPairNew :92-98,
-                  GenEvaluationKey(New) :230-274 (same ring degree), GenRelinearizationKey(New) :100-120, GenGaloisKey(New) :122-174,
+                  GenEvaluationKey(New) :230-274 (also between ring degrees), GenRelinearizationKey(New) :100-120, GenGaloisKey(New) :122-174,
                   GenGaloisKeys(New) :176-205 -- all keys of a call in one launch sequence
   Encryptor       Encrypt(New), EncryptZero(New), WithKey, WithPRNG: encryptor.go:148-216; secret key :355-460, public key :218-350
   Decryptor       Decrypt(New): decryptor.go:42-90
@@ -10,6 +10,8 @@
 Every arithmetic entry takes `samples=` in place of the PRNG: the uniform block(s) and the int32 error / ternary rows as host arrays; that is
 how it is pinned bit for bit (tests/keygen_restatement.py).  FUSED_KEYGEN selects the kernels of csrc/keygen.hip (rh_rlwe_gadget_encrypt,
 rh_rlwe_encrypt_sk, rh_rlwe_mul_pk, rh_rlwe_decrypt) or the composed ring calls of the reference: the same bits either way.
+gadget_rows also serves rgsw.Encryptor: the rows of many RGSW ciphertexts under one secret, rh_rgsw_encrypt or the composed calls
+(FUSED_KEYGEN["rgsw_encrypt"]).
 
 Rings: standard rings, and 3N rings (kind Matrix3N) whose degree is a multiple of 8; ringQ and ringP of the same kind.  On a 3N ring every
 NTT-domain block this module stores or hands out -- SecretKey.Value, public and evaluation keys, the ciphertexts Encrypt writes -- is in the
@@ -20,7 +22,7 @@ is converted with Ring.ToReferenceOrder first, and every block written carries t
 The error law: xe = (sigma, bound), the discrete Gaussian, or ("P", density) / ("H", weight), a ternary law through TernarySampler (the
 reference's Matrix CKKS test parameters use Xe = ring.Ternary{H: 1}; ring.NewSampler takes any law).
 
-Not built, refused by name: compressed (seeded) keys, evaluation keys between ring degrees, GenEvaluationKeysForRingSwapNew,
+Not built, refused by name: compressed (seeded) keys, GenEvaluationKeysForRingSwapNew,
 conjugate-invariant rings, 3N degrees that are no multiple of 8, Galois keys on 3N rings, the big-norm Gaussian, a plaintext and a ciphertext in
 different domains or allocated at different levels."""
 import functools
@@ -32,12 +34,44 @@ from .rlwe import ElementQP, GadgetCiphertext, PolyQP
 from .sampling import GaussianSampler, NewPRNG, SmallPoly, TernarySampler, UniformSampler, lift_small, rings_ok
 from .schemes import Ciphertext
 
-FUSED_KEYGEN = True          # the kernels of csrc/keygen.hip (True) or the composed ring calls (False); the measured choice: profiles/keygen.json
+class _KeygenSwitches(dict):
+    """FUSED_KEYGEN: its truth value is the switch of the kernels of csrc/keygen.hip that every entry of this module reads ("kernels");
+    ["rgsw_encrypt"]: rh_rgsw_encrypt (True) or the composed ring calls (False) for the rows of RGSW ciphertexts"""
+
+    def __bool__(self):
+        return bool(self["kernels"])
+
+
+# the kernels of csrc/keygen.hip (True) or the composed ring calls (False); the measured choice: profiles/keygen.json.  rgsw_encrypt: one launch for
+# every row against three ring calls per row and limb set; not measured on its own yet, it follows the choice of rh_rlwe_gadget_encrypt, whose
+# row sequence it shares
+FUSED_KEYGEN = _KeygenSwitches(kernels=True, rgsw_encrypt=True)
 SCRATCH_CAP = 1 << 30        # bytes of error scratch (int32 samples + their residues under Q and P) one chunk of a batched key generation may hold
 
 
 def _fused(fused):
-    return FUSED_KEYGEN if fused is None else bool(fused)
+    return bool(FUSED_KEYGEN) if fused is None else bool(fused)
+
+
+def _fused_rgsw(fused):
+    if fused is not None:
+        return bool(fused)
+    return bool(FUSED_KEYGEN["rgsw_encrypt"]) if isinstance(FUSED_KEYGEN, dict) else bool(FUSED_KEYGEN)
+
+
+def centred_coeffs(sk):
+    """the small coefficients of a secret key as int64: its int32 row when it carries one, else INTT and IMForm of limb 0 centred at q_0 >> 1
+    (`coeff > QHalf` is negative, core/rlwe/utils.go:266-275): one N-word download"""
+    ring = sk.Value.Q.ring
+    if sk.coeffs is not None:
+        return np.asarray(sk.coeffs.numpy(), dtype=np.int64).reshape(-1)[:ring.N]
+    r0 = ring.AtLevel(0)
+    t = r0.NewPoly(1)
+    r0.INTT(DevicePoly(r0, 1, 1, ptr=sk.Value.Q.ptr, owner=sk.Value.Q), t)
+    r0.IMForm(t, t)
+    x = t.numpy()[0, 0]
+    q0 = int(ring.moduli[0])
+    return np.where(x > np.uint64(q0 >> 1), x.astype(np.int64) - np.int64(q0), x.astype(np.int64))
 
 
 def _view(p, ring, first, count, limbs=None):
@@ -253,13 +287,16 @@ class KeyGenerator:
         return levelQ, levelP, int(BaseTwoDecomposition)
 
     @reference_order
-    def gadget_rows(self, skIn, skOutQ, skOutP, levelQ, levelP, pw2, nkeys, plaintext=True, samples=None, fused=None, dpl=None):
+    def gadget_rows(self, skIn, skOutQ, skOutP, levelQ, levelP, pw2, nkeys, plaintext=True, samples=None, fused=None, dpl=None, rgsw=None):
         """`nkeys` gadget ciphertexts at (levelQ, levelP) in one launch sequence (genEvaluationKey :276-316 for each): one uniform Read for every a,
         written straight into component 1 of the tables; one Gaussian Read, one lift and one NTT over every error row; one rh_rlwe_gadget_encrypt
         with the per-row key index.  skIn: (1 or nkeys, levelQ + 1, N) -- one input key for all (Galois keys) or one per key; skOutQ / skOutP:
         (nkeys, limbs, N); all NTT domain, Montgomery form.  plaintext=False: encryptions of zero (a public key is one such row).
         Chunked over keys so that the error scratch stays under SCRATCH_CAP.  samples: {"a": (aQ, aP or None), "e": int32} with aQ
         (nkeys * rows, levelQ + 1, N), aP (nkeys * rows, levelP + 1, N), e (nkeys * rows, N), key-major.
+        rgsw=(ptQ, index): the gadget ciphertexts are the halves of nkeys / 2 RGSW ciphertexts under the ONE secret skOutQ / skOutP (gadget 2 k is
+        Value[0] of ciphertext k, gadget 2 k + 1 its Value[1]); ptQ: (npt, levelQ + 1, N) plaintexts, NTT domain, Montgomery form; index[k]: the
+        plaintext of ciphertext k, negative for an encryption of zero; skIn is not read (rh_rgsw_encrypt, or the composed calls).
         Returns (tabQ, tabP, rows, dpl): tables of (nkeys * rows * 2, limbs, N)."""
         rq = self.ringQ.AtLevel(levelQ)
         rp = self.ringP.AtLevel(levelP) if levelP >= 0 else None
@@ -292,7 +329,7 @@ class KeyGenerator:
             tp = _view(tabP, rp, 2 * r0, 2 * rc) if rp is not None else None
             if scratch is None or scratch[0].npoly != rc:
                 scratch = (SmallPoly(rq, rc), DevicePoly(rq, rc, LQ), DevicePoly(rp, rc, LP) if rp is not None else None,
-                           DevicePoly(rq.AtLevel(0), (rc * (LQ + 1) + N - 1) // N + 1, 1))
+                           DevicePoly(rq.AtLevel(0), (rc * (LQ + 2) + N - 1) // N + 1, 1))
             small, eQ, eP, table = scratch
             if samples is None:
                 self.uniform.read_rows(rq, tq.ptr + LQ * N * 8, 2 * LQ, rc, call_a, poly0=r0, row0=0)
@@ -305,7 +342,18 @@ class KeyGenerator:
             rq.NTT(eQ, eQ)
             if rp is not None:
                 rp.NTT(eP, eP)
-            if _fused(fused):
+            if rgsw is not None:
+                ptQ, index = rgsw
+                if _fused_rgsw(fused):
+                    rt = np.array([[max(index[k // 2], 0), k & 1] + (row[1:] if index[k // 2] >= 0 else [0] * LQ) for k in range(k0, k0 + kc) for row in one],
+                                  dtype=np.uint64)
+                    _check(lib().rh_rgsw_encrypt(rq._h, rp._h if rp is not None else None, levelQ, levelP, eQ.ptr, eP.ptr if eP is not None else None,
+                                                 tq.ptr, tp.ptr if tp is not None else None, skOutQ.ptr, skOutP.ptr if skOutP is not None else None,
+                                                 ptQ.ptr if ptQ is not None else None, ptQ.npoly if ptQ is not None else 0,
+                                                 rt.ctypes.data_as(U64P), rc, table.ptr, table.words))
+                else:
+                    self._rows_composed_rgsw(rq, rp, tq, tp, eQ, eP, skOutQ, skOutP, ptQ, index, k0, kc, rows, one)
+            elif _fused(fused):
                 rt = np.array([[k] + row[1:] for k in range(k0, k0 + kc) for row in one], dtype=np.uint64)
                 _check(lib().rh_rlwe_gadget_encrypt(rq._h, rp._h if rp is not None else None, levelQ, levelP, eQ.ptr, eP.ptr if eP is not None else None,
                                                     tq.ptr, tp.ptr if tp is not None else None, skOutQ.ptr, skOutP.ptr if skOutP is not None else None,
@@ -331,12 +379,58 @@ class KeyGenerator:
                 si = _view(skIn, rq, k if skIn.npoly > 1 else 0, 1, LQ)
                 rq.vec_op("MUL_SCALAR_MONT_THEN_ADD", si, None, _view(tq, rq, 2 * r, 1), s0=scal)
 
+    def _rows_composed_rgsw(self, rq, rp, tq, tp, eQ, eP, skQ, skP, ptQ, index, k0, kc, rows, one):
+        """rgsw.Encryptor's calls per row (core/rgsw/encryptor.go:25-118): the encryption of zero as in _rows_composed, then
+        MulScalarMontgomeryThenAdd of the plaintext onto component 0 of a Value[0] row and component 1 of a Value[1] row"""
+        LQ = rq.level + 1
+        for r in range(kc * rows):
+            k = k0 + r // rows
+            for ring, tab, e, s in ((rq, tq, eQ, skQ), (rp, tp, eP, skP)):
+                if ring is None:
+                    continue
+                b, a, er = _view(tab, ring, 2 * r, 1), _view(tab, ring, 2 * r + 1, 1), _view(e, ring, r, 1)
+                ring.MForm(er, b)
+                ring.MulCoeffsMontgomeryThenSub(a, s, b)
+            scal = one[r % rows][1:]
+            if index[k // 2] >= 0 and any(scal):
+                rq.vec_op("MUL_SCALAR_MONT_THEN_ADD", _view(ptQ, rq, index[k // 2], 1, LQ), None, _view(tq, rq, 2 * r + (k & 1), 1), s0=scal)
+
     def _sk_rows(self, sk, levelQ, levelP):
         """views of sk's leading limbs (a single poly's leading limbs are contiguous)"""
         if sk.LevelQ() < levelQ or sk.LevelP() < levelP:
             raise RingHipError("the secret key has fewer limbs than the key's level")
         q = DevicePoly(self.ringQ.AtLevel(levelQ), 1, levelQ + 1, ptr=sk.Value.Q.ptr, owner=sk.Value.Q)
         p = DevicePoly(self.ringP.AtLevel(levelP), 1, levelP + 1, ptr=sk.Value.P.ptr, owner=sk.Value.P) if levelP >= 0 else None
+        return q, p
+
+    @reference_order
+    def _mapped_secret(self, sk, levelQ, levelP):
+        """The secret of a ring of smaller degree n as (Q rows, P rows) of this generator's ring, NTT domain, Montgomery form (:262-272):
+        ring.MapSmallDimensionToLargerDimensionNTT (Y = X^(N/n)) and ExtendBasisSmallNormAndCenterNTTMontgomery (core/rlwe/utils.go:250-284) restated
+        on the small coefficients: INTT and IMForm of limb 0, centred around q_0 / 2 (the key's int32 coefficients when it carries them: the same
+        numbers), placed at every (N/n)-th coefficient, lifted under limbs 0..levelQ of Q and 0..levelP of P (rh_small_lift), NTT, MForm.  The
+        canonical residues of s(X^(N/n)) under every limb: for the limbs of Q the small key holds, the repetition of its NTT rows gives the same
+        words, because both rings take psi from the same generator of q (rlwe._small_ntt).  The small ring's own P is never read; its moduli
+        must be a prefix of this ring's Q."""
+        small = sk.Value.Q.ring
+        _standard(self.ringQ, self.ringP, small)
+        n, N = small.N, self.ringQ.N
+        if n >= N:
+            raise RingHipError("cannot GenEvaluationKey: evaluation keys between ring degrees (N != n) are made by the key generator of the larger degree")
+        mods = [int(q) for q in small.moduli]
+        if mods != self.Q[:len(mods)]:
+            raise RingHipError("cannot GenEvaluationKey: the moduli of the ring of smaller degree must be a prefix of the moduli Q of the larger ring")
+        c = centred_coeffs(sk)
+        big = np.zeros((1, N), dtype=np.int32)
+        big[0, ::N // n] = c
+        rq = self.ringQ.AtLevel(levelQ)
+        rp = self.ringP.AtLevel(levelP) if levelP >= 0 else None
+        q = rq.NewPoly(1)
+        p = rp.NewPoly(1) if rp is not None else None
+        lift_small(rq, rp, SmallPoly.from_numpy(self.ringQ, big), q, p)
+        rq.NTT(q, q); rq.MForm(q, q)
+        if rp is not None:
+            rp.NTT(p, p); rp.MForm(p, p)
         return q, p
 
     def _key(self, cls, tabQ, tabP, first, rows, levelQ, levelP, pw2, dpl):
@@ -366,12 +460,15 @@ class KeyGenerator:
         return sk, self.GenPublicKeyNew(sk)
 
     def GenEvaluationKeyNew(self, skInput, skOutput, levelQ=None, levelP=None, BaseTwoDecomposition=0, compressed=False, samples=None, fused=None, cls=EvaluationKey):
-        """(:230-274), same ring degree: rows (-a skOut + e + w P skIn, a)"""
-        if skInput.Value.Q.ring.N != self.ringQ.N or skOutput.Value.Q.ring.N != self.ringQ.N:
-            raise RingHipError("cannot GenEvaluationKey: evaluation keys between ring degrees (N != n) are not built on the device path")
+        """(:230-274): rows (-a skOut + e + w P skIn, a).  One of the two keys may belong to a ring of smaller degree n: the key is then generated
+        in this generator's degree N, with the smaller key mapped to Y = X^(N/n) and extended to this generator's Q and P (_mapped_secret)."""
         levelQ, levelP, pw2 = self._levels(levelQ, levelP, BaseTwoDecomposition, compressed)
-        si, _ = self._sk_rows(skInput, levelQ, -1)
-        oq, op = self._sk_rows(skOutput, levelQ, levelP)
+        NIn, NOut = skInput.Value.Q.ring.N, skOutput.Value.Q.ring.N
+        if max(NIn, NOut) != self.ringQ.N:
+            raise RingHipError("cannot GenEvaluationKey: evaluation keys between ring degrees (N != n) are made by the key generator of the larger "
+                               "degree (generator: %d, skInput: %d, skOutput: %d)" % (self.ringQ.N, NIn, NOut))
+        si = self._mapped_secret(skInput, levelQ, -1)[0] if NIn != self.ringQ.N else self._sk_rows(skInput, levelQ, -1)[0]
+        oq, op = self._mapped_secret(skOutput, levelQ, levelP) if NOut != self.ringQ.N else self._sk_rows(skOutput, levelQ, levelP)
         tabQ, tabP, rows, dpl = self.gadget_rows(si, oq, op, levelQ, levelP, pw2, 1, samples=samples, fused=fused)
         return self._key(cls, tabQ, tabP, 0, rows, levelQ, levelP, pw2, dpl)
 

@@ -143,6 +143,8 @@ def lib():
         "rh_rlwe_rotate_sum_accumulate_qp": (i, [vp, i, i, C.c_uint64] + [vp] * 10 + [i, i]),
         "rh_rlwe_rotate_mul_accumulate_qp": (i, [vp, i, i, C.c_uint64] + [vp] * 11 + [i, i]),
         "rh_blindrot_core": (i, [vp, i, i, vp, i, vp, U64P, i, vp, vp, i, vp, vp, i]),
+        "rh_blindrot_mod_switch": (i, [vp, i, vp, i, vp, vp, i, vp]), "rh_blindrot_program_stride": (i, [i, i]),
+        "rh_blindrot_program": (i, [vp, i, vp, i, vp, i, vp, C.POINTER(C.c_int32), i, vp, vp, vp]), "rh_blindrot_monomials": (i, [vp, i, vp, i, vp]),
         "rh_rlwe_expand_step": (i, [vp, i, C.c_uint64, vp, vp, vp, vp, vp, i]),
         "rh_rlwe_pack_combine": (i, [vp, i, vp, vp, i, vp, C.POINTER(C.c_int32), i, vp, vp, vp]),
         "rh_rlwe_rotate_addsub_q": (i, [vp, i, C.c_uint64, vp, vp, vp, vp, i, vp, C.POINTER(C.c_int32), i]),
@@ -181,6 +183,8 @@ def lib():
         "rh_small_lift": (i, [vp, vp, i, i, vp, vp, i, vp, i, i, i]),
         "rh_rlwe_gadget_encrypt_table_words": (sz, [i, i]),
         "rh_rlwe_gadget_encrypt": (i, [vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp, i, i, U64P, i, vp, sz]),
+        "rh_rgsw_encrypt_table_words": (sz, [i, i]),
+        "rh_rgsw_encrypt": (i, [vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp, i, U64P, i, vp, sz]),
         "rh_rlwe_encrypt_sk": (i, [vp, i, vp, vp, vp, vp, vp, i]), "rh_rlwe_mul_pk": (i, [vp, i, vp, vp, vp, vp, vp, i]),
         "rh_rlwe_decrypt": (i, [vp, i, vp, vp, vp, vp, vp, i]),
         "rh_matrix_ckks_encode": (i, [vp, i, C.c_double, vp, i, i, i, i, vp]), "rh_matrix_ckks_decode": (i, [vp, C.c_double, vp, i, i, i, i, vp]),

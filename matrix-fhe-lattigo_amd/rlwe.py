@@ -5,7 +5,7 @@ the HIP library.  Key generation, encryption and decryption: keygen.py and sampl
   GadgetProduct          core/rlwe/evaluator_gadget_product.go:16-30
   DecomposeNTT           :431-453        GadgetProductHoisted   :326-349
   Automorphism           core/rlwe/evaluator_automorphism.go:14-60      AutomorphismHoisted  :62-105
-  ApplyEvaluationKey     core/rlwe/evaluator_evaluationkey.go:37-123 (same ring degree)   Relinearize  :125-153
+  ApplyEvaluationKey     core/rlwe/evaluator_evaluationkey.go:37-123 (also between ring degrees)   Relinearize  :125-153
 
 GadgetProduct covers both branches of GadgetProductLazy (:102-121): gadgetProductMultiplePLazy (levelP >= 1) and
 gadgetProductSinglePAndBitDecompLazy (levelP <= 0, optional BaseTwoDecomposition), for NTT- and coefficient-domain ciphertexts.
@@ -316,8 +316,10 @@ class Evaluator:
 
     # ---- core/rlwe/evaluator_evaluationkey.go ---------------------------------------------------------------
     def ApplyEvaluationKey(self, ctIn, evk, opOut):
-        """(:37-123), same ring degree on both sides (:97-99 -> applyEvaluationKey :105-112):
-        opOut = (ctIn[0] + KS(ctIn[1])_0, KS(ctIn[1])_1).  The ring-degree switching branches are not built."""
+        """(:37-123): opOut = (ctIn[0] + KS(ctIn[1])_0, KS(ctIn[1])_1) (applyEvaluationKey :105-112).  With operands of different ring degrees
+        (:50-93) the evaluator is the larger ring's and evk a key between the degrees (KeyGenerator.GenEvaluationKeyNew): to a larger degree the
+        input is first mapped to Y = X^(N/n) (SwitchCiphertextRingDegreeNTT), to a smaller one the key switch runs in the larger ring and its
+        output is mapped down.  NTT-domain operands."""
         if ctIn.Degree() != 1 or opOut.Degree() != 1:
             raise RingHipError("cannot ApplyEvaluationKey: input and output Ciphertext must be of degree 1")
         if not ctIn.IsNTT:
@@ -325,8 +327,31 @@ class Evaluator:
         level = min(ctIn.Level(), opOut.Level())
         ringQ = self.ringQ.AtLevel(level)
         npoly = ctIn.Value[1].npoly
-        self.GadgetProductThenAdd(level, ctIn.Value[1], evk, ctIn.Value[0], None, opOut)   # (:108-111) with the Add in the epilogue
+        NIn, NOut = ctIn.Value[0].ring.N, opOut.Value[0].ring.N
+        if NIn == NOut:
+            self.GadgetProductThenAdd(level, ctIn.Value[1], evk, ctIn.Value[0], None, opOut)   # (:108-111) with the Add in the epilogue
+            opOut.IsNTT = True
+            return
+        if (NOut if NIn < NOut else NIn) != ringQ.N:
+            raise RingHipError("cannot ApplyEvaluationKey: %s ring degree does not match evaluator params ring degree" % ("opOut" if NIn < NOut else "ctIn"))
+        tmp = Ciphertext([ringQ.NewPoly(npoly), ringQ.NewPoly(npoly)], is_ntt=True)
+        if NIn < NOut:
+            SwitchCiphertextRingDegreeNTT(ctIn, self.ringQ, tmp)       # Y = X^(N/n) -> X (:65-69)
+            self._switch_key(level, ringQ, tmp, evk, opOut)            # (:72)
+        else:
+            self._switch_key(level, ringQ, ctIn, evk, tmp)             # (:95)
+            SwitchCiphertextRingDegreeNTT(tmp, self.ringQ, opOut)      # X -> Y = X^(N/n) (:98-102)
+        self._copy_metadata(ctIn, opOut)                               # (:116)
         opOut.IsNTT = True
+
+    def _switch_key(self, level, ringQ, ctIn, evk, opOut):
+        """applyEvaluationKey (:105-112) with either branch of GadgetProduct, by the key's LevelP (as Automorphism below)"""
+        if evk.LevelP() >= 1:
+            self.GadgetProductThenAdd(level, ctIn.Value[1], evk, ctIn.Value[0], None, opOut)
+        else:
+            opOut.IsNTT = True
+            self.GadgetProduct(level, ctIn.Value[1], evk, opOut)
+            ringQ.Add(opOut.Value[0], ctIn.Value[0], opOut.Value[0])
 
     def Relinearize(self, ctIn, opOut, rlk=None):
         """(:125-153): degree 2 -> degree 1 with the relinearisation key (galois_keys["rlk"] or the argument)"""
