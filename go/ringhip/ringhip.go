@@ -360,6 +360,22 @@ func (d *DeviceRing) LinearCombination(level int, x []*C.uint64_t, rows []C.int,
 	d.must(C.rh_ckks_linear_combination(d.h, C.int(level), C.int(len(rows)), xp, rp, p(s0), p(s1), p(c0), p(c1), out[0], out[1], out[2], C.int(npoly), table, C.size_t(tableWords)))
 }
 
+// BgvPlainCombination runs a baby step of the BGV polynomial evaluator over a mapping (circuits/common/polynomial/polynomial_evaluator.go:281-319) as
+// one kernel (rh_bgv_plain_combination): x holds three device blocks per term, rows the limbs per poly of each term's blocks, m one shared plaintext
+// poly per term, c / cScalar the constant and its per-limb scalar (nil: none), table the caller's device scratch.
+func (d *DeviceRing) BgvPlainCombination(level int, x []*C.uint64_t, rows []C.int, m []*C.uint64_t, c *C.uint64_t, cScalar []uint64, out [3]*C.uint64_t, npoly int, table *C.uint64_t, tableWords int) {
+	var xp, mp **C.uint64_t
+	var rp *C.int
+	var cs *C.uint64_t
+	if len(rows) > 0 {
+		xp, rp, mp = &x[0], &rows[0], &m[0]
+	}
+	if len(cScalar) > 0 {
+		cs = (*C.uint64_t)(unsafe.Pointer(&cScalar[0]))
+	}
+	d.must(C.rh_bgv_plain_combination(d.h, C.int(level), C.int(len(rows)), xp, rp, mp, c, cs, out[0], out[1], out[2], C.int(npoly), table, C.size_t(tableWords)))
+}
+
 // AutomorphismNTT mirrors ring.Ring.AutomorphismNTT (ring/automorphism.go:52-73).
 func (d *DeviceRing) AutomorphismNTT(in *DevPoly, galEl uint64, out *DevPoly) {
 	d.must(C.rh_ring_automorphism_ntt(d.h, C.int(in.limbs-1), in.ptr, C.uint64_t(galEl), out.ptr, C.int(in.npoly), 0))

@@ -572,13 +572,30 @@ int rh_bfv_mul_scale_invariant(rh_bfv* b, int level, const uint64_t* a0_dev, con
  *   rh_bgv_mul_plain  the plaintext branches (:737-748, :1370-1400): out_j (+)= ct_j * pt * K for the 1, 2 or 3 components given
  *                     (ct1 / ct2 NULL with out1 / out2: fewer components); k, r1, accumulate (0 / 1) as above.
  *   rh_bgv_axpby      matchScaleThenEvaluateInPlace (:288-305): out = r0 a + r1 b (sub != 0: - r1 b) with r0[i] = MForm(r0), r1[i] = MForm(r1);
- *                     b = r1 = NULL: out = r0 a; a = r0 = NULL: out = +- r1 b (a component the other operand does not have). */
+ *                     b = r1 = NULL: out = r0 a; a = r0 = NULL: out = +- r1 b (a component the other operand does not have).
+ *   rh_bgv_plain_combination  a baby step of the BGV polynomial evaluator over a PolynomialVector with a mapping
+ *                     (circuits/common/polynomial/polynomial_evaluator.go:281-319): the Add of the encoded constant vector and one MulThenAdd
+ *                     by an encoded vector per power (:235-262, :1202-1239, :1370-1400) in ONE launch,
+ *                         out_j = [j == 0] c c_scalar + sum_k X_k,j (.) m_k  mod q_i, the canonical residue, for the 1, 2 or 3 outputs given.
+ *                     x_dev[3 k + j]: component j of term k, a block of x_rows[k] >= level + 1 limbs per poly (a power kept at a higher level
+ *                     is read as its AtLevel view).  m_dev[k] and c_dev (NULL: no constant): ONE poly of level + 1 limbs each, shared by every
+ *                     poly of the batch, NTT domain, Montgomery form: the plain lift of the vector (Embed without scale-up).  The T^-1 of
+ *                     Encode's scale-up and the T of tMontgomery cancel in a term; the constant keeps its T^-1 as c_scalar[i] = T^-1 mod q_i
+ *                     (host, level + 1 residues, given exactly when c_dev is).  table_dev: device scratch of the caller of at least
+ *                     rh_bgv_plain_combination_table_words(nterms) words (NULL with nterms = 0), which carries the terms to the kernel: the
+ *                     call keeps nothing in the handle.  An output may overlap no term, plaintext, other output or the table (RH_ERR_ARG).
+ *                     Products are summed in 128 bits and reduced once per rh_ckks_linear_combination_chunk() terms, which needs every
+ *                     modulus up to `level` below 2^61 (RH_ERR_ARG otherwise, checked per call). */
 int rh_bgv_tensor(rh_ring* r, int level, const uint64_t* a0_dev, const uint64_t* a1_dev, const uint64_t* b0_dev, const uint64_t* b1_dev,
                   uint64_t* c0_dev, uint64_t* c1_dev, uint64_t* c2_dev, int npoly, const uint64_t* k, const uint64_t* r1, int accumulate);
 int rh_bgv_mul_plain(rh_ring* r, int level, const uint64_t* ct0_dev, const uint64_t* ct1_dev, const uint64_t* ct2_dev, const uint64_t* pt_dev,
                      uint64_t* out0_dev, uint64_t* out1_dev, uint64_t* out2_dev, int npoly, const uint64_t* k, const uint64_t* r1, int accumulate);
 int rh_bgv_axpby(rh_ring* r, int level, const uint64_t* a_dev, const uint64_t* b_dev, uint64_t* out_dev, int npoly, const uint64_t* r0,
                  const uint64_t* r1, int sub);
+int rh_bgv_plain_combination(rh_ring* r, int level, int nterms, const uint64_t* const* x_dev, const int* x_rows, const uint64_t* const* m_dev,
+                             const uint64_t* c_dev, const uint64_t* c_scalar, uint64_t* out0_dev, uint64_t* out1_dev, uint64_t* out2_dev, int npoly,
+                             uint64_t* table_dev, size_t table_words);
+size_t rh_bgv_plain_combination_table_words(int nterms);
 
 /* ---- CKKS: the evaluator's element-wise sequences, one launch each (schemes/ckks/evaluator.go) -----------------------------------------
  * Entry points on a STANDARD or conjugate-invariant power-of-two ring handle (RH_ERR_ARG for a 3N ring, a null handle, a level out of

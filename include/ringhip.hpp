@@ -210,6 +210,24 @@ class Ring {
   void BgvAxpby(const Poly* a, const Poly* b, Poly& out, const uint64_t* r0, const uint64_t* r1, bool sub = false) const {
     check(rh_bgv_axpby(h_.get(), level_, a ? a->data() : nullptr, b ? b->data() : nullptr, out.data(), out.npoly(), r0, r1, sub ? 1 : 0));
   }
+  // BGV: a baby step of the polynomial evaluator over a mapping as one kernel (rh_bgv_plain_combination): out_j = [j == 0] c cScalar + sum_k X_k,j (.) m_k.
+  // terms[k]: the components of X_k (each term as many as `out`); m[k] and c (null: no constant, then cScalar null too): one shared poly each, NTT domain,
+  // Montgomery form; table: device scratch of the caller of at least PlainCombinationTableWords(terms.size()) words
+  static size_t PlainCombinationTableWords(size_t nterms) { return rh_bgv_plain_combination_table_words((int)nterms); }
+  void BgvPlainCombination(const std::vector<std::vector<const Poly*>>& terms, const std::vector<const Poly*>& m, const Poly* c, const uint64_t* cScalar,
+                           const std::vector<Poly*>& out, uint64_t* table, size_t tableWords) const {
+    if (out.empty() || out.size() > 3) throw std::invalid_argument("BgvPlainCombination: one to three output components");
+    if (m.size() != terms.size()) throw std::invalid_argument("BgvPlainCombination: one plaintext per term");
+    std::vector<const uint64_t*> x(3 * terms.size(), nullptr), pm(terms.size(), nullptr); std::vector<int> rows(terms.size(), 0);
+    for (size_t k = 0; k < terms.size(); ++k) {
+      if (terms[k].size() != out.size()) throw std::invalid_argument("BgvPlainCombination: every term has the output's components");
+      for (size_t j = 0; j < out.size(); ++j) x[3 * k + j] = terms[k][j]->data();
+      rows[k] = terms[k][0]->limbs();
+      pm[k] = m[k]->data();
+    }
+    check(rh_bgv_plain_combination(h_.get(), level_, (int)terms.size(), x.data(), rows.data(), pm.data(), c ? c->data() : nullptr, cScalar, out[0]->data(),
+                                   out.size() > 1 ? out[1]->data() : nullptr, out.size() > 2 ? out[2]->data() : nullptr, out[0]->npoly(), table, tableWords));
+  }
   void AutomorphismNTT(const Poly& in, uint64_t gen, Poly& out) const { check(rh_ring_automorphism_ntt(h_.get(), level_, in.data(), gen, out.data(), in.npoly(), 0)); }
   void Automorphism(const Poly& in, uint64_t gen, Poly& out) const { check(rh_ring_automorphism(h_.get(), level_, in.data(), gen, out.data(), in.npoly())); }
   // ct_c += phi_gen(tmp_c) modulo Q, both components in one launch: the end of AutomorphismHoisted + ringQ.Add (core/rlwe/inner_sum.go:279-280)

@@ -14,6 +14,7 @@ from . import rgsw  # noqa: F401,E402
 from . import blindrot  # noqa: F401,E402
 from . import bgv  # noqa: F401,E402
 from . import polynomial  # noqa: F401,E402
+from . import bgv_polynomial  # noqa: F401,E402
 from . import lintrans  # noqa: F401,E402
 from . import dft  # noqa: F401,E402
 from . import mod1  # noqa: F401,E402

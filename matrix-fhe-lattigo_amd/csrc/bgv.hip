@@ -14,13 +14,20 @@
 //   bgv_mul_plain_kernel  the plaintext branches (:737-748, :1370-1400): out[i] (+)= ct[i] * (pt * T * r0) for every component, the
 //                         plaintext word and k_i read once per coefficient.
 //   bgv_axpby_kernel      matchScaleThenEvaluateInPlace (:288-305): out = r0 * a +- r1 * b, out = r0 * a, out = +- r1 * b.
+//   bgv_plain_combination_kernel  a baby step of the BGV polynomial evaluator over a PolynomialVector with a mapping
+//                         (circuits/common/polynomial/polynomial_evaluator.go:281-319): the Add of the encoded constant vector (:235-262) and
+//                         one MulThenAdd by an encoded vector per power (:1202-1239, :1370-1400) in one launch.  Every plaintext is ONE poly
+//                         shared by the batch; the products are summed in 128 bits and reduced once per LC_CHUNK terms (lc_reduce.hip.hpp).
+//                         Its terms are AtLevel views of blocks at higher levels; its outputs may alias no input.
 //
-// Each thread reads all of its operands before it writes, so outputs may alias inputs element-wise (opOut is op0 / op1).  Bandwidth-bound,
+// Each thread reads all of its operands before it writes, so outputs may alias inputs element-wise (opOut is op0 / op1) in the first three
+// kernels.  Bandwidth-bound,
 // no LDS; 16-byte loads and stores, non-temporal beyond the Infinity Cache: the scaffold of stream_kernels.hip.hpp.
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include "engine_internal.hpp"
 #include "stream_kernels.hip.hpp"
+#include "lc_reduce.hip.hpp"
 
 // The per-limb constants travel by value as RhScalars: a = k (tensor, mul_plain) or MForm(r0) (axpby), b = r1.
 
@@ -120,6 +127,64 @@ bgv_axpby_kernel(const u64* a, const u64* b, u64* out, unsigned n, const LimbCon
   }
 }
 
+// ---- plain combination ------------------------------------------------------------------------------------------------------------------
+// out_j = [j == 0] c cs + sum_k X_k,j (.) m_k, the canonical residue.  m_k and c: one (L, N) poly each, NTT domain, Montgomery form, read for
+// every poly of the batch (default cache policy, like a diagonal of lintrans); cs: the per-limb scalar the constant is multiplied by (T^-1
+// mod q_i for an encoder constant: Encode's scale-up).  Each sum is T = sum x m 2^64 in 128 bits, taken to x m by lc_reduce's Montgomery step.
+// The device table of a call, in words: per term { block of component 0, 1, 2; limbs per poly of the blocks; the plaintext poly }.
+#define BPC_TERM_WORDS 5
+static inline size_t bpc_table_words(int nterms) { return (size_t)nterms * BPC_TERM_WORDS; }
+
+// grid: (npoly * L, chunks).  The term loops run on kernel arguments and table words alone: wave-uniform.
+template <int NC>
+__global__ void __launch_bounds__(256)
+bgv_plain_combination_kernel(BgvComps p, const u64* __restrict__ table, int nterms, const u64* cpoly, unsigned n, const LimbConsts* __restrict__ consts,
+                             int L, RhScalars s, int nt) {
+  const StreamRow row(consts, L, n);
+  const LimbConsts& c = row.c;
+  const size_t po = (size_t)row.limb * n;                                               // the row of a shared plaintext poly
+  const u64 cs = s.a[row.limb];
+  RH_FOR_EACH_PAIR(i, 0, n >> 1) {
+    const size_t w = 2 * (size_t)i;
+    ulonglong2 res[NC];
+#pragma unroll
+    for (int j = 0; j < NC; ++j) res[j] = make_ulonglong2(0, 0);
+    if (cpoly) {
+      const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(cpoly + po + w);
+      res[0] = make_ulonglong2(lc_reduce((u128)v.x * cs, c), lc_reduce((u128)v.y * cs, c));
+    }
+    for (int k0 = 0; k0 < nterms; k0 += LC_CHUNK) {
+      const int k1 = min(k0 + LC_CHUNK, nterms);
+      u128 acc[NC][2];
+#pragma unroll
+      for (int j = 0; j < NC; ++j) acc[j][0] = acc[j][1] = 0;
+      for (int k = k0; k < k1; k += LC_WIDTH) {
+        ulonglong2 x[LC_WIDTH][NC], m[LC_WIDTH];
+#pragma unroll
+        for (int g = 0; g < LC_WIDTH; ++g) {
+          if (k + g >= k1) break;
+          const u64* t = table + (size_t)(k + g) * BPC_TERM_WORDS;
+          const size_t o = row.at((int)t[3], n) + w;
+          m[g] = *reinterpret_cast<const ulonglong2*>(lc_block(t[4]) + po + w);          // shared by every poly: default cache policy
+#pragma unroll
+          for (int j = 0; j < NC; ++j) x[g][j] = rh_ld2(lc_block(t[j]) + o, nt);
+        }
+#pragma unroll
+        for (int g = 0; g < LC_WIDTH; ++g) {
+          if (k + g >= k1) break;
+#pragma unroll
+          for (int j = 0; j < NC; ++j) { acc[j][0] += (u128)x[g][j].x * m[g].x; acc[j][1] += (u128)x[g][j].y * m[g].y; }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < NC; ++j) { res[j].x = cred(res[j].x + lc_reduce(acc[j][0], c), c.q); res[j].y = cred(res[j].y + lc_reduce(acc[j][1], c), c.q); }
+    }
+    const size_t o = row.ro + w;
+#pragma unroll
+    for (int j = 0; j < NC; ++j) rh_st2(p.out[j] + o, res[j], nt);
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
@@ -188,4 +253,64 @@ extern "C" int rh_bgv_axpby(rh_ring* r, int level, const uint64_t* a, const uint
   else BGV_A(3);
 #undef BGV_A
   return rh_launch_ok("bgv_axpby_kernel");
+}
+
+extern "C" size_t rh_bgv_plain_combination_table_words(int nterms) { return nterms < 0 ? 0 : bpc_table_words(nterms); }
+
+extern "C" int rh_bgv_plain_combination(rh_ring* r, int level, int nterms, const uint64_t* const* x, const int* x_rows, const uint64_t* const* m,
+                                        const uint64_t* c, const uint64_t* c_scalar, uint64_t* out0, uint64_t* out1, uint64_t* out2, int npoly,
+                                        uint64_t* table, size_t table_words) {
+  const char* who = "rh_bgv_plain_combination";
+  if (int rc = rh_scheme_args(r, level, npoly, BGV_RINGS, 2, who)) return rc;
+  if (nterms < 0) return rh_fail(RH_ERR_ARG, "%s: nterms < 0", who);
+  if (!out0 || (out2 && !out1) || (c == nullptr) != (c_scalar == nullptr) || (nterms && (!x || !x_rows || !m))) return rh_fail(RH_ERR_ARG, "%s: null argument", who);
+  if (nterms && !table) return rh_fail(RH_ERR_ARG, "%s: null table (device scratch of rh_bgv_plain_combination_table_words(nterms) words)", who);
+  const int L = level + 1, nc = out2 ? 3 : out1 ? 2 : 1;
+  const size_t words = bpc_table_words(nterms), N = (size_t)r->N;
+  if (table_words < words) return rh_fail(RH_ERR_ARG, "%s: the table holds %zu words, %d terms need %zu", who, table_words, nterms, words);
+  if (int rc = rh_moduli_below(r, L, LC_MODULUS_BITS, LC_CHUNK, who)) return rc;
+  u64* outs[3] = {out0, out1, out2};
+  RhBlock written[4], read[4];
+  for (int j = 0; j < nc; ++j) written[j] = {outs[j], (size_t)npoly * L * N};
+  if (int rc = rh_blocks_disjoint(written, nc, who, "two outputs overlap")) return rc;
+  const int nw = nterms ? nc + 1 : nc;
+  if (nterms) written[nc] = {table, words};
+  for (int k = 0; k < nterms; ++k) {
+    if (x_rows[k] < L) return rh_fail(RH_ERR_ARG, "%s: term %d holds %d limbs per poly, fewer than level %d needs", who, k, x_rows[k], level);
+    if (!m[k]) return rh_fail(RH_ERR_ARG, "%s: term %d has no plaintext", who, k);
+    for (int j = 0; j < nc; ++j) {
+      if (!x[3 * k + j]) return rh_fail(RH_ERR_ARG, "%s: term %d has no component %d", who, k, j);
+      read[j] = {x[3 * k + j], (size_t)npoly * (size_t)x_rows[k] * N};
+    }
+    read[nc] = {m[k], (size_t)L * N};
+    if (int rc = rh_blocks_ok(written, nw, read, nc + 1, who, "an output (or the table) overlaps a term or its plaintext: the sum is not computed in place")) return rc;
+  }
+  if (c) {
+    read[0] = {c, (size_t)L * N};
+    if (int rc = rh_blocks_ok(written, nw, read, 1, who, "an output (or the table) overlaps the constant")) return rc;
+  }
+  if (nterms) if (int rc = rh_blocks_ok(written, nc, written + nc, 1, who, "an output overlaps the table")) return rc;
+  RhScalars s;
+  if (int rc = rh_pack_scalars(r, level, c_scalar, nullptr, false, &s, who, "constant's scalar")) return rc;
+  const unsigned rows = (unsigned)npoly * (unsigned)L;
+  const RhStreamGrid g = rh_stream_begin(r, rows);
+  hipStream_t st = rh_stream(r);
+  if (nterms) {
+    RhStage* stage;
+    if (int rc = rh_stage_slot(words, &stage, who)) return rc;
+    for (int k = 0; k < nterms; ++k) {
+      u64* e = stage->h + (size_t)k * BPC_TERM_WORDS;
+      for (int j = 0; j < 3; ++j) e[j] = j < nc ? (u64)(uintptr_t)x[3 * k + j] : 0;
+      e[3] = (u64)x_rows[k];
+      e[4] = (u64)(uintptr_t)m[k];
+    }
+    if (int rc = rh_stage_upload(stage, table, words, st, who)) return rc;
+  }
+  if (rows == 0) return RH_OK;
+  const BgvComps p{{nullptr, nullptr, nullptr}, {out0, out1, out2}};
+  const unsigned n = (unsigned)r->N;
+#define BGV_PC(NC) bgv_plain_combination_kernel<NC><<<g.grid, 256, 0, st>>>(p, table, nterms, c, n, r->d_consts, L, s, g.nt)
+  if (nc == 1) BGV_PC(1); else if (nc == 2) BGV_PC(2); else BGV_PC(3);
+#undef BGV_PC
+  return rh_launch_ok("bgv_plain_combination_kernel");
 }

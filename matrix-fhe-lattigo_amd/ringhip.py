@@ -157,6 +157,8 @@ def lib():
         "rh_bfv_mul_scale_invariant": (i, [vp, i, vp, vp, vp, vp, vp, vp, vp, i]),
         "rh_bgv_tensor": (i, [vp, i] + [vp] * 7 + [i, U64P, U64P, i]), "rh_bgv_mul_plain": (i, [vp, i] + [vp] * 7 + [i, U64P, U64P, i]),
         "rh_bgv_axpby": (i, [vp, i, vp, vp, vp, i, U64P, U64P, i]),
+        "rh_bgv_plain_combination": (i, [vp, i, i, C.POINTER(vp), C.POINTER(i), C.POINTER(vp), vp, U64P, vp, vp, vp, i, vp, sz]),
+        "rh_bgv_plain_combination_table_words": (sz, [i]),
         "rh_ckks_tensor": (i, [vp, i] + [vp] * 7 + [i, i, i]), "rh_ckks_mul_plain": (i, [vp, i] + [vp] * 7 + [i, i]),
         "rh_ckks_scalar": (i, [vp, i, i] + [vp] * 6 + [i, U64P, U64P]), "rh_ckks_scale_then_add": (i, [vp, i] + [vp] * 9 + [i, U64P, i, i]),
         "rh_ckks_linear_combination": (i, [vp, i, i, C.POINTER(vp), C.POINTER(i), U64P, U64P, U64P, U64P, vp, vp, vp, i, vp, sz]),
