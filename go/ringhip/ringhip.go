@@ -429,6 +429,38 @@ func (d *DeviceRing) PolyMul(a, b, c *DevPoly) {
 	d.must(C.rh_ring_polymul(d.h, a.ptr, b.ptr, c.ptr, C.int(a.npoly), C.int(a.limbs-1)))
 }
 
+// BgvEncoder is the device form of bgv.Encoder's state (schemes/bgv/encoder.go:49-96): ringQ, the plaintext ring T and the index matrix.
+type BgvEncoder struct {
+	h *C.rh_bgv_encoder
+	q *DeviceRing
+}
+
+func NewBgvEncoder(q, t *DeviceRing) (*BgvEncoder, error) {
+	e := &BgvEncoder{q: q}
+	if rc := C.rh_bgv_encoder_create(&e.h, q.h, t.h); rc != 0 {
+		return nil, fmt.Errorf("ringhip: %s", C.GoString(C.rh_last_error()))
+	}
+	return e, nil
+}
+
+// EmbedQP encodes a whole linear transformation in one pass (rh_bgv_embed_qp): rotateAndEncodeDiagonal
+// (circuits/common/lintrans/lintrans.go:271-292) for the outQ.npoly vectors of `values` (a device block of nvals words per vector), each row of
+// cols values rotated to the left by rot[k] (nil: none), embedded into the (Q, P) pair.
+func (e *BgvEncoder) EmbedQP(p *DeviceRing, scale uint64, values *C.uint64_t, nvals int, signed bool, rot []C.int, cols int, outQ, outP *DevPoly, isNTT, isMontgomery bool) {
+	var rp *C.int
+	if len(rot) > 0 {
+		rp = &rot[0]
+	}
+	b := func(v bool) C.int {
+		if v {
+			return 1
+		}
+		return 0
+	}
+	e.q.must(C.rh_bgv_embed_qp(e.h, p.h, C.int(outQ.limbs-1), C.int(outP.limbs-1), C.uint64_t(scale), values, C.int(nvals), b(signed), C.int(outQ.npoly), rp, C.int(cols),
+		outQ.ptr, outP.ptr, b(isNTT), b(isMontgomery)))
+}
+
 // KeySwitcher pairs the Q and P device rings (ring.BasisExtender + the gadget product of rlwe.Evaluator).
 type KeySwitcher struct {
 	be   *C.rh_bext

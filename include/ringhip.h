@@ -780,7 +780,17 @@ int rh_ckks_decode(rh_ckks_encoder* e, int level, int log_slots, double scale, d
  *                            is_montgomery; batched = 0: the values at coefficients 0 .. nvals-1, MulScalar(scale), RingT2Q, NTT.  Without
  *                            scale_up, is_ntt and is_montgomery the words are the raw residues modulo T the reference leaves.
  *   rh_bgv_decode            Decode (:442-487): Ring.INTT if is_ntt, RingQ2T, then DecodeRingT (batched) or MulScalar(scale^-1) and the
- *                            values in coefficient order.  in_dev is not modified. */
+ *                            values in coefficient order.  in_dev is not modified.
+ *   rh_bgv_embed_qp          a whole linear transformation in one pass (circuits/common/lintrans/lintrans.go:271-292 over Embed into a
+ *                            ringqp.Poly): for each of the nvec vectors, limbs 0 .. levelQ of outQ (nvec, levelQ + 1, N) and 0 .. levelP of outP
+ *                            (nvec, levelP + 1, N) are exactly the words of: each row of cols values rotated to the left by rot[k] & (cols - 1)
+ *                            on the host, rh_bgv_encode(ringQ, scale_up = 0), rh_bgv_encode(ringP).  rot: a HOST array of nvec rotations, or
+ *                            NULL (no rotation, cols ignored).  One gather (rotation + slot permutation), one inverse transform over T, one
+ *                            lift onto the rows of both rings, the forward transforms; "fused" = 0 issues the rotation as a pass of its own
+ *                            and then the composition of rh_bgv_encode per ring -- the same bits.  Refused by name: null pointers, levels out
+ *                            of range, a ringP that is no standard ring of degree N on ringQ's device, nvals > n; with rot: cols no power of
+ *                            two, or not nvals = n = 2 * cols (a BGV plaintext has the encoder's dimensions; shorter rows are the caller's to
+ *                            rotate); outputs that overlap the values or each other. */
 typedef struct rh_bgv_encoder rh_bgv_encoder;
 int rh_bgv_encoder_create(rh_bgv_encoder** out, rh_ring* ringQ, rh_ring* ringT);
 void rh_bgv_encoder_destroy(rh_bgv_encoder* e);
@@ -794,6 +804,8 @@ int rh_bgv_encode_ring_t(rh_bgv_encoder* e, uint64_t scale, const uint64_t* valu
 int rh_bgv_decode_ring_t(rh_bgv_encoder* e, uint64_t scale, const uint64_t* pT_dev, int nvec, uint64_t* values_dev, int nvals, int is_signed);
 int rh_bgv_ring_t2q(rh_bgv_encoder* e, rh_ring* ring, int level, int scale_up, const uint64_t* pT_dev, uint64_t* out_dev, int nvec);
 int rh_bgv_ring_q2t(rh_bgv_encoder* e, int level, const uint64_t* in_dev, uint64_t* pT_dev, int nvec);
+int rh_bgv_embed_qp(rh_bgv_encoder* e, rh_ring* ringP, int levelQ, int levelP, uint64_t scale, const uint64_t* values_dev, int nvals, int is_signed,
+                    int nvec, const int* rot, int cols, uint64_t* outQ_dev, uint64_t* outP_dev, int is_ntt, int is_montgomery);
 
 /* ---- limb-sharded hybrid key switch (BASELINE config 5): one process per GPU owns a subset of the limbs
  * of Q and P and the matching slice of the evaluation key.  Same arithmetic as rh_bext_gadget_product, cut where

@@ -414,6 +414,23 @@ class BfvEvaluator {
   std::shared_ptr<rh_bfv> h_;
 };
 
+// bgv.Encoder's state on the device (schemes/bgv/encoder.go:49-96) and the one-pass encoding of a linear transformation
+class BgvEncoder {
+ public:
+  BgvEncoder(const Ring& q, const Ring& t) { rh_bgv_encoder* h = nullptr; check(rh_bgv_encoder_create(&h, q.handle(), t.handle())); h_.reset(h, rh_bgv_encoder_destroy); }
+  void Reserve(int nvec) const { check(rh_bgv_encoder_reserve(h_.get(), nvec)); }
+  void SetTuning(const char* key, long value) const { check(rh_bgv_encoder_set_tuning(h_.get(), key, value)); }
+  // rotateAndEncodeDiagonal (circuits/common/lintrans/lintrans.go:271-292) for outQ.npoly() vectors at once (rh_bgv_embed_qp): values is a device
+  // block of nvals words per vector; rot (host, one rotation per vector) may be null
+  void EmbedQP(const Ring& p, uint64_t scale, const uint64_t* values, int nvals, bool isSigned, const int* rot, int cols, Poly& outQ, Poly& outP,
+               bool isNTT = true, bool isMontgomery = true) const {
+    check(rh_bgv_embed_qp(h_.get(), p.handle(), outQ.limbs() - 1, outP.limbs() - 1, scale, values, nvals, isSigned ? 1 : 0, outQ.npoly(), rot, cols,
+                          outQ.data(), outP.data(), isNTT ? 1 : 0, isMontgomery ? 1 : 0));
+  }
+ private:
+  std::shared_ptr<rh_bgv_encoder> h_;
+};
+
 // limb-sharded key switch (rh_kshard_*): this rank's limbs of the gadget product; the caller moves the
 // gathered source limbs (RCCL all-gather) between Digit / ModDown calls
 class KeySwitchShard {

@@ -16,6 +16,7 @@ from . import bgv  # noqa: F401,E402
 from . import polynomial  # noqa: F401,E402
 from . import bgv_polynomial  # noqa: F401,E402
 from . import lintrans  # noqa: F401,E402
+from . import bgv_lintrans  # noqa: F401,E402
 from . import dft  # noqa: F401,E402
 from . import mod1  # noqa: F401,E402
 from . import bootstrapping  # noqa: F401,E402

@@ -956,6 +956,30 @@ class Encoder:
         """:318-320"""
         return self.EmbedScale(values, False, metadata, polyOut)
 
+    def EmbedRows(self, values, rots, cols, metadata, polyQP):
+        """A whole linear transformation in one pass (rh_bgv_embed_qp): vector k of `values` -- a (nvec, 2 * cols) array or DeviceValues -- is
+        rotated to the left by rots[k] on each of its two rows (rotateAndEncodeDiagonal, circuits/common/lintrans/lintrans.go:271-292) and
+        embedded into poly k of the (Q, P) pair, the words Embed writes for the rotated vector.  rots None: no rotation, any length up to
+        the slot count."""
+        if not isinstance(polyQP, (tuple, list, rlwe.PolyQP)):
+            raise RingHipError("cannot embed: invalid polyOut.(Type) must be ringqp.Poly")
+        Q, P = (polyQP.Q, polyQP.P) if isinstance(polyQP, rlwe.PolyQP) else tuple(polyQP)
+        if not isinstance(Q, DevicePoly) or not isinstance(P, DevicePoly):
+            raise RingHipError("cannot embed: invalid polyOut.(Type) must be ringqp.Poly")
+        if self.ringP is None:
+            raise RingHipError("cannot embed into a ringqp.Poly: the encoder was built without ringP")
+        if self._ring_of(Q, "EmbedRows") is not self.ringQ or self._ring_of(P, "EmbedRows") is not self.ringP or P.npoly != Q.npoly:
+            raise RingHipError("cannot EmbedRows: polyQP must pair a block of ringQ with a block of ringP of as many polys")
+        dv = self._block(values, Q.npoly, "cannot EncodeRingT (FrequencyDomain): len(values)=%%d > slots=%d" % self.ringT.N)
+        rot = None
+        if rots is not None:
+            if len(rots) != Q.npoly:
+                raise RingHipError("cannot EmbedRows: %d rotations given for a block of %d polys" % (len(rots), Q.npoly))
+            rot = (C.c_int * max(Q.npoly, 1))(*[int(r) & (int(cols) - 1) for r in rots])
+        scale, ntt, mont = getattr(metadata, "Scale", 1), metadata.IsNTT, getattr(metadata, "IsMontgomery", False)
+        _check(lib().rh_bgv_embed_qp(self._h, self.ringP._h, Q.limbs - 1, P.limbs - 1, int(scale) % (1 << 64), dv.ptr, dv.n, 1 if dv.signed else 0,
+                                     Q.npoly, rot, int(cols), Q.ptr, P.ptr, 1 if ntt else 0, 1 if mont else 0))
+
     def EncodeRingT(self, values, scale, pT):
         """:187-246; pT: a DevicePoly of RingT(), one limb"""
         dv = self._block(values, pT.npoly, "cannot EncodeRingT (FrequencyDomain): len(values)=%%d > slots=%d" % self.ringT.N)

@@ -20,7 +20,7 @@ Refused by name: a basis other than Monomial (the reference's BGV package never 
 polynomials with Lazy = True (the power basis then holds powers of mixed degrees, and the reference's MulThenAdd drops the accumulator's third
 component when a relinearised power follows a lazy one: opOut.Resize(op0.Degree(), ...), schemes/bgv/evaluator.go:1170 -- there is nothing sound
 to match; PowerBasis.GenPower(lazy=True) itself is supported), a mapping on an evaluator without an encoder, conjugate-invariant and 3N rings.
-BGV linear transformations stay with the reference."""
+BGV linear transformations are bgv_lintrans.py."""
 import ctypes as C
 import math
 import types

@@ -11,7 +11,7 @@
 // set one of the two) -- the same bits; the exact-CRT branch (level > 0, gap > 1), which the reference takes through math/big, has the one
 // device form.
 //
-// The handle owns its scratch (one (nvec, n) block modulo T, one (nvec, L, N) poly block); rh_bgv_encoder_reserve sizes it so that no later
+// The handle owns its scratch (one (nvec, n) block modulo T, one (nvec, L, N) poly block, the rotation table of rh_bgv_embed_qp); rh_bgv_encoder_reserve sizes it so that no later
 // call allocates.  Calls are asynchronous on ringQ's stream -- ringT and the ring of rh_bgv_encode are pinned to it for the call -- and lock
 // the handle for the enqueue only: the scratch is reused in stream order.
 #include <hip/hip_runtime.h>
@@ -40,7 +40,7 @@ struct rh_bgv_encoder {
   std::vector<u64> tinv_mont;          // MForm(T^-1 mod q_i): (T^-1 mod Q_level) mod q_i, whatever the level
   std::vector<BextPlan> plans;         // per level >= 1, gap = 1: GenModUpConstants(Q[:level + 1], {T}) (:61-65)
   std::vector<u64> half_t;             // ... and floor(Q_level / 2) mod T, the scalar of SubScalarBigint (:411)
-  void* buf[2] = {nullptr, nullptr}; size_t buf_bytes[2] = {0, 0};
+  void* buf[3] = {nullptr, nullptr, nullptr}; size_t buf_bytes[3] = {0, 0, 0};   // (nvec, n) modulo T | (nvec, L, N) | one rotation per vector
   int fused_lift = BGV_ENC_FUSED_LIFT, fused_level0 = BGV_ENC_FUSED_Q2T_LEVEL0, fused_modup = BGV_ENC_FUSED_Q2T_MODUP;
   std::recursive_mutex mu;
 };
@@ -173,6 +173,7 @@ extern "C" int rh_bgv_encoder_reserve(rh_bgv_encoder* e, int nvec) {
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   (void)hipSetDevice(e->Q->device);
   if (int rc = benc_scratch(e, 0, (size_t)nvec * e->n * 8)) return rc;
+  if (int rc = benc_scratch(e, 2, (size_t)nvec * 8)) return rc;
   return benc_scratch(e, 1, (size_t)nvec * e->Q->L * e->Q->N * 8);
 }
 
@@ -380,4 +381,76 @@ extern "C" int rh_bgv_decode(rh_bgv_encoder* e, int level, uint64_t scale, const
   if (int rc = benc_q2t(e, level, src, bufT, nvec, sinv, 1, call.st)) return rc;
   if (batched) if (int rc = rh_ring_ntt_any(e->T, bufT, bufT, nvec, 1, 0, false)) return rc;
   return benc_slots(e, false, bufT, values_dev, (unsigned)nvals, nvec, batched, is_signed, call.st);
+}
+
+// A whole linear transformation: rotateAndEncodeDiagonal (circuits/common/lintrans/lintrans.go:271-292) for nvec diagonals at once, Embed into
+// the (Q, P) pair; see ringhip.h.  One gather (row rotation + slot permutation), ONE inverse transform over T, one lift onto the rows of
+// both rings, the forward transforms.  "fused" = 0: the rotation as a pass of its own, then the composition rh_bgv_encode issues, per ring.
+extern "C" int rh_bgv_embed_qp(rh_bgv_encoder* e, rh_ring* ringP, int levelQ, int levelP, uint64_t scale, const uint64_t* values_dev, int nvals,
+                               int is_signed, int nvec, const int* rot, int cols, uint64_t* outQ_dev, uint64_t* outP_dev, int is_ntt,
+                               int is_montgomery) {
+  const char* who = "rh_bgv_embed_qp";
+  if (int rc = benc_nvec(e, nvec, who)) return rc;
+  if (int rc = benc_ring(e, ringP, 0, who)) return rc;
+  if (int rc = benc_level(e->Q, levelQ, who)) return rc;
+  if (int rc = benc_level(ringP, levelP, who)) return rc;
+  if (!values_dev || !outQ_dev || !outP_dev) return rh_fail(RH_ERR_ARG, "%s: null argument", who);
+  if (int rc = benc_values(e, nvals, 1, true)) return rc;
+  if (rot) {
+    if (cols <= 0 || (cols & (cols - 1))) return rh_fail(RH_ERR_ARG, "%s: cols = %d is not a power of two", who, cols);
+    if ((unsigned)nvals != e->n || 2 * (long long)cols != (long long)nvals)
+      return rh_fail(RH_ERR_ARG, "%s: a rotation needs the encoder's own dimensions, nvals = n = 2 * cols (nvals = %d, n = %u, cols = %d); rows of another "
+                                 "length are rotated by the caller", who, nvals, e->n, cols);
+  }
+  const int LQ = levelQ + 1, LP = levelP + 1;
+  const size_t N = (size_t)e->Q->N;
+  { const RhBlock w[2] = {{outQ_dev, (size_t)nvec * LQ * N}, {outP_dev, (size_t)nvec * LP * N}}, r[1] = {{values_dev, (size_t)nvec * (size_t)nvals}};
+    if (int rc = rh_blocks_ok(w, 2, r, nvals ? 1 : 0, who, "an output overlaps the values")) return rc;
+    if (int rc = rh_blocks_disjoint(w, 2, who, "outQ and outP overlap")) return rc; }
+  if (nvec == 0) return RH_OK;
+  BencCall call(e);
+  if (int rc = benc_scratch(e, 0, (size_t)nvec * e->n * 8)) return rc;
+  u64* bufT = (u64*)e->buf[0];
+  const u64* d_rot = nullptr;
+  if (rot) {                                                             // rot & (cols - 1) per vector (:276), one word each, through the thread's staging slots
+    if (int rc = benc_scratch(e, 2, (size_t)nvec * 8)) return rc;
+    RhStage* stage;
+    if (int rc = rh_stage_slot((size_t)nvec, &stage, who)) return rc;
+    for (int k = 0; k < nvec; ++k) stage->h[k] = (u64)((unsigned)rot[k] & (unsigned)(cols - 1));
+    if (int rc = rh_stage_upload(stage, (u64*)e->buf[2], (size_t)nvec, call.st, who)) return rc;
+    d_rot = (const u64*)e->buf[2];
+  }
+  const int canonical = (is_ntt || is_montgomery) ? 1 : 0;
+  const u64 s_mont = rh::mform(scale, e->t);
+  if (e->fused_lift) {
+    bgv_embed_gather_kernel<<<benc_grid(e->n, nvec), 256, 0, call.st>>>(values_dev, bufT, e->d_inv, d_rot, e->n, (unsigned)nvals, (unsigned)cols, e->m, is_signed);
+    if (int rc = rh_launch_ok("bgv_embed_gather_kernel")) return rc;
+    if (int rc = rh_ring_ntt_any(e->T, bufT, bufT, nvec, 1, 0, true)) return rc;
+    const RhStreamGrid g = rh_stream_grid(e->Q, (unsigned)nvec * (unsigned)(LQ + LP));
+    bgv_lift_qp_kernel<<<g.grid, 256, 0, call.st>>>(bufT, outQ_dev, outP_dev, e->n, e->Q->logN, e->loggap, e->Q->d_consts, ringP->d_consts, LQ, LP, e->m,
+                                                     s_mont, canonical, is_montgomery ? 1 : 0, g.nt);
+    if (int rc = rh_launch_ok("bgv_lift_qp_kernel")) return rc;
+    if (is_ntt) {
+      if (int rc = rh_ring_ntt_any(e->Q, outQ_dev, outQ_dev, nvec, LQ, 0, false)) return rc;
+      if (int rc = rh_ring_ntt_any(ringP, outP_dev, outP_dev, nvec, LP, 0, false)) return rc;
+    }
+    return RH_OK;
+  }
+  const u64* src = values_dev;
+  if (d_rot) {                                                           // the rotated rows in the handle's poly block (nvec * n <= nvec * L * N words)
+    if (int rc = benc_scratch(e, 1, (size_t)nvec * e->Q->L * N * 8)) return rc;
+    bgv_rotate_rows_kernel<<<benc_grid(e->n, nvec), 256, 0, call.st>>>(values_dev, (u64*)e->buf[1], d_rot, (unsigned)cols);
+    if (int rc = rh_launch_ok("bgv_rotate_rows_kernel")) return rc;
+    src = (const u64*)e->buf[1];
+  }
+  if (int rc = benc_slots(e, true, src, bufT, (unsigned)nvals, nvec, 1, is_signed, call.st)) return rc;
+  if (int rc = rh_ring_ntt_any(e->T, bufT, bufT, nvec, 1, 0, true)) return rc;
+  if (int rc = benc_mul_scalar_t(e, bufT, bufT, nvec, s_mont)) return rc;              // once: both rings lift the same scaled block
+  rh_ring* rings[2] = {e->Q, ringP}; u64* outs[2] = {outQ_dev, outP_dev}; const int lv[2] = {levelQ, levelP};
+  for (int k = 0; k < 2; ++k) {
+    if (int rc = benc_lift(e, rings[k], lv[k], bufT, outs[k], nvec, 0, 0, 0, canonical, 0, call.st)) return rc;
+    if (is_ntt) if (int rc = rh_ring_ntt_any(rings[k], outs[k], outs[k], nvec, lv[k] + 1, 0, false)) return rc;
+    if (is_montgomery) if (int rc = rh_vec_launch(rings[k], RH_OP_MFORM, outs[k], nullptr, outs[k], nvec, lv[k] + 1, 0, nullptr, nullptr)) return rc;
+  }
+  return RH_OK;
 }

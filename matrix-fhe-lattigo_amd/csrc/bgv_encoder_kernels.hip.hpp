@@ -82,6 +82,74 @@ bgv_lift_kernel(const u64* __restrict__ pT, u64* __restrict__ out, unsigned n, u
   }
 }
 
+// ---- a whole linear transformation (circuits/common/lintrans/lintrans.go:271-292 + Embed into a ringqp.Poly) ------------------------------
+// The gather of rh_bgv_embed_qp: rotateAndEncodeDiagonal's row rotation and the slot permutation in one pass, one thread per word of pT.
+//   pT[vec][j] = rule(values[vec][r * cols + ((c + rot[vec]) & (cols - 1))]),   (r, c) the row and column of i = inv[j] in the 2 x cols matrix
+// with the value rules of bgv_slots_kernel<true> unchanged (BRedAdd / sign-abs, zero past nvals).  rot: one word per vector, already reduced
+// modulo cols, or nullptr (no rotation: the index is inv[j] itself, whatever nvals and cols).  With rot the host side has checked
+// nvals == n == 2 * cols, so every index read is below nvals.  values: (nvec, nvals); pT: (nvec, n).  grid (ceil(n / 256), nvec).
+__global__ void __launch_bounds__(256)
+bgv_embed_gather_kernel(const u64* __restrict__ values, u64* __restrict__ pT, const unsigned* __restrict__ inv, const u64* __restrict__ rot,
+                        unsigned n, unsigned nvals, unsigned cols, BgvModT m, int is_signed) {
+  const unsigned j = blockIdx.x * 256u + threadIdx.x;
+  if (j >= n) return;
+  const size_t vec = blockIdx.y;
+  unsigned i = inv[j];
+  if (rot) i = (i & ~(cols - 1)) | ((i + (unsigned)rot[vec]) & (cols - 1));
+  u64 w = 0;
+  if (i < nvals) {
+    const u64 c = values[vec * nvals + i];
+    if (is_signed) {
+      const u64 sign = c >> 63;
+      const u64 abs = bred_add(sign ? (u64)0 - c : c, m.t, m.bred0);
+      w = cred(sign * (m.t - abs) | (sign ^ 1) * abs, m.t);
+    } else {
+      w = bred_add(c, m.t, m.bred0);
+    }
+  }
+  pT[vec * n + j] = w;
+}
+
+// the row rotation alone (utils.RotateSliceAllocFree per row, :283-285), for the call-by-call form.  grid (ceil(2 * cols / 256), nvec).
+__global__ void __launch_bounds__(256)
+bgv_rotate_rows_kernel(const u64* __restrict__ values, u64* __restrict__ out, const u64* __restrict__ rot, unsigned cols) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= 2 * cols) return;
+  const size_t vec = blockIdx.y;
+  out[vec * 2 * cols + i] = values[vec * 2 * cols + ((i & ~(cols - 1)) | ((i + (unsigned)rot[vec]) & (cols - 1)))];
+}
+
+// The lift of rh_bgv_embed_qp: bgv_lift_kernel (has_scale, no scale_up) onto the rows of Q and of P in ONE launch -- row (vec, limb) of
+// nvec * (LQ + LP) reads its constants from the table of its own ring and writes its own block.  Per word: MRed by MForm(scale) modulo T,
+// canonical BRedAdd, MForm.  outQ: (nvec, LQ, N); outP: (nvec, LP, N).  grid (nvec * (LQ + LP), chunks).
+__global__ void __launch_bounds__(256)
+bgv_lift_qp_kernel(const u64* __restrict__ pT, u64* __restrict__ outQ, u64* __restrict__ outP, unsigned n, int logN, int loggap,
+                   const LimbConsts* __restrict__ constsQ, const LimbConsts* __restrict__ constsP, int LQ, int LP, BgvModT m, u64 s_mont,
+                   int canonical, int mont, int nt) {
+  const StreamRowQP row(blockIdx.x, constsQ, constsP, LQ, LP, logN);
+  const LimbConsts& c = row.c;
+  const u64* src = pT + (size_t)row.poly * n;
+  u64* out = (row.inQ ? outQ : outP) + row.ro;
+  auto one = [&](u64 x) -> u64 {
+    x = mred(x, s_mont, m.t, m.tinv);
+    if (canonical) x = bred_add(x, c.q, c.bred0);
+    if (mont) x = mform(x, c.q, c.bred0, c.bred1);
+    return x;
+  };
+  const unsigned mask = (1u << loggap) - 1, N = 1u << logN;
+  RH_FOR_EACH_PAIR(i, 0, N >> 1) {
+    const unsigned j = 2 * i;
+    ulonglong2 w = make_ulonglong2(0, 0);
+    if (loggap == 0) {
+      w = rh_ld2(src + j, false);
+      w.x = one(w.x); w.y = one(w.y);
+    } else if ((j & mask) == 0) {                  // gap >= 2: the odd word of a pair is never on the stride
+      w.x = one(src[j >> loggap]);
+    }
+    rh_st2(out + j, w, nt);
+  }
+}
+
 // the copy of RingT2Q alone (:364-381), for the call-by-call form of the lift.  grid (nvec * L, ceil(N / 256)).
 __global__ void __launch_bounds__(256)
 bgv_spread_kernel(const u64* __restrict__ pT, u64* __restrict__ out, unsigned n, unsigned N, int loggap, int L) {

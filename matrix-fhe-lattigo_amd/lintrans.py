@@ -15,7 +15,11 @@ The reference's lazy sums (MulCoeffsMontgomeryLazy(ThenAddLazy), AddLazy, Automo
 reads them (:220-239, :349-357, :419-427), so every value that leaves a loop is the canonical residue of the exact sum, whatever the schedule of the
 QiOverF / PiOverF reductions; both paths here keep canonical residues throughout.
 
-Not built: BGV linear transformations, conjugate-invariant and 3N rings, the big-float encoding path."""
+BGV linear transformations (circuits/bgv/lintrans) are bgv_lintrans.py: its Evaluator is the one below with the scheme's points overridden -- the
+scale of the input, the scale of the output, the rescale of EvaluateSequential and the slot count (the hooks _ks_of, _scale_in, _scale_out, _rescale
+and LinearTransformation.Slots).
+
+Not built: conjugate-invariant and 3N rings, the big-float encoding path."""
 import ctypes as C
 import math
 
@@ -169,34 +173,49 @@ class LinearTransformation:
         self.Scale, self.LogDimensions = Scale, LogDimensions
         self.IsBatched, self.IsNTT, self.IsMontgomery = True, True, True                   # (:181-191)
 
+    def Slots(self):
+        """1 << LogDimensions.Cols: the length of a row, which the rotations act on"""
+        return 1 << self.LogDimensions
+
     def BSGSIndex(self):
-        return BSGSIndex(list(self.Vec.keys()), 1 << self.LogDimensions, self.N1)
+        return BSGSIndex(list(self.Vec.keys()), self.Slots(), self.N1)
 
     def GaloisElements(self, N):
-        return GaloisElements(N, list(self.Vec.keys()), 1 << self.LogDimensions, self.LogBabyStepGiantStepRatio)
+        return GaloisElements(N, list(self.Vec.keys()), self.Slots(), self.LogBabyStepGiantStepRatio)
+
+
+def _rings_at(ringQ, ringP, levelQ, levelP):
+    """ringQP.AtLevel(levelQ, levelP) (:157) as the pair of level views"""
+    if ringP is None:
+        raise RingHipError("cannot NewTransformation: a linear transformation is encoded modulo QP and needs ringP")
+    if not (0 <= levelQ < ringQ.L and 0 <= levelP < ringP.L):
+        raise RingHipError("cannot NewTransformation: LevelQ = %d, LevelP = %d out of range" % (levelQ, levelP))
+    return ringQ.AtLevel(levelQ), ringP.AtLevel(levelP)
+
+
+def _vec_keys(diagslist, cols, logBabyStepGiantStepRatio):
+    """(:161-179) -> (N1, the keys of Vec in the order the reference allocates them)"""
+    keys = []
+    if logBabyStepGiantStepRatio < 0:
+        N1 = 0
+        for i in diagslist:
+            keys.append(i + cols if i < 0 else i)
+    else:
+        N1 = FindBestBSGSRatio(diagslist, cols, logBabyStepGiantStepRatio)
+        index, _, _ = BSGSIndex(diagslist, cols, N1)
+        for j in index:
+            for i in index[j]:
+                keys.append(j + i)
+    return N1, keys
 
 
 def NewTransformation(ringQ, ringP, ltparams):
     """NewLinearTransformation (:148-201): the diagonals allocated (not zeroed: Encode writes every one it is given) at (LevelQ, LevelP)"""
     cols = 1 << ltparams.LogDimensions
     levelQ, levelP = ltparams.LevelQ, ltparams.LevelP
-    if ringP is None:
-        raise RingHipError("cannot NewTransformation: a linear transformation is encoded modulo QP and needs ringP")
-    if not (0 <= levelQ < ringQ.L and 0 <= levelP < ringP.L):
-        raise RingHipError("cannot NewTransformation: LevelQ = %d, LevelP = %d out of range" % (levelQ, levelP))
-    rq, rp = ringQ.AtLevel(levelQ), ringP.AtLevel(levelP)
-    new = lambda: rlwe.PolyQP(DevicePoly(rq, 1, levelQ + 1), DevicePoly(rp, 1, levelP + 1))
-    vec = {}
-    if ltparams.LogBabyStepGiantStepRatio < 0:
-        N1 = 0
-        for i in ltparams.DiagonalsIndexList:
-            vec[i + cols if i < 0 else i] = new()
-    else:
-        N1 = FindBestBSGSRatio(ltparams.DiagonalsIndexList, cols, ltparams.LogBabyStepGiantStepRatio)
-        index, _, _ = BSGSIndex(ltparams.DiagonalsIndexList, cols, N1)
-        for j in index:
-            for i in index[j]:
-                vec[j + i] = new()
+    rq, rp = _rings_at(ringQ, ringP, levelQ, levelP)
+    N1, keys = _vec_keys(ltparams.DiagonalsIndexList, cols, ltparams.LogBabyStepGiantStepRatio)
+    vec = {k: rlwe.PolyQP(DevicePoly(rq, 1, levelQ + 1), DevicePoly(rp, 1, levelP + 1)) for k in keys}
     scale = ltparams.Scale if isinstance(ltparams.Scale, Scale) else Scale(ltparams.Scale)
     return LinearTransformation(ltparams.LogBabyStepGiantStepRatio, N1, levelQ, levelP, vec, scale, ltparams.LogDimensions)
 
@@ -215,7 +234,13 @@ def Encode(encoder, diagonals, allocated):
     (:246-262)"""
     if encoder.Prec() > 53:
         raise RingHipError("cannot Encode: encoder precision %d > 53 needs the *big.Float / *bignum.Complex encoder, which stays with the reference" % encoder.Prec())
-    cols = 1 << allocated.LogDimensions
+    for v, rot, idx in _encode_walk(diagonals, allocated):
+        _rotate_and_encode_diagonal(v, encoder, rot, allocated, allocated.Vec[idx])
+
+
+def _encode_walk(diagonals, allocated):
+    """the loops of Encode (:221-266) with its refusals: (values, rotation, key of Vec) per diagonal, in the reference's order"""
+    cols = allocated.Slots()
     N1 = allocated.N1
     if N1 == 0:
         for i in diagonals.DiagonalsIndexList():
@@ -226,7 +251,7 @@ def Encode(encoder, diagonals, allocated):
                 v = diagonals.At(i, cols)
             except RingHipError as e:
                 raise RingHipError("cannot Encode: %s" % e) from None
-            _rotate_and_encode_diagonal(v, encoder, 0, allocated, allocated.Vec[idx])
+            yield v, 0, idx
     else:
         index, _, _ = allocated.BSGSIndex()
         for j in index:
@@ -238,7 +263,7 @@ def Encode(encoder, diagonals, allocated):
                     v = diagonals.At(i + j, cols)
                 except RingHipError as e:
                     raise RingHipError("cannot Encode: %s" % e) from None
-                _rotate_and_encode_diagonal(v, encoder, rot, allocated, allocated.Vec[i + j])
+                yield v, rot, i + j
 
 
 def _view(p, k):
@@ -254,10 +279,7 @@ def NewTransformationFromBlock(ringQ, ringP, ltparams, encoder, index, block):
         raise RingHipError("cannot Encode: encoder precision %d > 53 needs the *big.Float / *bignum.Complex encoder, which stays with the reference" % encoder.Prec())
     cols = 1 << ltparams.LogDimensions
     levelQ, levelP = ltparams.LevelQ, ltparams.LevelP
-    if ringP is None:
-        raise RingHipError("cannot NewTransformation: a linear transformation is encoded modulo QP and needs ringP")
-    if not (0 <= levelQ < ringQ.L and 0 <= levelP < ringP.L):
-        raise RingHipError("cannot NewTransformation: LevelQ = %d, LevelP = %d out of range" % (levelQ, levelP))
+    rq, rp = _rings_at(ringQ, ringP, levelQ, levelP)
     index = [int(i) for i in index]
     if sorted(i & (cols - 1) for i in ltparams.DiagonalsIndexList) != sorted(index) or len(set(index)) != len(index):
         raise RingHipError("cannot NewTransformation: the block's rows are not the diagonals of DiagonalsIndexList")
@@ -265,7 +287,6 @@ def NewTransformationFromBlock(ringQ, ringP, ltparams, encoder, index, block):
         raise RingHipError("cannot NewTransformation: the block must be complex128 of shape (%d, %d)" % (len(index), cols))
     N1 = 0 if ltparams.LogBabyStepGiantStepRatio < 0 else FindBestBSGSRatio(index, cols, ltparams.LogBabyStepGiantStepRatio)
     scale = ltparams.Scale if isinstance(ltparams.Scale, Scale) else Scale(ltparams.Scale)
-    rq, rp = ringQ.AtLevel(levelQ), ringP.AtLevel(levelP)
     qp = rlwe.PolyQP(DevicePoly(rq, len(index), levelQ + 1), DevicePoly(rp, len(index), levelP + 1))
     lt = LinearTransformation(ltparams.LogBabyStepGiantStepRatio, N1, levelQ, levelP, {}, scale, ltparams.LogDimensions)
     encoder.Embed(block, lt, qp)
@@ -291,9 +312,23 @@ class Evaluator:
         self.ringQ, self.ringP = eval.ringQ, eval.ringP
         if self.ringQ.kind != Standard:
             raise RingHipError("cannot NewEvaluator: linear transformations on conjugate-invariant and 3N rings are not supported by the device path")
-        if eval.ks is None:
+        self.ks = self._ks_of(eval)
+        if self.ks is None:
             raise RingHipError("cannot NewEvaluator: the evaluator was built without ringP, which the key switch needs")
-        self.ks = eval.ks
+
+    # ---- the scheme's points (bgv_lintrans.Evaluator overrides them) ----------------------------------------------------------------------------
+    @staticmethod
+    def _ks_of(eval):
+        """the rlwe.Evaluator that holds the Galois keys and the key-switch buffers, None without ringP"""
+        return eval.ks
+
+    def _scale_in(self, ctIn):
+        return self.eval._scale(ctIn, "EvaluateMany")
+
+    @staticmethod
+    def _scale_out(scaleIn, lt):
+        """opOut.Scale = opOut.Scale.Mul(matrix.Scale)"""
+        return scaleIn.Mul(lt.Scale)
 
     def _use(self, fused):
         """fused: None (FUSED_LINTRANS), True / False (every kernel / none), or a dict kernel -> bool over FUSED_LINTRANS (measurements)"""
@@ -341,7 +376,7 @@ class Evaluator:
     def _keys_of(self, lt, levelP):
         """every key a transformation needs, looked up before the first launch"""
         N = self.ringQ.N
-        slots = 1 << lt.LogDimensions
+        slots = lt.Slots()
         if lt.N1 == 0:
             rots, who = [k & (slots - 1) for k in sorted(lt.Vec) if k != 0], "MultiplyByDiagMatrix"
         else:
@@ -426,7 +461,7 @@ class Evaluator:
         for c in (0, 1):
             rq.CopyLvl(ctIn.Value[c], ct.Value[c])
         meta = {name: getattr(ctIn, name) for name in rlwe.METADATA if hasattr(ctIn, name)}
-        scaleIn = self.eval._scale(ctIn, "EvaluateMany")
+        scaleIn = self._scale_in(ctIn)
         dec = self._dec(levelQ, levelP, npoly)
         self.ks.DecomposeNTT(levelQ, levelP, ct.Value[1], True, dec)                                   # (:43)
         ctPreRot = {}
@@ -445,7 +480,7 @@ class Evaluator:
             for name, v in meta.items():                                                               # *opOut.MetaData = *ctIn.MetaData
                 setattr(out, name, v)
             out.IsNTT = True
-            out.Scale = scaleIn.Mul(lt.Scale)                                                          # opOut.Scale = opOut.Scale.Mul(matrix.Scale)
+            out.Scale = self._scale_out(scaleIn, lt)
 
     def PreRotatedCiphertextForDiagonalMatrixMultiplication(self, levelQ, levelP, ctIn, BuffDecompQP, rots, ctPreRot):
         """(:71-99): ctPreRot[i] = AutomorphismHoistedLazy(ctIn, 5^i) for every i of rots that is not there yet (0 excepted); entries that are not
@@ -478,7 +513,7 @@ class Evaluator:
         npoly = ctIn.Value[0].npoly
         rq, rp = self.ringQ.AtLevel(levelQ), self.ringP.AtLevel(levelP)
         N = self.ringQ.N
-        slots = 1 << matrix.LogDimensions
+        slots = matrix.Slots()
         keys = sorted(matrix.Vec)
         state = bool(keys) and keys[0] == 0
         if state:

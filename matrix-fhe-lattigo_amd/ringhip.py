@@ -179,6 +179,7 @@ def lib():
         "rh_bgv_encode": (i, [vp, vp, i, C.c_uint64, vp, i, i, i, vp, i, i, i, i]), "rh_bgv_decode": (i, [vp, i, C.c_uint64, vp, i, vp, i, i, i, i]),
         "rh_bgv_encode_ring_t": (i, [vp, C.c_uint64, vp, i, i, i, vp]), "rh_bgv_decode_ring_t": (i, [vp, C.c_uint64, vp, i, vp, i, i]),
         "rh_bgv_ring_t2q": (i, [vp, vp, i, i, vp, vp, i]), "rh_bgv_ring_q2t": (i, [vp, i, vp, vp, i]),
+        "rh_bgv_embed_qp": (i, [vp, vp, i, i, C.c_uint64, vp, i, i, i, C.POINTER(C.c_int), i, vp, vp, i, i]),
         "rh_sample_uniform": (i, [vp, i, U64P, C.c_uint64, C.c_uint64, C.c_uint64, vp, i, i]),
         "rh_sample_gaussian": (i, [vp, U64P, C.c_uint64, C.c_uint64, vp, i, vp, i]),
         "rh_sample_ternary": (i, [vp, U64P, C.c_uint64, C.c_uint64, C.c_uint64, vp, i]),
