@@ -4,7 +4,7 @@ ARCH  ?= gfx950
 PKG   := matrix-fhe-lattigo_amd
 CSRC  := $(PKG)/csrc
 LIB   := $(PKG)/lib/libringhip.so
-SRCS  := $(CSRC)/engine.hip $(CSRC)/ntt3n.hip $(CSRC)/bext.hip $(CSRC)/rescale.hip $(CSRC)/keyswitch.hip $(CSRC)/kshard.hip $(CSRC)/automorphism.hip $(CSRC)/inner_sum.hip $(CSRC)/ring_packing.hip $(CSRC)/lintrans.hip $(CSRC)/bfv.hip $(CSRC)/bgv.hip $(CSRC)/ckks.hip $(CSRC)/ckks_encoder.hip $(CSRC)/dft.hip $(CSRC)/bootstrap.hip $(CSRC)/bgv_encoder.hip $(CSRC)/blindrot.hip $(CSRC)/keygen.hip $(CSRC)/multiparty.hip $(CSRC)/mp_refresh.hip $(CSRC)/matrix_ckks.hip
+SRCS  := $(CSRC)/engine.hip $(CSRC)/ntt3n.hip $(CSRC)/bext.hip $(CSRC)/rescale.hip $(CSRC)/keyswitch.hip $(CSRC)/kshard.hip $(CSRC)/automorphism.hip $(CSRC)/inner_sum.hip $(CSRC)/ring_packing.hip $(CSRC)/lintrans.hip $(CSRC)/bfv.hip $(CSRC)/bgv.hip $(CSRC)/ckks.hip $(CSRC)/ckks_encoder.hip $(CSRC)/dft.hip $(CSRC)/bootstrap.hip $(CSRC)/bgv_encoder.hip $(CSRC)/blindrot.hip $(CSRC)/keygen.hip $(CSRC)/multiparty.hip $(CSRC)/mp_refresh.hip $(CSRC)/matrix_ckks.hip $(CSRC)/noise.hip
 HDRS  := $(wildcard $(CSRC)/*.hip.hpp) $(wildcard $(CSRC)/*.inc) $(wildcard $(CSRC)/*.hpp) $(wildcard include/*.h)
 
 ROCM ?= /opt/rocm

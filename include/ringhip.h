@@ -1011,6 +1011,49 @@ int rh_mp_big_muldiv(rh_ring* r, const uint64_t* blk_dev, uint64_t* out_dev, int
 int rh_mp_refresh_recode(rh_ring* ringIn, int levelIn, const uint64_t* in_dev, int in_rows, const uint64_t* blk_dev, int n, int W, rh_ring* ringOut,
                          int levelOut, uint64_t* out_dev, int npoly, const uint64_t* m, int mwords, const uint64_t* d, int dwords, int accumulate);
 
+/* ---- the noise meters (csrc/noise.hip; ring.Log2OfStandardDeviation, core/rlwe/utils.go of the reference) ------------------------------------
+ *   rh_ring_centered_moments  the exact integers PolyToBigintCentered(p, gap, .) (ring/ring.go:503-543, ring/ringqp) would give, summed: for every
+ *                          poly of a COEFFICIENT-domain block, over limbs 0..levelQ of ringQ and, with ringP, limbs 0..levelP of ringP as one RNS
+ *                          basis m_0 .. m_{L-1} (Q first) of product M: v = CRT(residues of coefficient i gap) in [0, M), x = v - M when
+ *                          v >= floor(M / 2) (note the >=), for the n = N / gap coefficients 0, gap, 2 gap ...  Any residues: words >= m_i are
+ *                          reduced first.  Every ring kind; N need not be a power of two.  q: row (poly, limb) at (poly * q_rows + limb) * N
+ *                          words, p likewise; ringP NULL: Q alone (p NULL, levelP and p_rows not read).
+ *                          out: rh_ring_centered_moments_words(L) words per poly, L = levelQ + 1 [+ levelP + 1], all integers, no float anywhere.
+ *                          With the mixed-radix digits d_0 .. d_{L-1} of v (v = sum_i R_i d_i, R_i = m_0 ... m_{i-1}, 0 <= d_i < m_i) and two
+ *                          more rows d_L = 1, d_{L+1} = c (1 on the lanes where M was subtracted), the block holds
+ *                            P_ij = sum over the n lanes of d_i d_j, 0 <= i <= j <= L + 1, three little-endian words each (192 bits), pair (i, j)
+ *                                   at 3 (i (L + 2) - i (i - 1) / 2 + j - i): the upper triangle, row-major;
+ *                            then the L digits of the smallest |x| and the L digits of the largest |x| (|x| = sum_i R_i digit_i).
+ *                          So  sum c = P_{L,L+1},  sum v = sum_i R_i P_{i,L},  sum x = sum v - M sum c,
+ *                              sum x^2 = sum_{i <= j < L} (2 - [i = j]) R_i R_j P_ij - 2 M sum_i R_i P_{i,L+1} + M^2 sum c.
+ *                          (P_{L,L} counts the lanes of whole chunks, not n.)  The sums are exact whatever the launch geometry.
+ *                          Scratch (tables, per-workgroup partials) belongs to ringQ's handle, as the rescale and AtLevel scratch does, and
+ *                          every call rewrites it in stream order: calls on one handle must go to ONE stream.  Two host threads that drive
+ *                          the same handle on different streams would overwrite each other's tables under a running kernel; give each such
+ *                          thread a handle of its own.  The handle's lock serialises the host side alone.  Enqueued on ringQ's stream.
+ *                          RH_ERR_UNSUPPORTED: more than 64 moduli over Q and P together.  RH_ERR_ARG: gap does not divide N; the two handles
+ *                          are on different streams (rh_ring_set_stream); a modulus of 2^61 or more; the moduli are not pairwise distinct.
+ *   rh_rlwe_gadget_phase   NoiseGadgetCiphertext (core/rlwe/utils.go:51-102) up to its INTT for many gadget ciphertexts in one launch that reads
+ *                          every row once.  Output poly o names one key and one power-of-two index j < min_i len(Value[i]):
+ *                            out[o] = sum over the key's RNS digits i of (Value[i][j][0] + Value[i][j][1] * sk[sk_o])  on the limbs of Q and of P,
+ *                                     - pt[pt_o] * s_o  on the limbs of Q,  s_o = MForm(P 2^(j pw2)) per limb (MForm(2^(j pw2)) without P)
+ *                          NTT domain, Montgomery form in and out, canonical residues: the words the reference's MulCoeffsMontgomeryThenAdd,
+ *                          Add, MulScalarBigint, MulScalar and Sub leave in Value[0][j][0].  The digit sum is kept lazily and reduced once per
+ *                          row.  A public key (NoisePublicKey, :13-25) is one row without a plaintext.
+ *                          Key tables: (rows, 2, limbs, N) as rh_rlwe_gadget_encrypt writes them, one for Q and one for P, anywhere on the
+ *                          device.  sk: (nsk, limbs, N) for Q and for P; pt: (npt, levelQ + 1, N).  out: (outs, limbs, N) for Q and for P.
+ *                          rowtab (HOST): outs x (6 + max_terms + levelQ + 1) words: the address of the key's Q table, of its P table (0
+ *                          without P), the rows the key has, sk_o, pt_o (all ones: no plaintext), the term count m_o <= max_terms, max_terms row
+ *                          numbers (the first m_o are read: the rows of Value[i][j], i = 0 ..), then s_o per limb of Q.  table_dev: device scratch
+ *                          of rh_rlwe_gadget_phase_table_words(levelQ, outs, max_terms) words.  ringP NULL: no P (skP, outP NULL).
+ *                          Standard rings and 3N rings; conjugate-invariant rings are refused. */
+size_t rh_ring_centered_moments_words(int limbs);
+int rh_ring_centered_moments(rh_ring* ringQ, int levelQ, const uint64_t* q_dev, int q_rows, rh_ring* ringP, int levelP, const uint64_t* p_dev, int p_rows,
+                             int gap, int npoly, uint64_t* out_dev);
+size_t rh_rlwe_gadget_phase_table_words(int levelQ, int outs, int max_terms);
+int rh_rlwe_gadget_phase(rh_ring* ringQ, rh_ring* ringP, int levelQ, int levelP, const uint64_t* skQ, const uint64_t* skP, int nsk, const uint64_t* ptQ, int npt,
+                         uint64_t* outQ, uint64_t* outP, const uint64_t* rowtab, int outs, int max_terms, uint64_t* table_dev, size_t table_words);
+
 #ifdef __cplusplus
 }
 #endif

@@ -276,6 +276,13 @@ class Ring {
   // MForm + MulCoeffsMontgomery + INTT as one call (schemes/ckks/evaluator.go:821-834 + INTT)
   void INTTMul(const Poly& a, const Poly& b, Poly& out) const { check(rh_ring_intt_mul(h_.get(), a.data(), b.data(), out.data(), a.npoly(), level_)); }
 
+  // The exact sums behind Log2OfStandardDeviation (ring/ring.go:647-686) of every poly of a coefficient-domain block, modulo Q (this ring) or, with
+  // ringP, modulo QP: rh_ring_centered_moments_words(limbs) words per poly into `out` (device), laid out as ringhip.h documents
+  void CenteredMoments(const Poly& q, uint64_t* out, int gap = 1, const Ring* ringP = nullptr, const Poly* p = nullptr) const {
+    check(rh_ring_centered_moments(h_.get(), level_, q.data(), q.limbs(), ringP ? ringP->handle() : nullptr, ringP ? ringP->level_ : 0,
+                                   p ? p->data() : nullptr, p ? p->limbs() : 0, gap, q.npoly(), out));
+  }
+
   std::vector<SubRing> SubRings;
  private:
   template <class F> void hostPoly(F f, const std::vector<const uint64_t*>& p1, const std::vector<uint64_t*>& p2, int lazy) const {

@@ -25,3 +25,5 @@ from . import comparison  # noqa: F401,E402
 from . import inverse  # noqa: F401,E402
 from . import multiparty  # noqa: F401,E402
 from . import matrix_ckks  # noqa: F401,E402
+from . import noise  # noqa: F401,E402
+from . import precision  # noqa: F401,E402

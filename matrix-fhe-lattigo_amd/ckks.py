@@ -1123,3 +1123,7 @@ class Decryptor(rlwe.Decryptor):
         pt = Plaintext(poly, ct.Scale, ct.LogDimensions, ct.IsNTT, getattr(ct, "IsMontgomery", False), getattr(ct, "IsBatched", True))
         self.Decrypt(ct, pt, fused)
         return pt
+
+
+# ---- ckks.GetPrecisionStats (schemes/ckks/precision.go): host statistics over the device Decode (precision.py) -------------------------------------------
+from .precision import GetPrecisionStats, PrecisionStats, Stats  # noqa: E402,F401

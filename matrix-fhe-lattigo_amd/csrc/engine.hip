@@ -252,6 +252,7 @@ extern "C" void rh_ring_destroy(rh_ring* r) {
   rh_rescale_teardown(r);
   for (int i = 0; i < 2; ++i) if (r->d_rs[i]) (void)hipFree(r->d_rs[i]);
   if (r->d_rows) (void)hipFree(r->d_rows);
+  if (r->d_noise) (void)hipFree(r->d_noise);
   rh_ring3n_teardown(r);
   delete r;
 }

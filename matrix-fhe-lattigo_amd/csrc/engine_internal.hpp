@@ -62,6 +62,7 @@ struct rh_ring {
   std::vector<void*> rescale_tables;      // per level, rescale.hip
   u64* d_rs[2] = {nullptr, nullptr}; size_t rs_words[2] = {0, 0};
   u64* d_rows = nullptr; size_t rows_words = 0;   // dense scratch of the rows-per-poly transforms that compact / expand (engine.hip: ntt_rows)
+  u64* d_noise = nullptr; size_t noise_words = 0; // tables and per-workgroup partials of rh_ring_centered_moments (noise.hip)
   std::atomic<long> stats_rows_direct{0}, stats_rows_compacted{0};   // rh_ring_stats: how the rows-per-poly calls were served
   int fuse_submul = 1;            // ModDown / rescale: subtract-multiply fused into the forward tile kernel's epilogue
   int fuse_ci = 1;                // conjugate-invariant ring: the fold inside the column stages (N = 2^14 .. 2^16)

@@ -14,6 +14,7 @@ its wrapping 64-bit sum of NTTLazy digits times Montgomery-form key rows never o
 of the same sum (tests/test_blindrot_oracle.py restates the literal loop against the Montgomery branch)."""
 from .ringhip import RingHipError
 from .rlwe import ElementQP, Evaluator as RLWEEvaluator, GadgetCiphertext
+from .noise import NoiseRGSWCiphertext  # noqa: F401  (core/rgsw/utils.go)
 
 
 class Ciphertext:

@@ -199,6 +199,9 @@ def lib():
         "rh_mp_big_sample": (i, [vp, U64P, C.c_uint64, C.c_uint64, i, vp, i, i, i]), "rh_mp_big_to_rns": (i, [vp, i, vp, i, i, vp, i, i]),
         "rh_mp_big_from_rns": (i, [vp, i, vp, i, vp, i, i, i, i]), "rh_mp_big_muldiv": (i, [vp, vp, vp, i, i, i, U64P, i, U64P, i]),
         "rh_mp_refresh_recode": (i, [vp, i, vp, i, vp, i, i, vp, i, vp, i, U64P, i, U64P, i, i]),
+        "rh_ring_centered_moments_words": (sz, [i]), "rh_ring_centered_moments": (i, [vp, i, vp, i, vp, i, vp, i, i, i, vp]),
+        "rh_rlwe_gadget_phase_table_words": (sz, [i, i, i]),
+        "rh_rlwe_gadget_phase": (i, [vp, vp, i, i, vp, vp, i, vp, i, vp, vp, U64P, i, i, vp, sz]),
         "rh_kshard_create": (i, [C.POINTER(vp), vp, vp, U64P, i, U64P, i, C.POINTER(i), i, C.POINTER(i), i]),
         "rh_kshard_destroy": (None, [vp]), "rh_kshard_num_digits": (i, [vp]),
         "rh_kshard_digit_range": (i, [vp, i, C.POINTER(i), C.POINTER(i)]),
@@ -802,6 +805,17 @@ class Ring:
         mods, Q, crt = self._crt()
         half = Q >> 1
         return [v - Q if v >= half else v for v in self.PolyToBigint(p1, gap, poly)]
+
+    def CenteredMoments(self, p, gap=1, fused=None):
+        """per poly of a coefficient-domain batch: (n, sum x, sum x^2, min |x|, max |x|) over the values PolyToBigintCentered(p, gap, .) gives
+        (:503-543), as Python integers: rh_ring_centered_moments, exact at any number of limbs (noise.py)"""
+        from .noise import centered_moments
+        return centered_moments(self, p, gap=gap, fused=fused)
+
+    def Log2OfStandardDeviation(self, p, fused=None):
+        """:647-686: base-2 logarithm of the standard deviation (divisor N - 1) of the centred coefficients, one float per poly of the batch"""
+        from .noise import log2_of_standard_deviation
+        return log2_of_standard_deviation(self, p, fused=fused)
 
     def Equal(self, p1, p2):
         """:546-558: Reduce both operands IN PLACE (as the reference does), then compare limbs 0..level"""

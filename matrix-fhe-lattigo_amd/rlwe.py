@@ -1326,3 +1326,8 @@ from .sampling import (  # noqa: E402,F401
 from .keygen import (  # noqa: E402,F401
     SecretKey, PublicKey, EvaluationKey, RelinearizationKey, GaloisKey, MemEvaluationKeySet, KeyGenerator, Encryptor, Decryptor, Plaintext,
 )
+# ---- the noise meters: ring.Log2OfStandardDeviation and core/rlwe/utils.go:13-183 (noise.py) ----------------------------------------------------------
+from .noise import (  # noqa: E402,F401
+    FUSED_NOISE, NoisePublicKey, NoiseRelinearizationKey, NoiseGaloisKey, NoiseGaloisKeys, NoiseGadgetCiphertext, NoiseEvaluationKey, Norm, NormStats,
+    CenteredMomentsQP, Log2OfStandardDeviationQP,
+)
