@@ -251,6 +251,14 @@ int rh_ring_unfold_ci_to_standard(rh_ring* r, int level, const uint64_t* ci_dev,
 int rh_ring_fold_standard_to_ci(rh_ring* r, int level, const uint64_t* std_dev, const uint64_t* index_dev, uint64_t* ci_dev, int npoly);
 int rh_ring_pad_default_to_ci(rh_ring* r, int level, const uint64_t* std_dev, int is_ntt, uint64_t* ci_dev, int npoly);
 
+/* The tail of DomainSwitcher.ComplexToReal (schemes/ckks/bridge.go:79-83) as one launch over both components of a batch: the Add of the
+ * gadget product's first output g0 with c0 over rows of 2n words and the two FoldStandardToConjugateInvariant calls,
+ *   out0[j] = CRed(CRed(g0[index[j]] + c0[index[j]]) + CRed(g0[j] + c0[j])),  out1[j] = CRed(g1[index[j]] + g1[j]),  j < n.
+ * r: a ring of degree n with the level's moduli (the conjugate-invariant ring); g0, g1, c0: (npoly, level+1, 2n) canonical words; out0, out1:
+ * (npoly, level+1, n), disjoint from the inputs; index_dev as for rh_ring_fold_standard_to_ci.  The words of the composed calls. */
+int rh_ckks_bridge_fold_tail(rh_ring* r, int level, const uint64_t* g0_dev, const uint64_t* g1_dev, const uint64_t* c0_dev,
+                             const uint64_t* index_dev, uint64_t* out0_dev, uint64_t* out1_dev, int npoly);
+
 /* ---- RNS rescale (ring/scaling.go): divide by the last modulus, `nb` times.  round = 0: floored, 1: rounded.
  * p0: npoly polys of level+1 limbs; p1: npoly polys of p1_rows >= level+1-nb limbs (limbs 0..level-nb are written).
  *   rh_ring_div_by_last_modulus_many      coefficient domain: DivFloorByLastModulus(:21-28) / DivRoundByLastModulus
@@ -743,7 +751,15 @@ int rh_ckks_double_angle(rh_ring* r, int level, uint64_t* c0_dev, uint64_t* c1_d
  *                            Level 0 and the ring's top level only: polyToFloatCRT reconstructs over the encoder's FULL ring, so at a
  *                            level in between the reference's result depends on stale limbs of its buffer -- RH_ERR_UNSUPPORTED. */
 typedef struct rh_ckks_encoder rh_ckks_encoder;
+/* Conjugate-invariant rings: rh_ckks_encoder_create keeps refusing them, in the words it always had; the real-only encoder is the entry
+ * of its own below (the Python constructor ckks.Encoder refuses such a ring with the same text unless ckks.NewEncoder(params) passes the
+ * permit).  rh_ckks_encoder_create_real: ring of degree n and kind RH_RING_CI, roots: the NthRoot + 1 = 4n + 1 entries; rotGroup is
+ * 5^j mod 4n for j < n and log_slots runs up to log2 n (n real slots).  Every other entry takes the handle as it takes a standard one:
+ * rh_ckks_encode reads the real parts alone (encoder.go:225-228; utils.go:145-147) and spreads at stride n / slots before the ring's own
+ * transform; rh_ckks_decode gathers `slots` coefficients and sets imag[i] = 0 - real[slots - i] before the special FFT (the `isreal`
+ * arms of polyToComplexNoCRT / polyToComplexCRT). */
 int rh_ckks_encoder_create(rh_ckks_encoder** out, rh_ring* ring, const double* roots, size_t nroots, unsigned prec);
+int rh_ckks_encoder_create_real(rh_ckks_encoder** out, rh_ring* ring, const double* roots, size_t nroots, unsigned prec);
 void rh_ckks_encoder_destroy(rh_ckks_encoder* e);
 int rh_ckks_encoder_reserve(rh_ckks_encoder* e, int nvec);
 int rh_ckks_encoder_set_tuning(rh_ckks_encoder* e, const char* key, long value);

@@ -267,6 +267,10 @@ class Ring {
   void PadDefaultRingToConjugateInvariant(const Poly& std_, bool isNTT, Poly& ci) const {
     check(rh_ring_pad_default_to_ci(h_.get(), level_, std_.data(), isNTT ? 1 : 0, ci.data(), std_.npoly()));
   }
+  // the tail of ckks.DomainSwitcher.ComplexToReal (schemes/ckks/bridge.go:79-83) in one launch; receiver: the conjugate-invariant ring of degree n
+  void BridgeFoldTail(const Poly& g0, const Poly& g1, const Poly& c0, const Poly& index, Poly& out0, Poly& out1) const {
+    check(rh_ckks_bridge_fold_tail(h_.get(), level_, g0.data(), g1.data(), c0.data(), index.data(), out0.data(), out1.data(), g0.npoly()));
+  }
   void Shift(const Poly& p1, int k, Poly& p2) const { check(rh_ring_shift(h_.get(), level_, p1.data(), p2.data(), k, p1.npoly())); }
   void MultByMonomial(const Poly& p1, int k, Poly& p2) const { check(rh_ring_mult_by_monomial(h_.get(), level_, p1.data(), p2.data(), k, p1.npoly())); }
   void MulByVectorMontgomery(const Poly& p1, const Poly& vector, Poly& p2, bool thenAddLazy = false) const {

@@ -16,7 +16,7 @@ from fractions import Fraction
 
 import numpy as np
 
-from .ringhip import ConjugateInvariant, DevicePoly, RingHipError, _check, _p, _u64, lib
+from .ringhip import AutomorphismNTTIndex, ConjugateInvariant, DevicePoly, Ring, RingHipError, Standard, _check, _p, _u64, lib
 from .schemes import Ciphertext, MatrixCKKSEvaluator
 from . import rlwe
 
@@ -917,10 +917,14 @@ class Plaintext(Ciphertext):
 
 class Encoder:
     """ckks.Encoder on device batches: Encode / Decode / DecodePublic / Embed / FFT / IFFT of nvec vectors at once (csrc/ckks_encoder.hip).
-    Refused by name: conjugate-invariant and 3N rings, precision > 53 (the *big.Float / *bignum.Complex path), Decode with IsBatched = false
-    at a level that is neither 0 nor the ring's top level."""
+    Refused by name: 3N rings, precision > 53 (the *big.Float / *bignum.Complex path), Decode with IsBatched = false at a level that is
+    neither 0 nor the ring's top level.
+    Conjugate-invariant rings: the real-only embedding (m = 4N roots, up to N real slots; Embed drops the imaginary parts, Decode returns what
+    the reference's `isreal` arms and its FFT leave in them), behind the permit conjugate_invariant=True that ckks.NewEncoder(params) sets
+    (sampling.rings_ok says why a permit); without it the constructor refuses such a ring in the words of rh_ckks_encoder_create.  On such
+    a ring Embed into a PolyQP (ringP) is refused by name."""
 
-    def __init__(self, ringQ, precision=53, roots=None, ringP=None):
+    def __init__(self, ringQ, precision=53, roots=None, ringP=None, conjugate_invariant=False):
         """ringP: the key-switch ring, for Embed into an rlwe.PolyQP (the ringqp.Poly arm of embedDouble, encoder.go:304-311: the diagonals of a
         linear transformation); None (default): a PolyQP is refused by name"""
         import ctypes as C
@@ -928,10 +932,14 @@ class Encoder:
         self._h = self._hP = None
         if self.prec < 0:
             raise RingHipError("cannot NewEncoder: negative precision")
-        self.m = 2 * ringQ.N
+        self.real = ringQ.kind == ConjugateInvariant and bool(conjugate_invariant)
+        if self.real and ringP is not None:
+            raise RingHipError("cannot NewEncoder: Embed into a ringqp.Poly (ringP) is built on standard rings only, not on conjugate-invariant rings")
+        self.m = (4 if self.real else 2) * ringQ.N
         r = np.ascontiguousarray(GetRootsComplex128(self.m) if roots is None else roots, dtype=np.float64)
         h = C.c_void_p()
-        _check(lib().rh_ckks_encoder_create(C.byref(h), ringQ._h, r.ctypes.data_as(C.POINTER(C.c_double)), r.size // 2, self.prec))
+        create = lib().rh_ckks_encoder_create_real if self.real else lib().rh_ckks_encoder_create      # the latter refuses a conjugate-invariant ring
+        _check(create(C.byref(h), ringQ._h, r.ctypes.data_as(C.POINTER(C.c_double)), r.size // 2, self.prec))
         self._h = h
         if ringP is not None:                                      # the same quantizer and transform over the P moduli
             if ringP.N != ringQ.N or ringP.kind != ringQ.kind:
@@ -939,7 +947,7 @@ class Encoder:
             hP = C.c_void_p()
             _check(lib().rh_ckks_encoder_create(C.byref(hP), ringP._h, r.ctypes.data_as(C.POINTER(C.c_double)), r.size // 2, self.prec))
             self._hP = hP
-        self.LogMaxSlots = ringQ.N.bit_length() - 2
+        self.LogMaxSlots = ringQ.N.bit_length() - (1 if self.real else 2)
         import threading
         self._tls = threading.local()      # per host thread: the upload blocks host values go through, kept so that no call frees device memory
 
@@ -985,7 +993,7 @@ class Encoder:
             a = np.broadcast_to(a, (nvec, a.shape[0]))
         if a.ndim != 2 or a.shape[0] != nvec:
             raise RingHipError("cannot %s: %d vectors given for a block of %d polys" % (who, a.shape[0] if a.ndim == 2 else -1, nvec))
-        maxCols = self.ringQ.N >> 1
+        maxCols = 1 << self.LogMaxSlots
         if a.shape[1] > maxCols or a.shape[1] > slots:
             raise RingHipError("cannot %s: ensure that #values (%d) <= slots (%d) <= maxCols (%d)" % (who, a.shape[1], slots, maxCols))
         full = np.zeros((nvec, slots), dtype=np.complex128)                      # zeroes all other values (:292-295)
@@ -1123,6 +1131,271 @@ class Decryptor(rlwe.Decryptor):
         pt = Plaintext(poly, ct.Scale, ct.LogDimensions, ct.IsNTT, getattr(ct, "IsMontgomery", False), getattr(ct, "IsBatched", True))
         self.Decrypt(ct, pt, fused)
         return pt
+
+
+# ---- ckks.Parameters (schemes/ckks/params.go) and the constructors that take them (schemes/ckks/ckks.go) ---------------------------------------
+class Parameters:
+    """ckks.Parameters with explicit moduli (no prime generation): ringQ / ringP = Ring(2^LogN, ., kind=RingType).  RingType: Standard or
+    ConjugateInvariant; Xs: ("P", density) or ("H", weight); Xe: (sigma, bound).  The New* factories below are how a conjugate-invariant ring
+    reaches the key layer and the encoder: they pass the permit conjugate_invariant=True (sampling.rings_ok)."""
+
+    def __init__(self, LogN, Q, P, LogDefaultScale, RingType=Standard, Xs=("P", 2 / 3), Xe=(3.2, 19), device=0):
+        if RingType not in (Standard, ConjugateInvariant):
+            raise RingHipError("cannot NewParameters: RingType must be Standard or ConjugateInvariant")
+        self.logN, self.ringType, self.device = int(LogN), RingType, device
+        self.Q, self.P = [int(q) for q in Q], [int(p) for p in (P or [])]
+        nth = self.NthRoot()
+        for q in self.Q + self.P:
+            if q % nth != 1:
+                raise RingHipError("cannot NewParameters: modulus %d is not 1 mod NthRoot = %d" % (q, nth))
+        n = 1 << self.logN
+        self.ringQ = Ring(n, self.Q, kind=RingType, device=device)
+        self.ringP = Ring(n, self.P, kind=RingType, device=device) if self.P else None
+        self.logDefaultScale = int(LogDefaultScale)
+        self.scale = Scale(1 << self.logDefaultScale)
+        self.xs, self.xe = tuple(Xs), tuple(Xe)
+
+    def N(self): return 1 << self.logN
+    def LogN(self): return self.logN
+    def MaxLevel(self): return len(self.Q) - 1
+    def MaxLevelQ(self): return len(self.Q) - 1
+    def MaxLevelP(self): return len(self.P) - 1
+    def RingQ(self): return self.ringQ
+    def RingP(self): return self.ringP
+    def RingType(self): return self.ringType
+    def NthRoot(self): return (4 if self.ringType == ConjugateInvariant else 2) << self.logN       # ring/ring.go:178-183
+    def DefaultScale(self): return self.scale
+    def LogDefaultScale(self): return self.logDefaultScale
+    def LogMaxSlots(self): return self.logN if self.ringType == ConjugateInvariant else self.logN - 1
+    def MaxSlots(self): return 1 << self.LogMaxSlots()                                # params.go:138-177: Cols = N, or N / 2 on a standard ring
+    def LogMaxDimensions(self): return (0, self.LogMaxSlots())                        # ring.Dimensions{Rows, Cols}
+    def MaxDimensions(self): return (1, self.MaxSlots())
+    def GaloisElement(self, k): return GaloisElement(self.N(), k, self.NthRoot())
+    def EncodingPrecision(self): return max(53, self.logDefaultScale)                 # params.go:187-195
+    def Xs(self): return self.xs
+    def Xe(self): return self.xe
+    def _ci(self): return self.ringType == ConjugateInvariant
+
+    def StandardParameters(self, P=None):
+        """params.go:103-113 over core/rlwe/params.go StandardParameters: the receiver when it is standard; else the standard parameters of
+        twice the degree (the same NthRoot) with the same Q and P.  P=...: other auxiliary moduli for the standard side."""
+        if self.ringType == Standard and P is None:
+            return self
+        logN = self.logN + (1 if self.ringType == ConjugateInvariant else 0)
+        return Parameters(logN, self.Q, self.P if P is None else P, self.logDefaultScale, Standard, self.xs, self.xe, self.device)
+
+    def close(self):
+        for r in (self.ringQ, self.ringP):
+            if r is not None:
+                r.close()
+
+
+def NewKeyGenerator(params, prng=None):
+    return rlwe.KeyGenerator(params.RingQ(), params.RingP(), params.Xs(), params.Xe(), prng, conjugate_invariant=params._ci())
+
+
+def NewEncoder(params, precision=None, roots=None):
+    """ckks.NewEncoder: precision None is Parameters.EncodingPrecision()"""
+    return Encoder(params.RingQ(), params.EncodingPrecision() if precision is None else precision, roots,
+                   None if params._ci() else params.RingP(), conjugate_invariant=params._ci())
+
+
+def NewEncryptor(params, key, prng=None):
+    return Encryptor(params.RingQ(), params.RingP(), key, prng, params.Xs(), params.Xe(), conjugate_invariant=params._ci())
+
+
+def NewDecryptor(params, sk):
+    return Decryptor(params.RingQ(), sk, conjugate_invariant=params._ci())
+
+
+def NewEvaluator(params, evk=None, **kw):
+    """evk: a MemEvaluationKeySet (or None)"""
+    gks = dict(evk.GaloisKeys) if evk is not None else None
+    return Evaluator(params.RingQ(), params.RingP(), rlk=evk.RelinearizationKey if evk is not None else None, galois_keys=gks,
+                     encoding_precision=params.EncodingPrecision(), **kw)
+
+
+def NewPlaintext(params, level, nvec=1, log_slots=None, is_ntt=True):
+    """ckks.NewPlaintext (ckks.go): the default scale and the maximum dimensions"""
+    return Plaintext(params.RingQ().AtLevel(level).NewPoly(nvec), params.DefaultScale(), params.LogMaxSlots() if log_slots is None else log_slots, is_ntt)
+
+
+def NewCiphertext(params, degree, level, nvec=1, is_ntt=True):
+    rq = params.RingQ().AtLevel(level)
+    ct = Ciphertext([rq.NewPoly(nvec) for _ in range(degree + 1)], is_ntt=is_ntt)
+    ct.Scale, ct.LogDimensions, ct.IsBatched, ct.IsMontgomery = params.DefaultScale(), params.LogMaxSlots(), True, False
+    return ct
+
+
+# ---- ckks.DomainSwitcher (schemes/ckks/bridge.go) ---------------------------------------------------------------------------------------------------
+# "fold_tail": the tail of ComplexToReal -- rh_ckks_bridge_fold_tail (True) or the reference's Add and two FoldStandardToConjugateInvariant
+# calls (False); "unfold_then_add": RealToComplex -- GadgetProductThenAdd with the unfolded c0 as addend (True) or GadgetProduct, Add, CopyLvl
+# (False; also what keys with at most one modulus of P and coefficient-domain ciphertexts take).  The same bits.  profiles/ci_ckks.json
+# (n = 2^16, 25 + 5 limbs, call rates): the tail alone 1.84x (batch 1) and 1.53x (batch 8) faster in one launch, a whole ComplexToReal 1.9 % and
+# 2.3 %, a whole RealToComplex 0.6 % and 4.0 %, each outside the spread of its windows: both default to the fused side.
+FUSED_BRIDGE = {"fold_tail": True, "unfold_then_add": True}
+
+
+class DomainSwitcher:
+    """ckks.DomainSwitcher on batches of ciphertexts: ComplexToReal / RealToComplex between the standard ring of degree 2n and the
+    conjugate-invariant ring of degree n.  params: parameters of either type (its RingQ's degree and moduli fix both rings); the keys are
+    those of KeyGenerator.GenEvaluationKeysForRingSwapNew.  The level is min(ctIn.Level(), opOut.Level()): a ctIn above it is read at that
+    level; an opOut above it is refused by name (a device batch cannot be resized)."""
+
+    def __init__(self, params, complexToRealEvk=None, realToComplexEvk=None):
+        self.stdToci, self.ciToStd = complexToRealEvk, realToComplexEvk
+        rq = params.RingQ()
+        ci = params.RingType() == ConjugateInvariant
+        n = rq.N if ci else rq.N // 2
+        self._own = []
+        mods = [int(q) for q in rq.moduli]
+        for q in mods:
+            if q % (4 * n) != 1:
+                raise RingHipError("cannot NewDomainSwitcher because the standard NTT is undefined for params: modulus %d is not 1 mod %d" % (q, 4 * n))
+        if ci:
+            self.conjugateRingQ = rq
+            self.stdRingQ = Ring(2 * n, mods, kind=Standard, device=params.device)
+            self._own.append(self.stdRingQ)
+        else:
+            self.stdRingQ = rq
+            self.conjugateRingQ = Ring(n, mods, kind=ConjugateInvariant, device=params.device)
+            self._own.append(self.conjugateRingQ)
+        N = self.stdRingQ.N
+        self.automorphismIndex = AutomorphismNTTIndex(N, 2 * N, 2 * N - 1)
+        self._index = DevicePoly.from_numpy(self.conjugateRingQ.AtLevel(0), _u64(self.automorphismIndex).reshape(-1)[:n].reshape(1, 1, n))
+        self._pool = {}
+        self._ks_own = None
+
+    def close(self):
+        self._pool.clear()
+        if self._ks_own is not None:
+            self._ks_own.close()
+            self._ks_own = None
+        for r in self._own:
+            r.close()
+        self._own = []
+
+    def _ks(self, eval, key, who):
+        """the key-switch evaluator: the ckks.Evaluator's, or one of the switcher's own over ringQ alone for keys without P.  The device gadget
+        product strides a key by the limb counts of the evaluator's rings (rlwe.GadgetCiphertext), so a key made at lower levels is refused."""
+        ks = eval.ks
+        if ks is None:
+            if self._ks_own is None:
+                self._ks_own = rlwe.Evaluator(eval.ringQ, None)
+            ks = self._ks_own
+        have = (ks.ringQ.L - 1, ks.ringP.L - 1 if ks.ringP is not None else -1)
+        if (key.LevelQ(), key.LevelP()) != have:
+            raise RingHipError("cannot %s: the key is made at levels (Q %d, P %d) but the evaluator's rings hold levels (Q %d, P %d): build the "
+                               "evaluator over rings of the key's limb counts" % ((who, key.LevelQ(), key.LevelP()) + have))
+        return ks
+
+    def _buf(self, tag, ring, npoly, limbs):
+        key = (tag, id(ring._h), npoly, limbs)
+        p = self._pool.get(key)
+        if p is None:
+            p = self._pool[key] = DevicePoly(ring, npoly, limbs)
+        return p
+
+    def _at_level(self, tag, ring, p, level):
+        """a block read at `level`: itself, a view of a single poly's leading limbs, or a copy of a batch's"""
+        if p.limbs == level + 1:
+            return p
+        if p.npoly == 1:
+            return DevicePoly(ring, 1, level + 1, ptr=p.ptr, owner=p)
+        out = self._buf(tag, ring, p.npoly, level + 1)
+        ring.CopyLvl(p, out)
+        return out
+
+    def _enter(self, who, eval, ctIn, opOut):
+        if eval.ringQ.kind != Standard:
+            raise RingHipError("cannot %s: provided evaluator is not instantiated with RingType ring.Standard" % who)
+        to_real = who == "ComplexToReal"
+        big, small = (ctIn, opOut) if to_real else (opOut, ctIn)
+        if big.Value[0].ring.N != 2 * small.Value[0].ring.N:
+            raise RingHipError("cannot %s: %s" % (who, "ctIn ring degree must be twice opOut ring degree" if to_real
+                                                  else "opOut ring degree must be twice ctIn ring degree"))
+        level = min(ctIn.Level(), opOut.Level())
+        if opOut.Level() != level:
+            raise RingHipError("cannot %s: opOut is allocated at level %d above the level %d of the switch: a device batch cannot be resized, "
+                               "allocate opOut at ctIn's level or below" % (who, opOut.Level(), level))
+        if opOut.Degree() != 1 or ctIn.Degree() != 1 or opOut.Value[0].npoly != ctIn.Value[0].npoly:
+            raise RingHipError("cannot %s: ciphertexts of degree 1 and the same batch size" % who)
+        return level
+
+    @staticmethod
+    def _meta(ctIn, opOut, scale):
+        for name in ("LogDimensions", "IsBatched", "IsMontgomery"):
+            if hasattr(ctIn, name):
+                setattr(opOut, name, getattr(ctIn, name))
+        opOut.IsNTT, opOut.Scale = ctIn.IsNTT, scale
+
+    def ComplexToReal(self, eval, ctIn, opOut, fused=None):
+        """(:55-87): enc(real(m) + i imag(m)) on the standard ring -> enc(2 real(m)) read at twice the scale on the conjugate-invariant ring"""
+        who = "ComplexToReal"
+        level = self._enter(who, eval, ctIn, opOut)
+        if self.stdToci is None:
+            raise RingHipError("cannot ComplexToReal: no realToComplexEvk provided to this DomainSwitcher")
+        rs, rc = self.stdRingQ.AtLevel(level), self.conjugateRingQ.AtLevel(level)
+        npoly = ctIn.Value[0].npoly
+        c0, c1 = (self._at_level(("in", c), rs, ctIn.Value[c], level) for c in (0, 1))
+        tmp = Ciphertext([self._buf(("g", c), rs, npoly, level + 1) for c in (0, 1)], is_ntt=ctIn.IsNTT)
+        self._ks(eval, self.stdToci, who).GadgetProduct(level, c1, self.stdToci, tmp)
+        if FUSED_BRIDGE["fold_tail"] if fused is None else fused:
+            _check(lib().rh_ckks_bridge_fold_tail(rc._h, level, tmp.Value[0].ptr, tmp.Value[1].ptr, c0.ptr, self._index.ptr,
+                                                  opOut.Value[0].ptr, opOut.Value[1].ptr, npoly))
+        else:
+            rs.Add(tmp.Value[0], c0, tmp.Value[0])
+            rc.FoldStandardToConjugateInvariant(tmp.Value[0], self._index, opOut.Value[0])
+            rc.FoldStandardToConjugateInvariant(tmp.Value[1], self._index, opOut.Value[1])
+        s = ctIn.Scale if isinstance(ctIn.Scale, Scale) else Scale(ctIn.Scale)
+        self._meta(ctIn, opOut, s.Mul(Scale(2)))
+
+    def RealToComplex(self, eval, ctIn, opOut, fused=None):
+        """(:96-129): enc(real(m)) on the conjugate-invariant ring -> enc(real(m) + 0 i) on the standard ring"""
+        who = "RealToComplex"
+        level = self._enter(who, eval, ctIn, opOut)
+        if self.ciToStd is None:
+            raise RingHipError("cannot RealToComplex: no realToComplexEvk provided to this DomainSwitcher")
+        rs, rc = self.stdRingQ.AtLevel(level), self.conjugateRingQ.AtLevel(level)
+        npoly = ctIn.Value[0].npoly
+        c0, c1 = (self._at_level(("in", c), rc, ctIn.Value[c], level) for c in (0, 1))
+        key = self.ciToStd
+        fuse = FUSED_BRIDGE["unfold_then_add"] if fused is None else fused
+        if fuse and key.LevelP() >= 1 and ctIn.IsNTT:
+            both = self._buf("u", rs, 2 * npoly, level + 1)                     # one unfold over both components
+            if c1.ptr == c0.ptr + c0.words * 8:
+                src = DevicePoly(rc, 2 * npoly, level + 1, ptr=c0.ptr, owner=c0)
+                rs.UnfoldConjugateInvariantToStandard(src, both)
+            else:
+                for c, v in enumerate((c0, c1)):
+                    rs.UnfoldConjugateInvariantToStandard(v, DevicePoly(rs, npoly, level + 1, ptr=both.ptr + c * npoly * (level + 1) * rs.N * 8, owner=both))
+            u0 = DevicePoly(rs, npoly, level + 1, ptr=both.ptr, owner=both)
+            u1 = DevicePoly(rs, npoly, level + 1, ptr=both.ptr + npoly * (level + 1) * rs.N * 8, owner=both)
+            self._ks(eval, key, who).GadgetProductThenAdd(level, u1, key, u0, None, opOut)
+        else:
+            rs.UnfoldConjugateInvariantToStandard(c0, opOut.Value[0])
+            rs.UnfoldConjugateInvariantToStandard(c1, opOut.Value[1])
+            tmp = Ciphertext([self._buf(("g", c), rs, npoly, level + 1) for c in (0, 1)], is_ntt=ctIn.IsNTT)
+            self._ks(eval, key, who).GadgetProduct(level, opOut.Value[1], key, tmp)
+            rs.Add(opOut.Value[0], tmp.Value[0], opOut.Value[0])
+            rs.CopyLvl(tmp.Value[1], opOut.Value[1])
+        self._meta(ctIn, opOut, ctIn.Scale if isinstance(ctIn.Scale, Scale) else Scale(ctIn.Scale))
+
+    def ComplexToRealNew(self, eval, ctIn, fused=None):
+        rc = self.conjugateRingQ.AtLevel(min(ctIn.Level(), self.stdToci.LevelQ() if self.stdToci is not None else ctIn.Level()))
+        out = Ciphertext([rc.NewPoly(ctIn.Value[0].npoly) for _ in (0, 1)], is_ntt=ctIn.IsNTT)
+        self.ComplexToReal(eval, ctIn, out, fused)
+        return out
+
+    def RealToComplexNew(self, eval, ctIn, fused=None):
+        rs = self.stdRingQ.AtLevel(min(ctIn.Level(), self.ciToStd.LevelQ() if self.ciToStd is not None else ctIn.Level()))
+        out = Ciphertext([rs.NewPoly(ctIn.Value[0].npoly) for _ in (0, 1)], is_ntt=ctIn.IsNTT)
+        self.RealToComplex(eval, ctIn, out, fused)
+        return out
+
+
+def NewDomainSwitcher(params, complexToRealEvk=None, realToComplexEvk=None):
+    return DomainSwitcher(params, complexToRealEvk, realToComplexEvk)
 
 
 # ---- ckks.GetPrecisionStats (schemes/ckks/precision.go): host statistics over the device Decode (precision.py) -------------------------------------------

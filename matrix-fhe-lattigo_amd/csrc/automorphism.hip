@@ -232,3 +232,45 @@ extern "C" int rh_ring_pad_default_to_ci(rh_ring* r, int level, const uint64_t* 
   ci_pad_kernel<<<dim3(rows, word_chunks(n)), 256, 0, rh_stream(r)>>>(std_, ci, n, is_ntt ? 1 : 0, r->d_consts, level + 1);
   return rh_launch_ok("ci_pad_kernel");
 }
+
+// ---- the tail of DomainSwitcher.ComplexToReal (schemes/ckks/bridge.go:79-83) as one launch over both components of a batch -----------
+// out0[j] = CRed(CRed(g0[idx[j]] + c0[idx[j]]) + CRed(g0[j] + c0[j])), out1[j] = CRed(g1[idx[j]] + g1[j]) for j < n: Ring.Add over rows
+// of 2n words and the two FoldStandardToConjugateInvariant calls.  Every operand canonical, so every intermediate is the word the composed
+// calls write.  g0, g1, c0: (npoly, level + 1, 2n); out0, out1: (npoly, level + 1, n); blockIdx.x = component * rows + row.
+__global__ void __launch_bounds__(256)
+ckks_bridge_fold_tail_kernel(const u64* __restrict__ g0, const u64* __restrict__ g1, const u64* __restrict__ c0, const u64* __restrict__ index,
+                             u64* __restrict__ out0, u64* __restrict__ out1, unsigned n, unsigned rows, const LimbConsts* __restrict__ consts, int L) {
+  const unsigned comp = blockIdx.x / rows, row = blockIdx.x % rows;
+  const u64 q = consts[row % (unsigned)L].q;
+  const size_t bi = (size_t)row * 2 * n, bo = (size_t)row * n;
+  for (unsigned j = blockIdx.y * blockDim.x + threadIdx.x; j < n; j += gridDim.y * blockDim.x) {
+    const unsigned i = (unsigned)index[j];
+    if (comp == 0) {
+      u64 a = g0[bi + i] + c0[bi + i], b = g0[bi + j] + c0[bi + j];
+      a = a >= q ? a - q : a; b = b >= q ? b - q : b;
+      const u64 v = a + b;
+      out0[bo + j] = v >= q ? v - q : v;
+    } else {
+      const u64 v = g1[bi + i] + g1[bi + j];
+      out1[bo + j] = v >= q ? v - q : v;
+    }
+  }
+}
+// r: the conjugate-invariant ring of degree n (or any ring of that degree and those moduli, as for rh_ring_fold_standard_to_ci);
+// index: n entries below 2n on the device, the caller's responsibility like a Go slice index
+extern "C" int rh_ckks_bridge_fold_tail(rh_ring* r, int level, const uint64_t* g0, const uint64_t* g1, const uint64_t* c0, const uint64_t* index,
+                                        uint64_t* out0, uint64_t* out1, int npoly) {
+  const char* who = "rh_ckks_bridge_fold_tail";
+  if (!index || !g1 || !c0 || !out1) return rh_fail(RH_ERR_ARG, "%s: null argument", who);
+  if (int rc = index_map_common(r, level, g0, out0, npoly, who)) return rc;
+  if (r->N < 2) return rh_fail(RH_ERR_ARG, "%s: degree < 2", who);
+  if ((size_t)npoly * (size_t)(level + 1) * 2 > 0x7fffffffu) return rh_fail(RH_ERR_ARG, "%s: too many rows for one launch", who);
+  const unsigned rows = (unsigned)npoly * (unsigned)(level + 1), n = (unsigned)r->N;
+  const size_t wi = (size_t)rows * 2 * n, wo = (size_t)rows * n;
+  const RhBlock wr[2] = {{out0, wo}, {out1, wo}}, rd[4] = {{g0, wi}, {g1, wi}, {c0, wi}, {index, n}};
+  if (int rc = rh_blocks_ok(wr, 2, rd, 4, who, "an output overlaps an input")) return rc;
+  if (int rc = rh_blocks_disjoint(wr, 2, who, "the two outputs overlap")) return rc;
+  if (!rows) return RH_OK;
+  ckks_bridge_fold_tail_kernel<<<dim3(2 * rows, word_chunks(n)), 256, 0, rh_stream(r)>>>(g0, g1, c0, index, out0, out1, n, rows, r->d_consts, level + 1);
+  return rh_launch_ok("ckks_bridge_fold_tail_kernel");
+}

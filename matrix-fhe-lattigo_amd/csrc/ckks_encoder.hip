@@ -1,4 +1,5 @@
-// ckks_encoder.hip -- schemes/ckks/encoder.go (float64 path, prec <= 53) on device batches of nvec vectors, standard rings.
+// ckks_encoder.hip -- schemes/ckks/encoder.go (float64 path, prec <= 53) on device batches of nvec vectors: standard rings
+// (rh_ckks_encoder_create) and the real-only embedding of conjugate-invariant rings (rh_ckks_encoder_create_real).
 //
 //   Encode  = copy -> special IFFT (ckks_vector_ops.go:18-47) -> quantize with the stride-gap spread (utils.go:130-234,
 //             core/rlwe/utils.go:187-245) [-> MForm inside the quantizer] [-> Ring.NTT]
@@ -8,6 +9,12 @@
 // The sparse case of NTTSparseAndMontgomery transforms in dimension n with the roots of N and repeats every value gap times; that is the
 // full transform of the polynomial in X^gap, so the spread followed by the ring's own NTT gives the same canonical words, and MForm before
 // or after a transform whose outputs are canonical commutes with it.  The transforms' stage grouping is in ckks_encoder_kernels.hip.hpp.
+//
+// Conjugate-invariant ring of degree n (e->real): m = NthRoot = 4n, rotGroup of n entries, up to n slots (one FFT size above a standard ring
+// of the same degree: the same stage kernels, one more stage).  Encode drops the imaginary parts on the way into the scratch block
+// (encoder.go:225-228), quantizes the real parts alone at stride n / slots (utils.go:145-147) and transforms with the ring's own
+// conjugate-invariant NTT; Decode reads the first `slots` strided coefficients and sets imag[i] = 0 - real[slots - i] (the `isreal` arms,
+// encoder.go:825-831, :938-944) before the special FFT.
 //
 // The handle owns its scratch (two complex blocks and one poly block); rh_ckks_encoder_reserve sizes it so that no later call allocates.
 // Calls are asynchronous on the ring's stream and lock the handle for the enqueue only: the scratch is reused in stream order.
@@ -20,6 +27,8 @@
 struct rh_ckks_encoder {
   rh_ring* Q = nullptr;
   int logN = 0, logm = 0;
+  bool real = false;                   // conjugate-invariant ring: the real-only embedding
+  int max_log_slots = 0;               // LogMaxDimensions().Cols: logN - 1, or logN when real
   EncCplx* d_roots = nullptr;          // m + 1 roots as the caller computed them (GetRootsComplex128, utils.go:53-77)
   unsigned* d_rot = nullptr;           // rotGroup: 5^j mod m, j < m / 4 (encoder.go:77-83)
   u64* d_tables = nullptr;             // garner | qmod | Q | Q >> 1
@@ -42,16 +51,14 @@ extern "C" void rh_ckks_encoder_destroy(rh_ckks_encoder* e) {
   delete e;
 }
 
-extern "C" int rh_ckks_encoder_create(rh_ckks_encoder** out, rh_ring* ring, const double* roots, size_t nroots, unsigned prec) {
-  if (!out || !ring || !roots) return rh_fail(RH_ERR_ARG, "rh_ckks_encoder_create: null argument");
-  if (ring->kind == RH_RING_CI) return rh_fail(RH_ERR_UNSUPPORTED, "rh_ckks_encoder_create: conjugate-invariant rings are not supported (the real-only embedding stays with the reference)");
-  if (ring->kind != RH_RING_STANDARD) return rh_fail(RH_ERR_UNSUPPORTED, "rh_ckks_encoder_create: 3N rings are not supported (the CKKS encoder is defined on power-of-two cyclotomics)");
-  if (prec > 53) return rh_fail(RH_ERR_UNSUPPORTED, "rh_ckks_encoder_create: prec = %u > 53 needs the *big.Float / *bignum.Complex encoder, which stays with the reference", prec);
-  const size_t m = 2 * (size_t)ring->N;
-  if (nroots != m + 1) return rh_fail(RH_ERR_ARG, "rh_ckks_encoder_create: %zu roots given, NthRoot + 1 = %zu expected", nroots, m + 1);
-  if (ring->L > RH_MAX_LIMBS) return rh_fail(RH_ERR_ARG, "rh_ckks_encoder_create: %d limbs, at most %d", ring->L, RH_MAX_LIMBS);
+static int enc_create(rh_ckks_encoder** out, rh_ring* ring, const double* roots, size_t nroots, unsigned prec, bool real, const char* who) {
+  if (prec > 53) return rh_fail(RH_ERR_UNSUPPORTED, "%s: prec = %u > 53 needs the *big.Float / *bignum.Complex encoder, which stays with the reference", who, prec);
+  const size_t m = (real ? 4 : 2) * (size_t)ring->N;
+  if (nroots != m + 1) return rh_fail(RH_ERR_ARG, "%s: %zu roots given, NthRoot + 1 = %zu expected", who, nroots, m + 1);
+  if (ring->L > RH_MAX_LIMBS) return rh_fail(RH_ERR_ARG, "%s: %d limbs, at most %d", who, ring->L, RH_MAX_LIMBS);
   rh_ckks_encoder* e = new rh_ckks_encoder();
-  e->Q = ring; e->logN = ring->logN; e->logm = ring->logN + 1;
+  e->Q = ring; e->logN = ring->logN; e->logm = ring->logN + (real ? 2 : 1);
+  e->real = real; e->max_log_slots = real ? ring->logN : ring->logN - 1;
   const int L = ring->L;
   std::vector<unsigned> rot(m >> 2);
   unsigned five = 1;
@@ -91,6 +98,20 @@ extern "C" int rh_ckks_encoder_create(rh_ckks_encoder** out, rh_ring* ring, cons
   return RH_OK;
 }
 
+extern "C" int rh_ckks_encoder_create(rh_ckks_encoder** out, rh_ring* ring, const double* roots, size_t nroots, unsigned prec) {
+  if (!out || !ring || !roots) return rh_fail(RH_ERR_ARG, "rh_ckks_encoder_create: null argument");
+  if (ring->kind == RH_RING_CI) return rh_fail(RH_ERR_UNSUPPORTED, "rh_ckks_encoder_create: conjugate-invariant rings are not supported (the real-only embedding stays with the reference)");
+  if (ring->kind != RH_RING_STANDARD) return rh_fail(RH_ERR_UNSUPPORTED, "rh_ckks_encoder_create: 3N rings are not supported (the CKKS encoder is defined on power-of-two cyclotomics)");
+  return enc_create(out, ring, roots, nroots, prec, false, "rh_ckks_encoder_create");
+}
+
+// the real-only encoder of a conjugate-invariant ring: roots of 4N + 1 entries
+extern "C" int rh_ckks_encoder_create_real(rh_ckks_encoder** out, rh_ring* ring, const double* roots, size_t nroots, unsigned prec) {
+  if (!out || !ring || !roots) return rh_fail(RH_ERR_ARG, "rh_ckks_encoder_create_real: null argument");
+  if (ring->kind != RH_RING_CI) return rh_fail(RH_ERR_UNSUPPORTED, "rh_ckks_encoder_create_real: a conjugate-invariant ring is expected (standard rings: rh_ckks_encoder_create)");
+  return enc_create(out, ring, roots, nroots, prec, true, "rh_ckks_encoder_create_real");
+}
+
 extern "C" int rh_ckks_encoder_set_tuning(rh_ckks_encoder* e, const char* key, long value) {
   if (!e || !key) return rh_fail(RH_ERR_ARG, "rh_ckks_encoder_set_tuning: null argument");
   if (!strcmp(key, "ckks_fft_lds_log")) {
@@ -115,7 +136,7 @@ extern "C" int rh_ckks_encoder_reserve(rh_ckks_encoder* e, int nvec) {
   if (!e || nvec < 0) return rh_fail(RH_ERR_ARG, "rh_ckks_encoder_reserve: bad argument");
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   (void)hipSetDevice(e->Q->device);
-  const size_t N = (size_t)e->Q->N, cb = (size_t)nvec * (N >> 1) * sizeof(EncCplx);
+  const size_t N = (size_t)e->Q->N, cb = ((size_t)nvec << e->max_log_slots) * sizeof(EncCplx);
   if (int rc = enc_scratch(e, 0, cb)) return rc;
   if (int rc = enc_scratch(e, 1, cb)) return rc;
   return enc_scratch(e, 2, (size_t)nvec * e->Q->L * N * 8);
@@ -147,8 +168,8 @@ static int enc_fft(rh_ckks_encoder* e, EncCplx* data, EncCplx* tmp, int logn, in
 
 static int enc_args(rh_ckks_encoder* e, int log_slots, int nvec, const char* who) {
   if (!e) return rh_fail(RH_ERR_ARG, "%s: null encoder handle", who);
-  if (log_slots < 0 || log_slots > e->logN - 1)
-    return rh_fail(RH_ERR_ARG, "%s: logSlots (%d) must be greater or equal to 0 and smaller than %d", who, log_slots, e->logN);
+  if (log_slots < 0 || log_slots > e->max_log_slots)
+    return rh_fail(RH_ERR_ARG, "%s: logSlots (%d) must be greater or equal to 0 and smaller than %d", who, log_slots, e->max_log_slots + 1);
   if (nvec < 0 || nvec > 65535) return rh_fail(RH_ERR_ARG, "%s: nvec = %d out of range [0, 65535]", who, nvec);
   return RH_OK;
 }
@@ -182,7 +203,7 @@ static int enc_quantize(rh_ckks_encoder* e, int level, const double* vals, u64* 
   const unsigned n = (unsigned)e->Q->N;
   const dim3 g((n + 255) / 256, (unsigned)nvec);
   ckks_quantize_kernel<<<g, 256, 0, st>>>(vals, out, n, level + 1, e->Q->d_consts, scale, batched, slots, nvals, loggap,
-                                          (is_ntt || mont) ? 1 : 0, mont ? 1 : 0);
+                                          (is_ntt || mont) ? 1 : 0, mont ? 1 : 0, batched && e->real ? 1 : 0);
   if (int rc = rh_launch_ok("ckks_quantize_kernel")) return rc;
   if (is_ntt) return rh_ring_ntt_any(e->Q, out, out, nvec, level + 1, 0, false);
   return RH_OK;
@@ -202,9 +223,13 @@ extern "C" int rh_ckks_encode(rh_ckks_encoder* e, int level, int log_slots, doub
   const size_t cb = ((size_t)nvec << log_slots) * sizeof(EncCplx);
   if (int rc = enc_scratch(e, 0, cb)) return rc;
   if (log_slots > e->fft_lds_log) if (int rc = enc_scratch(e, 1, cb)) return rc;
-  if (hipMemcpyAsync(e->buf[0], values_dev, cb, hipMemcpyDeviceToDevice, st) != hipSuccess) return rh_fail(RH_ERR_DEVICE, "rh_ckks_encode: copy failed");
+  if (e->real) {                                                        // buffCmplx[i] = complex(real(values[i]), 0) (:225-228)
+    const size_t count = (size_t)nvec << log_slots;
+    ckks_copy_real_kernel<<<(unsigned)((count + 255) / 256), 256, 0, st>>>(values_dev, (double*)e->buf[0], count);
+    if (int rc = rh_launch_ok("ckks_copy_real_kernel")) return rc;
+  } else if (hipMemcpyAsync(e->buf[0], values_dev, cb, hipMemcpyDeviceToDevice, st) != hipSuccess) return rh_fail(RH_ERR_DEVICE, "rh_ckks_encode: copy failed");
   if (int rc = enc_fft(e, (EncCplx*)e->buf[0], (EncCplx*)e->buf[1], log_slots, nvec, true, st)) return rc;
-  return enc_quantize(e, level, (const double*)e->buf[0], out_dev, nvec, scale, 1, 1u << log_slots, 0, e->logN - 1 - log_slots, is_ntt,
+  return enc_quantize(e, level, (const double*)e->buf[0], out_dev, nvec, scale, 1, 1u << log_slots, 0, e->max_log_slots - log_slots, is_ntt,
                       is_montgomery, st);
 }
 
@@ -251,8 +276,8 @@ extern "C" int rh_ckks_decode(rh_ckks_encoder* e, int level, int log_slots, doub
     return rh_launch_ok("ckks_crt_to_double_kernel");
   }
   if (log_slots > e->fft_lds_log) if (int rc = enc_scratch(e, 1, ((size_t)nvec << log_slots) * sizeof(EncCplx))) return rc;
-  const dim3 g((2 * slots + 255) / 256, (unsigned)nvec);
-  ckks_crt_to_double_kernel<<<g, 256, 0, st>>>(src, values_dev, n, L, e->Q->d_consts, e->tb, scale, slots, e->logN - 1 - log_slots, 0);
+  const dim3 g(((e->real ? 1 : 2) * slots + 255) / 256, (unsigned)nvec);
+  ckks_crt_to_double_kernel<<<g, 256, 0, st>>>(src, values_dev, n, L, e->Q->d_consts, e->tb, scale, slots, e->max_log_slots - log_slots, e->real ? 2 : 0);
   if (int rc = rh_launch_ok("ckks_crt_to_double_kernel")) return rc;
   if (int rc = enc_fft(e, (EncCplx*)values_dev, (EncCplx*)e->buf[1], log_slots, nvec, false, st)) return rc;
   if (logprec != 0 || real_only) {

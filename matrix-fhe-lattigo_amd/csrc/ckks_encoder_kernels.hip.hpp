@@ -137,6 +137,15 @@ ckks_fft_lds_kernel(const EncCplx* src, EncCplx* dst, int logn, int logb, int lo
   }
 }
 
+// buffCmplx[i] = complex(real(values[i]), 0): the copy into the encoder's buffer on a conjugate-invariant ring (encoder.go:225-228)
+__global__ void __launch_bounds__(256)
+ckks_copy_real_kernel(const double* __restrict__ vals, double* __restrict__ out, size_t count) {
+  const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= count) return;
+  out[2 * i] = vals[2 * i];
+  out[2 * i + 1] = 0.0;
+}
+
 // ---- quantizer (SingleFloat64ToFixedPointCRT, utils.go:171-234) -------------------------------------------------------------------------
 // (m * 2^e) mod q for a 53-bit m and e >= 0: the integer the reference's big.Float path holds (its 53-bit + 0.5 is a no-op at >= 2^64)
 __device__ __forceinline__ u64 enc_big_mod(u64 m, int e, const LimbConsts& c) {
@@ -150,19 +159,21 @@ __device__ __forceinline__ u64 enc_big_mod(u64 m, int e, const LimbConsts& c) {
 // One thread per coefficient, limb loop inside; out: (nvec, L, N).  grid (N / 256 rounded up, nvec).
 //   batched:  vals (nvec, slots) complex: coefficient i = k * gap takes re[k] for k < slots, im[k - slots] for k < 2 slots; zero elsewhere
 //             (Complex128ToFixedPointCRT, then the stride-gap spread of NTTSparseAndMontgomery)
+//             real (conjugate-invariant ring, gap = N / slots): coefficient i = k * gap takes re[k] for k < slots and nothing reads the
+//             imaginary parts (the `else` arm, utils.go:145-147): half the value traffic, no second coefficient block
 //   !batched: vals (nvec, nvals) doubles: coefficient i < nvals takes vals[i] (Float64ToFixedPointCRT)
 // canonical: the word is reduced to [0, q) -- the reference stores positive words unreduced and q for a negative multiple of q; what follows
 //            (NTT, MForm) maps either to the canonical residue of the class, so the reduction happens here.  mont: then MForm.
 __global__ void __launch_bounds__(256)
 ckks_quantize_kernel(const double* __restrict__ vals, u64* __restrict__ out, unsigned n, int L, const LimbConsts* __restrict__ consts,
-                     double scale, int batched, unsigned slots, unsigned nvals, int loggap, int canonical, int mont) {
+                     double scale, int batched, unsigned slots, unsigned nvals, int loggap, int canonical, int mont, int real) {
   const unsigned i = blockIdx.x * 256u + threadIdx.x;
   if (i >= n) return;
   const size_t vec = blockIdx.y;
   double v = 0.0;
   if (batched) {
     const unsigned k = i >> loggap;
-    if ((k << loggap) == i && k < 2 * slots) v = k < slots ? vals[(vec * slots + k) * 2] : vals[(vec * slots + (k - slots)) * 2 + 1];
+    if ((k << loggap) == i && k < (real ? slots : 2 * slots)) v = k < slots ? vals[(vec * slots + k) * 2] : vals[(vec * slots + (k - slots)) * 2 + 1];
   } else if (i < nvals) {
     v = vals[vec * nvals + i];
   }
@@ -213,16 +224,19 @@ struct EncCrtTables {
 // (coefficient N/2 + (k - slots) * gap).  The integer is rebuilt exactly: mixed-radix digits d_j (Garner), Horner over words, c >= Q >> 1
 // gives c - Q, then the top 64 bits and a sticky bit round to nearest, ties to even -- big.Float.Float64 (level > 0) and float64(uint64)
 // (level 0) are that rounding.  vals: (nvec, slots) complex, written whole.  grid (2 slots / 256 rounded up, nvec).
-// coeffs != 0 (polyToFloatNoCRT / polyToFloatCRT, encoder.go:1006-1185): no gather -- thread k takes coefficient k of all N, vals is
+// coeffs == 1 (polyToFloatNoCRT / polyToFloatCRT, encoder.go:1006-1185): no gather -- thread k takes coefficient k of all N, vals is
 // (nvec, N) doubles.  grid (N / 256 rounded up, nvec).
+// coeffs == 2 (the `isreal` arms, :825-831, :938-944; n / slots = gap): thread k < slots takes coefficient k * gap, x, and writes
+// re[k] = x / scale and im[slots - k] = 0 - x / scale (im[0] = 0): "values[i] -= complex(0, real(values[slots-i]))" for i >= 1, with the
+// division before (CRT) or after (level 0) the subtraction -- the same double, division being odd.  grid (slots / 256 rounded up, nvec).
 __global__ void __launch_bounds__(256)
 ckks_crt_to_double_kernel(const u64* __restrict__ poly, double* __restrict__ vals, unsigned n, int L, const LimbConsts* __restrict__ consts,
                           EncCrtTables tb, double scale, unsigned slots, int loggap, int coeffs) {
   const unsigned k = blockIdx.x * 256u + threadIdx.x;
-  if (k >= (coeffs ? n : 2 * slots)) return;
+  if (k >= (coeffs == 1 ? n : coeffs == 2 ? slots : 2 * slots)) return;
   const size_t vec = blockIdx.y;
   const bool imag = !coeffs && k >= slots;
-  const unsigned s = imag ? k - slots : k, idx = coeffs ? k : (imag ? (n >> 1) : 0u) + (s << loggap);
+  const unsigned s = imag ? k - slots : k, idx = coeffs == 1 ? k : (imag ? (n >> 1) : 0u) + (s << loggap);
   const u64* p = poly + vec * (size_t)L * n + idx;
   u64 d[RH_MAX_LIMBS_K], acc[RH_MAX_LIMBS_K];
   for (int j = 0; j < L; ++j) {                                   // d_j = (r_j - (d_0 + q_0 (d_1 + q_1 (...))) mod q_j) * garner_j mod q_j
@@ -275,7 +289,11 @@ ckks_crt_to_double_kernel(const u64* __restrict__ poly, double* __restrict__ val
     x = ldexp((double)mant, 64 * top - lz + 11);
   }
   if (neg) x = -x;
-  if (coeffs) vals[vec * n + k] = x / scale;
+  if (coeffs == 2) {
+    const double y = x / scale;
+    vals[(vec * slots + s) * 2] = y;
+    vals[(vec * slots + (s ? slots - s : 0u)) * 2 + 1] = s ? 0.0 - y : 0.0;
+  } else if (coeffs) vals[vec * n + k] = x / scale;
   else vals[(vec * slots + s) * 2 + (imag ? 1 : 0)] = x / scale;
 }
 

@@ -17,11 +17,12 @@
 #include "keygen_kernels.hip.hpp"
 
 // The rings of this file: standard rings, and 3N rings whose rows split into groups of eight coefficients (every kernel here addresses row r at
-// r * N words).  Conjugate-invariant rings are refused.  The other checks are those of the row-streaming entries: level, limb and row counts.
+// r * N words), and conjugate-invariant rings: every kernel here is per coefficient or row-wise in the NTT domain, so the ring type does not
+// enter (the transforms are the ring's own).  Who may hand such a ring in is decided above this file: the bare Python constructors refuse it,
+// ckks.Parameters passes the permit (sampling.rings_ok).  The other checks are those of the row-streaming entries: level, limb and row counts.
 static int kg_ring_ok(const rh_ring* r, int level, int count, const char* who, const char* negative = "negative count") {
   if (!r) return rh_fail(RH_ERR_ARG, "%s: null ring handle", who);
-  if (r->kind == RH_RING_CI) return rh_fail(RH_ERR_UNSUPPORTED, "%s: conjugate-invariant rings are not supported", who);
-  if (r->kind != RH_RING_STANDARD && (r->N & 7))
+  if (r->kind == RH_RING_3N && (r->N & 7))
     return rh_fail(RH_ERR_UNSUPPORTED, "%s: a 3N ring of degree %d: the samplers serve groups of eight coefficients (N %% 8 must be 0)", who, r->N);
   if (level < 0 || level >= r->L) return rh_fail(RH_ERR_ARG, "%s: level %d out of range [0,%d)", who, level, r->L);
   if (level + 1 > RH_MAX_LIMBS) return rh_fail(RH_ERR_ARG, "%s: at most %d limbs", who, RH_MAX_LIMBS);

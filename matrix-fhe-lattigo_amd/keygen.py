@@ -22,14 +22,16 @@ is converted with Ring.ToReferenceOrder first, and every block written carries t
 The error law: xe = (sigma, bound), the discrete Gaussian, or ("P", density) / ("H", weight), a ternary law through TernarySampler (the
 reference's Matrix CKKS test parameters use Xe = ring.Ternary{H: 1}; ring.NewSampler takes any law).
 
-Not built, refused by name: compressed (seeded) keys, GenEvaluationKeysForRingSwapNew,
-conjugate-invariant rings, 3N degrees that are no multiple of 8, Galois keys on 3N rings, the big-norm Gaussian, a plaintext and a ciphertext in
+Conjugate-invariant rings: behind the permit conjugate_invariant=True (sampling.rings_ok), which ckks.Parameters' factories set; the Galois
+elements are then taken modulo NthRoot = 4N.  GenEvaluationKeysForRingSwapNew (:207-228) is called on the standard ring's generator.
+
+Not built, refused by name: compressed (seeded) keys, conjugate-invariant rings without the permit, 3N degrees that are no multiple of 8, Galois keys on 3N rings, the big-norm Gaussian, a plaintext and a ciphertext in
 different domains or allocated at different levels."""
 import functools
 
 import numpy as np
 
-from .ringhip import BasisExtender, DevicePoly, Matrix3N, RingHipError, Standard, U64P, _check, lib
+from .ringhip import BasisExtender, ConjugateInvariant, DevicePoly, Matrix3N, RingHipError, Standard, U64P, _check, lib
 from .rlwe import ElementQP, GadgetCiphertext, PolyQP
 from .sampling import GaussianSampler, NewPRNG, SmallPoly, TernarySampler, UniformSampler, lift_small, rings_ok
 from .schemes import Ciphertext
@@ -102,13 +104,13 @@ def reference_order(method):
     return run
 
 
-def error_sampler(prng, ring, xe):
+def error_sampler(prng, ring, xe, conjugate_invariant=False):
     """the sampler of the error law xe: (sigma, bound), or ("P", density) / ("H", weight)"""
     if isinstance(xe[0], str):
         if xe[0] not in ("P", "H") or len(xe) != 2:
             raise RingHipError("the error law is (sigma, bound), (\"P\", density) or (\"H\", weight)")
-        return TernarySampler(prng, ring, **{xe[0]: xe[1]})
-    return GaussianSampler(prng, ring, *xe)
+        return TernarySampler(prng, ring, conjugate_invariant=conjugate_invariant, **{xe[0]: xe[1]})
+    return GaussianSampler(prng, ring, *xe, conjugate_invariant=conjugate_invariant)
 
 
 class Plaintext:
@@ -233,15 +235,16 @@ def gadget_row_table(Q, P, levelQ, levelP, pw2, dpl, key=0):
 class KeyGenerator:
     """rlwe.KeyGenerator over (ringQ, ringP): ringP None for parameters without P.  xs: ("P", density) or ("H", weight); xe: (sigma, bound)."""
 
-    def __init__(self, ringQ, ringP=None, xs=("P", 2 / 3), xe=(3.2, 19), prng=None):
-        rings_ok("KeyGenerator", ringQ, ringP)
+    def __init__(self, ringQ, ringP=None, xs=("P", 2 / 3), xe=(3.2, 19), prng=None, conjugate_invariant=False):
+        rings_ok("KeyGenerator", ringQ, ringP, conjugate_invariant)
+        self._ci = bool(conjugate_invariant)
         if ringP is not None and ringP.N != ringQ.N:
             raise RingHipError("KeyGenerator: ringQ and ringP differ in degree")
         self.ringQ, self.ringP = ringQ, ringP
         self.prng = NewPRNG() if prng is None else prng
         self.xs, self.xe = tuple(xs), tuple(xe)
-        self.uniform = UniformSampler(self.prng, ringQ, ringP)
-        self.gauss = error_sampler(self.prng, ringQ, self.xe)
+        self.uniform = UniformSampler(self.prng, ringQ, ringP, conjugate_invariant=self._ci)
+        self.gauss = error_sampler(self.prng, ringQ, self.xe, self._ci)
         self.Q, self.P = [int(q) for q in ringQ.moduli], [int(p) for p in ringP.moduli] if ringP is not None else []
 
     # ---- secret keys ------------------------------------------------------------------------------------------------------------------------
@@ -262,10 +265,10 @@ class KeyGenerator:
         if samples is not None:
             return self._secret_from(SmallPoly.from_numpy(self.ringQ, np.asarray(samples, dtype=np.int32).reshape(1, -1)))
         kind, v = self.xs
-        return self._secret_from(TernarySampler(self.prng, self.ringQ, **{kind: v}).ReadNew(1))
+        return self._secret_from(TernarySampler(self.prng, self.ringQ, conjugate_invariant=self._ci, **{kind: v}).ReadNew(1))
 
     def GenSecretKeyWithHammingWeightNew(self, hw):
-        return self._secret_from(TernarySampler(self.prng, self.ringQ, H=int(hw)).ReadNew(1))
+        return self._secret_from(TernarySampler(self.prng, self.ringQ, H=int(hw), conjugate_invariant=self._ci).ReadNew(1))
 
     def GenSecretKey(self, sk, samples=None):
         new = self.GenSecretKeyNew(samples)
@@ -502,12 +505,13 @@ class KeyGenerator:
         rq = self.ringQ.AtLevel(levelQ)
         rp = self.ringP.AtLevel(levelP) if levelP >= 0 else None
         n, N = len(galEls), rq.N
+        NthRoot = (4 if rq.kind == ConjugateInvariant else 2) * N          # ring.NthRoot (ring/ring.go:178-183)
         outQ = DevicePoly(rq, n, levelQ + 1)
         outP = DevicePoly(rp, n, levelP + 1) if rp is not None else None
         for k, g in enumerate(galEls):
             if g & 1 == 0:
                 raise RingHipError("cannot GenGaloisKey: the Galois element must be odd")
-            inv = pow(g, 2 * N - 1, 2 * N)                              # Parameters.ModInvGaloisElement (core/rlwe/params.go:677-681)
+            inv = pow(g, NthRoot - 1, NthRoot)                          # Parameters.ModInvGaloisElement (core/rlwe/params.go:677-681)
             rq.AutomorphismNTT(sq, inv, _view(outQ, rq, k, 1))
             if rp is not None:
                 rp.AutomorphismNTT(sp, inv, _view(outP, rp, k, 1))
@@ -515,7 +519,7 @@ class KeyGenerator:
         keys = []
         for k, g in enumerate(galEls):
             gk = self._key(GaloisKey, tabQ, tabP, k * rows, rows, levelQ, levelP, pw2, dpl)
-            gk.GaloisElement, gk.NthRoot = g, 2 * N
+            gk.GaloisElement, gk.NthRoot = g, NthRoot
             keys.append(gk)
         return keys
 
@@ -536,16 +540,52 @@ class KeyGenerator:
             else:
                 gks[i].__dict__.update(new.__dict__)
 
-    def GenEvaluationKeysForRingSwapNew(self, *args, **kw):
-        raise RingHipError("GenEvaluationKeysForRingSwapNew: conjugate-invariant rings are not supported by the device path")
+    def ring_swap_secret(self, skConjugateInvariant):
+        """The conjugate-invariant secret of degree n as a secret of this generator's standard ring of degree 2n (:212-217), from its small
+        coefficients s: m[0] = s_0, m[i] = s_i and m[2n - i] = -s_i for 1 <= i < n, m[n] = 0 -- the element s(X + X^-1) of Z[X]/(X^2n + 1) --
+        lifted under this ring's Q and P, NTT, MForm.  Its Q rows are UnfoldConjugateInvariantToStandard of the secret's own rows (what the
+        reference computes); its P rows are made here because the two parameter sets need not share P."""
+        who = "GenEvaluationKeysForRingSwapNew"
+        small = skConjugateInvariant.Value.Q.ring
+        n = small.N
+        if self.ringQ.kind != Standard or small.kind != ConjugateInvariant or self.ringQ.N != 2 * n:
+            raise RingHipError("%s: the generator's ring must be the standard ring of degree 2n of a conjugate-invariant secret of degree n "
+                               "(generator: degree %d, skConjugateInvariant: degree %d)" % (who, self.ringQ.N, n))
+        c = centred_coeffs(skConjugateInvariant)
+        m = np.zeros((1, 2 * n), dtype=np.int32)
+        m[0, :n] = c
+        m[0, n + 1:] = -c[:0:-1]
+        return self._secret_from(SmallPoly.from_numpy(self.ringQ, m))
+
+    def GenEvaluationKeysForRingSwapNew(self, skStd, skConjugateInvariant, levelQ=None, levelP=None, BaseTwoDecomposition=0, compressed=False,
+                                        samples=None, fused=None):
+        """(:207-228), on the standard ring's generator: (stdToci, ciToStd), the keys from skStd to the mapped conjugate-invariant secret
+        (ring_swap_secret) and back, both through GenEvaluationKeyNew.  samples: a pair, one entry per key."""
+        who = "GenEvaluationKeysForRingSwapNew"
+        rs, rc = skStd.Value.Q.ring, skConjugateInvariant.Value.Q.ring
+        if rs.kind != Standard or rc.kind != ConjugateInvariant or rs.N != 2 * rc.N or rs.N != self.ringQ.N:
+            raise RingHipError("%s: skStd must belong to the generator's standard ring of degree 2n and skConjugateInvariant to a conjugate-invariant "
+                               "ring of degree n (generator: %d, skStd: %d, skConjugateInvariant: %d)" % (who, self.ringQ.N, rs.N, rc.N))
+        k = min(skStd.LevelQ(), skConjugateInvariant.LevelQ()) + 1
+        if [int(q) for q in rc.moduli][:k] != self.Q[:k]:
+            raise RingHipError("%s: the two secrets must share the moduli Q" % who)
+        if levelQ is None:
+            levelQ = k - 1
+        if levelQ > k - 1:
+            raise RingHipError("%s: levelQ %d above the secrets' common level %d" % (who, levelQ, k - 1))
+        mapped = self.ring_swap_secret(skConjugateInvariant)
+        sa, sb = samples if samples is not None else (None, None)
+        kw = dict(levelQ=levelQ, levelP=levelP, BaseTwoDecomposition=BaseTwoDecomposition, compressed=compressed, fused=fused)
+        return self.GenEvaluationKeyNew(skStd, mapped, samples=sa, **kw), self.GenEvaluationKeyNew(mapped, skStd, samples=sb, **kw)
 
 
 class Encryptor:
     """rlwe.Encryptor: `key` a SecretKey or a PublicKey.  Ciphertexts are batches (one Ciphertext whose polys hold npoly ciphertexts): one sampler
     Read per batch, the ciphertext's index within the batch in the substream id."""
 
-    def __init__(self, ringQ, ringP=None, key=None, prng=None, xs=("P", 2 / 3), xe=(3.2, 19)):
-        rings_ok("Encryptor", ringQ, ringP)
+    def __init__(self, ringQ, ringP=None, key=None, prng=None, xs=("P", 2 / 3), xe=(3.2, 19), conjugate_invariant=False):
+        rings_ok("Encryptor", ringQ, ringP, conjugate_invariant)
+        self._ci = bool(conjugate_invariant)
         self.ringQ, self.ringP, self.key = ringQ, ringP, key
         self.xs, self.xe = tuple(xs), tuple(xe)
         self._set_prng(NewPRNG() if prng is None else prng)
@@ -553,9 +593,9 @@ class Encryptor:
 
     def _set_prng(self, prng):
         self.prng = prng
-        self.uniform = UniformSampler(prng, self.ringQ, self.ringP)
-        self.gauss = error_sampler(prng, self.ringQ, self.xe)
-        self.ternary = TernarySampler(prng, self.ringQ, **{self.xs[0]: self.xs[1]})
+        self.uniform = UniformSampler(prng, self.ringQ, self.ringP, conjugate_invariant=self._ci)
+        self.gauss = error_sampler(prng, self.ringQ, self.xe, self._ci)
+        self.ternary = TernarySampler(prng, self.ringQ, conjugate_invariant=self._ci, **{self.xs[0]: self.xs[1]})
 
     def _copy(self):
         new = object.__new__(type(self))                                   # a ckks.Encryptor stays one
@@ -741,7 +781,7 @@ class Encryptor:
             raise RingHipError("cannot EncryptZero: ringqp elements are encrypted under a secret key on the device path")
         if not ct.IsNTT or ct.Value[0].Q.npoly != 1:
             raise RingHipError("cannot EncryptZero: ringqp elements are taken one at a time, in the NTT domain and in Montgomery form")
-        kg = KeyGenerator(self.ringQ, self.ringP, self.xs, self.xe, self.prng)
+        kg = KeyGenerator(self.ringQ, self.ringP, self.xs, self.xe, self.prng, conjugate_invariant=self._ci)
         levelQ, levelP = ct.LevelQ(), ct.LevelP()
         sq, sp = kg._sk_rows(self.key, levelQ, levelP)
         tabQ, tabP, _, _ = kg._zero_rows(sq, sp, levelQ, levelP, samples, fused)
@@ -756,8 +796,8 @@ class Encryptor:
 class Decryptor:
     """rlwe.Decryptor (decryptor.go:42-90): pt = c0 + s (c1 + s c2), degree <= 2, in the ciphertext's domain"""
 
-    def __init__(self, ringQ, sk):
-        rings_ok("Decryptor", ringQ)
+    def __init__(self, ringQ, sk, conjugate_invariant=False):
+        rings_ok("Decryptor", ringQ, None, conjugate_invariant)
         self.ringQ, self.sk = ringQ, sk
 
     @reference_order

@@ -97,6 +97,7 @@ def lib():
         "rh_ring_shift": (i, [vp, i, vp, vp, i, i]), "rh_ring_automorphism_ntt_index": (i, [vp, i, vp, vp, vp, i, i]), "rh_ring_mult_by_monomial": (i, [vp, i, vp, vp, i, i]),
         "rh_ring_unfold_ci_to_standard": (i, [vp, i, vp, vp, i]), "rh_ring_fold_standard_to_ci": (i, [vp, i, vp, vp, vp, i]),
         "rh_ring_pad_default_to_ci": (i, [vp, i, vp, i, vp, i]),
+        "rh_ckks_bridge_fold_tail": (i, [vp, i, vp, vp, vp, vp, vp, vp, i]),
         "rh_ntt_forward": (i, [vp, i, U64P, U64P]), "rh_ntt_forward_lazy": (i, [vp, i, U64P, U64P]),
         "rh_ntt_backward": (i, [vp, i, U64P, U64P]), "rh_ntt_backward_lazy": (i, [vp, i, U64P, U64P]),
         "rh_ntt_poly_forward": (i, [vp, i, C.POINTER(vp), C.POINTER(vp), i]), "rh_ntt_poly_backward": (i, [vp, i, C.POINTER(vp), C.POINTER(vp), i]),
@@ -170,6 +171,7 @@ def lib():
         "rh_ckks_dft_finish": (i, [vp, C.c_uint, i, vp, vp, C.c_double, i, C.POINTER(i), vp, sz]),
         "rh_ckks_bootstrap_modup": (i, [vp, vp, i, i, vp, vp, i, vp, vp, vp, vp, i, U64P, U64P]), "rh_ckks_double_angle": (i, [vp, i, vp, vp, i, U64P, U64P]),
         "rh_ckks_encoder_create": (i, [C.POINTER(vp), vp, C.POINTER(C.c_double), sz, C.c_uint]), "rh_ckks_encoder_destroy": (None, [vp]),
+        "rh_ckks_encoder_create_real": (i, [C.POINTER(vp), vp, C.POINTER(C.c_double), sz, C.c_uint]),
         "rh_ckks_encoder_reserve": (i, [vp, i]), "rh_ckks_encoder_set_tuning": (i, [vp, C.c_char_p, C.c_long]),
         "rh_ckks_special_ifft": (i, [vp, vp, i, i]), "rh_ckks_special_fft": (i, [vp, vp, i, i]),
         "rh_ckks_encode": (i, [vp, i, i, C.c_double, vp, i, vp, i, i]), "rh_ckks_encode_coeffs": (i, [vp, i, C.c_double, vp, i, i, vp, i]),

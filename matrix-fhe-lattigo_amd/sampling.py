@@ -20,7 +20,8 @@ Deviations from the reference, on purpose: the stream is not the Go sampler's se
 of bytes per coefficient); the Gaussian comes from a cumulative table exact to 2^-63; a zero is the canonical 0 whatever its sign (the
 reference writes q for a zero of sign 0).  Standard rings and 3N rings whose degree is a multiple of 8 (a lane serves a group of eight
 coefficients; rows are addressed at N words, not at 2^logN).  The big-norm Gaussian (:99-153), conjugate-invariant rings and the other 3N
-degrees are refused by name."""
+degrees are refused by name.  Conjugate-invariant rings are served behind a permit: the keyword conjugate_invariant=True, which only the
+factories of ckks.Parameters set (rings_ok says why); the arithmetic is the same, N coefficients per row."""
 import ctypes as C
 import secrets
 import struct
@@ -98,12 +99,16 @@ def NewPRNG():
     return KeyedPRNG(secrets.token_bytes(64))
 
 
-def rings_ok(who, ring, ringP=None):
-    """the rings of the key layer: standard rings and 3N rings with N % 8 == 0, ringQ and ringP of the same kind"""
+def rings_ok(who, ring, ringP=None, conjugate_invariant=False):
+    """the rings of the key layer: standard rings and 3N rings with N % 8 == 0, ringQ and ringP of the same kind.
+    conjugate_invariant: the permit for conjugate-invariant rings.  The samplers, KeyGenerator, Encryptor and Decryptor take it as a keyword of
+    that name and hand it on; the factories of ckks.Parameters (NewKeyGenerator, NewEncryptor, NewDecryptor) are what sets it, the way the
+    reference reaches such a ring through a parameters object.  A bare constructor on a conjugate-invariant ring handle keeps refusing: the
+    multiparty protocols, RGSW, blind rotation and the traces build on these constructors and are not made for such rings."""
     for r in (ring, ringP):
         if r is None:
             continue
-        if r.kind == ConjugateInvariant:
+        if r.kind == ConjugateInvariant and not conjugate_invariant:
             raise RingHipError("cannot %s: conjugate-invariant rings are not supported (of the power-of-two rings, standard rings only)" % who)
         if r.kind == Matrix3N and r.N % 8:
             raise RingHipError("cannot %s: a 3N ring of degree %d: the samplers serve groups of eight coefficients (N %% 8 must be 0)" % (who, r.N))
@@ -152,8 +157,8 @@ class SmallPoly:
 class UniformSampler:
     """ring.UniformSampler / ringqp.UniformSampler: uniform residues under the limbs of ringQ and, for QP polys, of ringP (rows LQ, LQ + 1, ...)"""
 
-    def __init__(self, prng, ring, ringP=None):
-        rings_ok("UniformSampler", ring, ringP)
+    def __init__(self, prng, ring, ringP=None, conjugate_invariant=False):
+        rings_ok("UniformSampler", ring, ringP, conjugate_invariant)
         self.prng, self.ring, self.ringP = prng, ring, ringP
 
     def read_rows(self, ring, ptr, out_rows, npoly, call, poly0=0, row0=0):
@@ -198,8 +203,8 @@ def gaussian_table(sigma, bound):
 class GaussianSampler:
     """ring.GaussianSampler for ring.DiscreteGaussian{Sigma, Bound}: int32 (npoly, N) signed coefficients"""
 
-    def __init__(self, prng, ring, sigma=3.2, bound=19):
-        rings_ok("GaussianSampler", ring)
+    def __init__(self, prng, ring, sigma=3.2, bound=19, conjugate_invariant=False):
+        rings_ok("GaussianSampler", ring, None, conjugate_invariant)
         self.prng, self.ring, self.sigma, self.bound = prng, ring, float(sigma), float(bound)
         self.table = gaussian_table(sigma, bound)
         self._table = DevicePoly(ring.AtLevel(0), (len(self.table) + ring.N - 1) // ring.N, 1)       # whole rows of N words
@@ -245,8 +250,8 @@ def ternary_hamming_weight(N, H, rng=None):
 class TernarySampler:
     """ring.TernarySampler for ring.Ternary{P} (on the device) or ring.Ternary{H} (on the host, uploaded): int32 (npoly, N)"""
 
-    def __init__(self, prng, ring, P=None, H=None):
-        rings_ok("TernarySampler", ring)
+    def __init__(self, prng, ring, P=None, H=None, conjugate_invariant=False):
+        rings_ok("TernarySampler", ring, None, conjugate_invariant)
         if (P is None) == (H is None):
             raise RingHipError("TernarySampler: give the density P or the Hamming weight H, one of them")
         self.prng, self.ring, self.P, self.H = prng, ring, P, H
@@ -270,8 +275,9 @@ class TernarySampler:
 
 def lift_small(ringQ, ringP, small, outQ, outP=None, accumulate=False):
     """int32 coefficients -> residues under every limb of outQ (and of outP under ringP): x >= 0 ? x : q - |x|, what Read +
-    ExtendBasisSmallNormAndCenter produce; accumulate: ReadAndAdd, out = CRed(out + lift).  outQ / outP: DevicePoly batches of small.npoly polys."""
-    rings_ok("lift_small", ringQ, ringP if outP is not None else None)
+    ExtendBasisSmallNormAndCenter produce; accumulate: ReadAndAdd, out = CRed(out + lift).  outQ / outP: DevicePoly batches of small.npoly polys.
+    Per coefficient, so a conjugate-invariant ring is served like a standard one (nothing builds on its refusal)."""
+    rings_ok("lift_small", ringQ, ringP if outP is not None else None, conjugate_invariant=True)
     if outQ.npoly != small.npoly or (outP is not None and outP.npoly != small.npoly):
         raise RingHipError("lift_small: the blocks hold different numbers of polys")
     _check(lib().rh_small_lift(ringQ._h, ringP._h if outP is not None else None, outQ.limbs - 1, outP.limbs - 1 if outP is not None else -1, small.ptr,
