@@ -719,6 +719,22 @@ int rh_ckks_bootstrap_modup(rh_ring* rQ, rh_ring* rP, int levelQ, int levelP, co
                             uint64_t* out0_dev, uint64_t* out1_dev, uint64_t* c1Q_dev, uint64_t* c1P_dev, int npoly, const uint64_t* scalarQ,
                             const uint64_t* scalarP);
 int rh_ckks_double_angle(rh_ring* r, int level, uint64_t* c0_dev, uint64_t* c1_dev, int npoly, const uint64_t* s0, const uint64_t* s1);
+/*   rh_ckks_bootstrap_pack   BootstrapMany's pack (evaluator.go:1035-1058): n ciphertexts -> ceil(n / 2^g), g tree levels of
+ *                            eve += odd * xPow2[logGap - i]; group j of the output is the sum over the inputs j 2^g + k that exist of
+ *                            in times the rows of the set bits of k (a ciphertext without a partner moves up as it is, :1052-1057).
+ *                            in0 / in1: blocks (n, in_rows, N), out0 / out1: blocks (ceil(n / 2^g), out_rows, N), NTT domain; xp: the block
+ *                            (g, xp_rows, N) with row i = xPow2[logGap - i], NTT domain, Montgomery form; every *_rows >= level + 1.
+ *   rh_ckks_bootstrap_unpack its inverse (:985-1001): ceil(n / 2^g) ciphertexts -> n, out[j 2^g + k] = in[j] times the rows xinv[i] =
+ *                            xPow2Inv[logGap - i] of the set bits of k, out[j 2^g] a copy; a new block.
+ *                            Both: ceil(g / 4) launches over both components, up to four levels each; for g > 4 the intermediates go
+ *                            through `scratch` (rh_ckks_bootstrap_pack_scratch_words(N, level + 1, n, g) words, 0 for g <= 4).  1 <= g <= 16.
+ *                            Outputs are canonical for canonical inputs; the inputs are left as they were; an output or the scratch that
+ *                            overlaps an input, the table or another output is refused.  Standard and conjugate-invariant rings. */
+size_t rh_ckks_bootstrap_pack_scratch_words(int N, int L, int n, int g);
+int rh_ckks_bootstrap_pack(rh_ring* r, int level, int n, int g, const uint64_t* in0_dev, const uint64_t* in1_dev, int in_rows, uint64_t* out0_dev,
+                           uint64_t* out1_dev, int out_rows, const uint64_t* xp_dev, int xp_rows, uint64_t* scratch_dev, size_t scratch_words);
+int rh_ckks_bootstrap_unpack(rh_ring* r, int level, int n, int g, const uint64_t* in0_dev, const uint64_t* in1_dev, int in_rows, uint64_t* out0_dev,
+                             uint64_t* out1_dev, int out_rows, const uint64_t* xinv_dev, int xinv_rows, uint64_t* scratch_dev, size_t scratch_words);
 
 /* ---- CKKS encoder: the float64 path of schemes/ckks/encoder.go on device batches of nvec vectors ------------------------------------
  * A handle on a STANDARD ring.  Refused by name (RH_ERR_UNSUPPORTED): conjugate-invariant rings, 3N rings, prec > 53 (the *big.Float /

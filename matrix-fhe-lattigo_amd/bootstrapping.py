@@ -12,16 +12,23 @@ A batch of npoly ciphertexts is one Ciphertext; all of them share level and scal
 Parameters is built from explicit pieces.  Where the reference works in place on its input (ScaleDown, ModUp), the device path writes new
 blocks and leaves the caller's ciphertext as it was.
 
-Refused by name: IterationsParameters (META-BTS) and PREC128, conjugate-invariant residual rings (EvaluateConjugateInvariant), N1 != N2 (the
-ring-degree switch), ciphertexts whose LogDimensions differ from the bootstrapping LogSlots (the pack / unpack of BootstrapMany), the
+Refused by name by Evaluator: IterationsParameters (META-BTS) and PREC128, conjugate-invariant residual rings (EvaluateConjugateInvariant),
+N1 != N2 (the ring-degree switch), ciphertexts whose LogDimensions differ from the bootstrapping LogSlots (the pack / unpack of BootstrapMany), the
 DecodeThenModUp and Custom circuit orders, and the reference's own refusals (SinContinuous with a double angle, CosDiscrete below degree
-2 (K - 1), inconsistent levels, missing keys)."""
+2 (K - 1), inconsistent levels, missing keys).
+
+Bootstrapper (the interface of bootstrapper.go) is BootstrapMany :259-314 around one inner Evaluator: PackAndSwitchN1ToN2 :880-911,
+UnpackAndSwitchN2ToN1 :915-961, pack :1008-1065 and unpack :965-1004 (rh_ckks_bootstrap_pack / _unpack, csrc/bootstrap.hip),
+EvaluateConjugateInvariant :493-538, ComplexToRealNew / RealToComplexNew :848-868; Parameters.GenEvaluationKeys is keys.go:69-144.  It takes the
+three arms Evaluator refuses; iterations, PREC128 and the other circuit orders stay refused."""
 import math
 from fractions import Fraction
 
+import numpy as np
+
 from . import dft, mod1, polynomial, rlwe
-from .ckks import Decryptor, DeviceValues, Encoder, Encryptor, Evaluator as CkksEvaluator, Scale, _round
-from .ringhip import ConjugateInvariant, RingHipError, Standard, _check, _p, _u64, lib
+from .ckks import Decryptor, DeviceValues, DomainSwitcher, Encoder, Encryptor, Evaluator as CkksEvaluator, Scale, _round
+from .ringhip import ConjugateInvariant, DevicePoly, RingHipError, Standard, _check, _p, _u64, lib
 from .schemes import Ciphertext
 
 ModUpThenEncode, DecodeThenModUp, Custom = 0, 1, 2       # CircuitOrder (parameters_literal.go:144-150)
@@ -51,6 +58,110 @@ def modup_lift(ringQ, ringP, levelQ, levelP, in0, in1, out0, out1=None, c1Q=None
                                          c1Q.ptr if c1Q is not None else None, c1P.ptr if c1P is not None else None, in0.npoly, _p(sq), _p(sp)))
 
 
+# which passes of BootstrapMany run as rh_ckks_bootstrap_pack / rh_ckks_bootstrap_unpack (True) or as the reference's ring calls (False):
+# MulCoeffsMontgomeryThenAdd per pair and level (pack), CopyNew + MulCoeffsMontgomery (unpack), Mul(ct, +-1j) + Add (the conjugate-invariant
+# pair fold and unfold).  The same bits either way.
+FUSED_BOOTSTRAP_MANY = {"pack": True, "unpack": True, "pair_fold": True, "pair_unfold": True}
+
+
+def pack_table(ring, xPow2, logGap, g):
+    """rows i = xPow2[logGap - i], 0 <= i < g, of GenXPow2NTT's list as ONE block (g, level + 1, N): the table rh_ckks_bootstrap_pack / _unpack take"""
+    if g < 1 or logGap - (g - 1) < 0 or logGap >= len(xPow2):
+        raise RingHipError("cannot build the pack table: rows %d .. %d of %d powers" % (logGap - (g - 1), logGap, len(xPow2)))
+    block = ring.NewPoly(g)
+    for i in range(g):
+        ring.CopyLvl(xPow2[logGap - i], rlwe._view(block, i, 1))
+    return block
+
+
+def _pack_shapes(ring, n, g, ins, outs, table, who):
+    L = ring.level + 1
+    if len(ins) != 2 or len(outs) != 2:
+        raise RingHipError("cannot %s: two components in and two out" % who)
+    if any(p.limbs < L for p in (*ins, *outs, table)):
+        raise RingHipError("cannot %s: every block and the table hold at least level + 1 = %d limbs" % (who, L))
+    if ins[0].limbs != ins[1].limbs or outs[0].limbs != outs[1].limbs:
+        raise RingHipError("cannot %s: the two components differ in limbs" % who)
+    if table.npoly != g:
+        raise RingHipError("cannot %s: the table holds %d rows per limb, %d tree levels need %d" % (who, table.npoly, g, g))
+    words = lib().rh_ckks_bootstrap_pack_scratch_words(ring.N, L, n, g)
+    return _Scratch(ring, words) if words else None
+
+
+class _Scratch:
+    """device words for the intermediates of a tree deeper than four levels"""
+
+    def __init__(self, ring, words):
+        self.words = int(words)
+        self._p = DevicePoly(ring, (self.words + ring.N - 1) // ring.N, 1)
+        self.ptr = self._p.ptr
+
+
+def bootstrap_pack(ring, g, ins, outs, xp):
+    """pack (evaluator.go:1035-1058) as rh_ckks_bootstrap_pack: ins = (c0, c1), batches of n polys; outs: batches of ceil(n / 2^g); xp: pack_table.
+    The inputs are left as they were."""
+    n = ins[0].npoly
+    if ins[1].npoly != n or any(o.npoly != -(-n >> g) for o in outs):
+        raise RingHipError("cannot pack: %d ciphertexts over %d tree levels give %d, the components hold %s and %s polys"
+                           % (n, g, -(-n >> g), [p.npoly for p in ins], [p.npoly for p in outs]))
+    sc = _pack_shapes(ring, n, g, ins, outs, xp, "pack")
+    words = getattr(sc, "words", 0)
+    _check(lib().rh_ckks_bootstrap_pack(ring._h, ring.level, n, g, ins[0].ptr, ins[1].ptr, ins[0].limbs, outs[0].ptr, outs[1].ptr, outs[0].limbs,
+                                        xp.ptr, xp.limbs, sc.ptr if words else None, words))
+
+
+def bootstrap_unpack(ring, g, n, ins, outs, xinv):
+    """unpack (:985-1001) as rh_ckks_bootstrap_unpack: ins: batches of ceil(n / 2^g) polys; outs: NEW batches of n polys; xinv: pack_table of xPow2Inv"""
+    if any(p.npoly != -(-n >> g) for p in ins) or any(o.npoly != n for o in outs):
+        raise RingHipError("cannot unpack: %d ciphertexts over %d tree levels come from %d, the components hold %s and %s polys"
+                           % (n, g, -(-n >> g), [p.npoly for p in ins], [p.npoly for p in outs]))
+    sc = _pack_shapes(ring, n, g, ins, outs, xinv, "unpack")
+    words = getattr(sc, "words", 0)
+    _check(lib().rh_ckks_bootstrap_unpack(ring._h, ring.level, n, g, ins[0].ptr, ins[1].ptr, ins[0].limbs, outs[0].ptr, outs[1].ptr, outs[0].limbs,
+                                          xinv.ptr, xinv.limbs, sc.ptr if words else None, words))
+
+
+def pack_composed(ring, g, ins, outs, xp, work=None):
+    """the reference's tree as written (:1035-1058) on a copy of the inputs: MulCoeffsMontgomeryThenAdd(odd, xPow2[logGap - i], eve) per pair
+    and level, the odd one out moving up as it is (:1052-1057).  work: two blocks for the copies (allocated here without)"""
+    n = ins[0].npoly
+    for c in (0, 1):
+        copy = ring.NewPoly(n) if work is None else work[c]
+        ring.CopyLvl(ins[c], copy)
+        cts = [rlwe._view(copy, k, 1) for k in range(n)]
+        for i in range(g):
+            t = rlwe._view(xp, i, 1)
+            for j in range(len(cts) >> 1):
+                ring.MulCoeffsMontgomeryThenAdd(cts[2 * j + 1], t, cts[2 * j])
+                cts[j] = cts[2 * j]
+            if len(cts) & 1:
+                cts[len(cts) >> 1] = cts[-1]
+                cts = cts[:(len(cts) >> 1) + 1]
+            else:
+                cts = cts[:len(cts) >> 1]
+        for j, v in enumerate(cts):
+            ring.CopyLvl(v, rlwe._view(outs[c], j, 1))
+
+
+def unpack_composed(ring, g, n, ins, outs, xinv):
+    """the reference's loops as written (:968-1001) per packed ciphertext: CopyNew, then MulCoeffsMontgomery by xPow2Inv[logGap - i] in place"""
+    G = 1 << g
+    for c in (0, 1):
+        for j in range(ins[c].npoly):
+            nj = min(n - j * G, G)                                                   # n = min(NbPackedCTs, 2^logPackCTs) (:973)
+            cts = [rlwe._view(outs[c], j * G + k, 1) for k in range(nj)]
+            for v in cts:
+                ring.CopyLvl(rlwe._view(ins[c], j, 1), v)
+            for i in range(min((nj - 1).bit_length(), g)):                           # :985
+                step = 1 << (i + 1)
+                t = rlwe._view(xinv, i, 1)
+                for j0 in range(0, nj, step):
+                    for k in range(step >> 1, step):
+                        if j0 + k >= nj:
+                            break
+                        ring.MulCoeffsMontgomery(cts[j0 + k], t, cts[j0 + k])
+
+
 class Parameters:
     """bootstrapping.Parameters (parameters.go:18-35) from explicit pieces.  ringQ / ringP: the rings of BootstrappingParameters, whose first
     ResidualMaxLevel + 1 moduli are ResidualParameters.Q; ResidualDefaultScale / BootstrappingDefaultScale: the two DefaultScale();
@@ -58,8 +169,18 @@ class Parameters:
 
     def __init__(self, ringQ, ringP, ResidualMaxLevel, ResidualDefaultScale, SlotsToCoeffsParameters, Mod1ParametersLiteral, CoeffsToSlotsParameters,
                  EphemeralSecretWeight=32, BootstrappingDefaultScale=None, CircuitOrder=ModUpThenEncode, IterationsParameters=None,
-                 ResidualRingType=Standard, ResidualN=None, PrecisionMode=PREC64):
+                 ResidualRingType=Standard, ResidualN=None, PrecisionMode=PREC64, ResidualRingQ=None, BootstrappingSecretWeight=None):
+        """ResidualRingQ: the ring handle of ResidualParameters (degree N1, Standard or ConjugateInvariant) when it is not the bootstrapping ring
+        itself: its moduli are Q[:ResidualMaxLevel + 1], and ResidualN / ResidualRingType follow from it (Bootstrapper reads it).
+        BootstrappingSecretWeight: the Hamming weight of the ephemeral secret GenEvaluationKeys samples when N1 != N2; None: the ternary law."""
         self.ringQ, self.ringP, self.ResidualMaxLevel = ringQ, ringP, int(ResidualMaxLevel)
+        self.ResidualRingQ, self.BootstrappingSecretWeight = ResidualRingQ, BootstrappingSecretWeight
+        if ResidualRingQ is not None:
+            if [int(q) for q in ResidualRingQ.moduli] != [int(q) for q in ringQ.moduli[:self.ResidualMaxLevel + 1]]:
+                raise RingHipError("cannot NewParameters: the moduli of ResidualRingQ are not Q[:ResidualMaxLevel + 1] of the bootstrapping parameters")
+            if ResidualRingQ.kind not in (Standard, ConjugateInvariant):
+                raise RingHipError("cannot NewParameters: ResidualRingQ must be a standard or a conjugate-invariant ring")
+            ResidualRingType, ResidualN = ResidualRingQ.kind, ResidualRingQ.N
         self.ResidualDefaultScale = Scale(ResidualDefaultScale)
         self.BootstrappingDefaultScale = Scale(ResidualDefaultScale if BootstrappingDefaultScale is None else BootstrappingDefaultScale)
         self.SlotsToCoeffsParameters, self.Mod1ParametersLiteral, self.CoeffsToSlotsParameters = SlotsToCoeffsParameters, Mod1ParametersLiteral, CoeffsToSlotsParameters
@@ -90,15 +211,65 @@ class Parameters:
         keys.add(2 * N - 1)
         return sorted(keys)
 
+    def GenEvaluationKeys(self, skN1, prng=None, samples=None, xe=(3.2, 19)):
+        """keys.go:69-144 -> (EvaluationKeys, skN2), every key made on the device by the key layer's own calls, in the reference's order: the
+        ephemeral secret and the keys between the rings (N1 != N2), or skN1 extended to all of Q and P (N1 == N2:
+        ExtendBasisSmallNormAndCenterNTTMontgomery, here the small coefficients -- the key's own, or INTT / IMForm of limb 0 centred -- lifted
+        under QP); the two encapsulation keys; the relinearisation key; the Galois keys of GaloisElements() (the conjugation among them) in one
+        launch sequence.  samples: {name: what that key-layer call takes as samples} for any of "skN2", "EvkN1ToN2", "EvkN2ToN1", "RingSwap"
+        (a pair), "skSparse", "EvkDenseToSparse", "EvkSparseToDense", "rlk", "galois"."""
+        from .keygen import centred_coeffs
+        from .ringhip import Ring
+        from .sampling import SmallPoly
+        samples = samples or {}
+        rq, rp = self.ringQ, self.ringP
+        kgen = rlwe.KeyGenerator(rq, rp, xe=xe, prng=prng)
+        prng = kgen.prng
+        N1to2 = N2to1 = RtoC = CtoR = None
+        if self.ResidualN != rq.N:
+            if "skN2" in samples or self.BootstrappingSecretWeight is None:
+                skN2 = kgen.GenSecretKeyNew(samples.get("skN2"))
+            else:
+                skN2 = kgen.GenSecretKeyWithHammingWeightNew(self.BootstrappingSecretWeight)
+            if self.ResidualRingType == ConjugateInvariant:
+                CtoR, RtoC = kgen.GenEvaluationKeysForRingSwapNew(skN2, skN1, samples=samples.get("RingSwap"))
+            else:
+                N1to2 = kgen.GenEvaluationKeyNew(skN1, skN2, samples=samples.get("EvkN1ToN2"))
+                N2to1 = kgen.GenEvaluationKeyNew(skN2, skN1, samples=samples.get("EvkN2ToN1"))
+        else:
+            if skN1.Value.Q.ring.N != rq.N or skN1.Value.Q.ring.kind != Standard:
+                raise RingHipError("cannot GenEvaluationKeys: skN1 is not a secret of the standard ring of degree %d" % rq.N)
+            c = centred_coeffs(skN1)
+            skN2 = kgen._secret_from(SmallPoly.from_numpy(rq, np.asarray(c, dtype=np.int32).reshape(1, -1)))
+        d2s = s2d = None
+        if self.EphemeralSecretWeight != 0:                                                           # genEncapsulationEvaluationKeysNew (:123-144)
+            q0 = Ring(rq.N, [int(rq.moduli[0])], device=rq.device)
+            p0 = Ring(rq.N, [int(rp.moduli[0])], device=rq.device)
+            kgenSparse = rlwe.KeyGenerator(q0, p0, xe=xe, prng=prng)
+            if "skSparse" in samples:
+                skSparse = kgenSparse.GenSecretKeyNew(samples["skSparse"])
+            else:
+                skSparse = kgenSparse.GenSecretKeyWithHammingWeightNew(self.EphemeralSecretWeight)
+            small = SmallPoly.from_numpy(rq, np.asarray(centred_coeffs(skSparse), dtype=np.int32).reshape(1, -1))
+            d2s = kgenSparse.GenEvaluationKeyNew(skN2, skSparse, samples=samples.get("EvkDenseToSparse"))       # limb 0 of skN2 is read
+            s2d = kgen.GenEvaluationKeyNew(kgen._secret_from(small), skN2, samples=samples.get("EvkSparseToDense"))
+        rlk = kgen.GenRelinearizationKeyNew(skN2, samples=samples.get("rlk"))
+        galEls = [g for g in self.GaloisElements() if g != 1]
+        gks = kgen.GenGaloisKeysNew(galEls, skN2, samples=samples.get("galois"))
+        return EvaluationKeys(rlk, dict(zip(galEls, gks)), d2s, s2d, N1to2, N2to1, RtoC, CtoR), skN2
+
 
 class EvaluationKeys:
     """bootstrapping.EvaluationKeys (keys.go:33-41) as far as this path reads them: the relinearisation key and the Galois keys
     (rlwe.GadgetCiphertext over ringQ, ringP) and the two encapsulation keys -- EvkDenseToSparse over the one-limb rings of Q[:1] and P[:1]
     (keys.go:131-141), EvkSparseToDense over ringQ, ringP"""
 
-    def __init__(self, rlk=None, galois_keys=None, EvkDenseToSparse=None, EvkSparseToDense=None):
+    def __init__(self, rlk=None, galois_keys=None, EvkDenseToSparse=None, EvkSparseToDense=None, EvkN1ToN2=None, EvkN2ToN1=None,
+                 EvkRealToCmplx=None, EvkCmplxToReal=None):
         self.rlk, self.galois_keys = rlk, dict(galois_keys or {})
         self.EvkDenseToSparse, self.EvkSparseToDense = EvkDenseToSparse, EvkSparseToDense
+        self.EvkN1ToN2, self.EvkN2ToN1 = EvkN1ToN2, EvkN2ToN1                     # Bootstrapper: the ring-degree switch (keys.go:33-41)
+        self.EvkRealToCmplx, self.EvkCmplxToReal = EvkRealToCmplx, EvkCmplxToReal # Bootstrapper: the ring-type switch
 
 
 def _with_scaling(lit, scaling):
@@ -372,6 +543,313 @@ class Evaluator:
             h.Scale, h.LogDimensions = out.Scale, out.LogDimensions
             halves.append(h)
         return halves[0], halves[1]
+
+
+class _PackingContext:
+    """packingContext (:871-876): the ring packed in and its LogMaxSlots, the dimension packed up to, the ciphertexts' own, their number"""
+
+    def __init__(self, ring, ParamsLogMaxSlots, LogMaxDimensions, LogSlots, NbPackedCTs):
+        self.ring, self.ParamsLogMaxSlots, self.LogMaxDimensions, self.LogSlots, self.NbPackedCTs = ring, ParamsLogMaxSlots, LogMaxDimensions, LogSlots, NbPackedCTs
+
+
+class _SwitcherParameters:
+    """what ckks.DomainSwitcher reads of its parameters"""
+
+    def __init__(self, ring):
+        self.ring, self.device = ring, ring.device
+
+    def RingQ(self):
+        return self.ring
+
+    def RingType(self):
+        return self.ring.kind
+
+
+class Bootstrapper:
+    """The Bootstrapper interface (bootstrapper.go) over bootstrapping.Evaluator: BootstrapMany (evaluator.go:259-314) with the arms Evaluator
+    refuses -- ciphertexts packed more sparsely than the bootstrapping (pack / unpack, :965-1065), ResidualParameters.N != BootstrappingParameters.N
+    (PackAndSwitchN1ToN2 / UnpackAndSwitchN2ToN1, :880-961) and conjugate-invariant residual parameters (EvaluateConjugateInvariant, :493-538).
+    It owns one inner Evaluator over the standard ring of degree N2 (the same parameters with ResidualRingType = Standard, ResidualN = N2 and,
+    for a conjugate-invariant residual ring, SlotsToCoeffsParameters.Scaling = 0.5, :71): every core step is that evaluator's.
+
+    A batch of n ciphertexts is one Ciphertext with npoly = n; all share level, scale and LogDimensions (the per-pair min(level) of :1042 is
+    moot).  BootstrapMany returns a batch of n at OutputLevel() with Scale = ResidualDefaultScale and leaves its input as it was; the packed
+    ciphertexts go through Evaluate as ONE batch.  On a conjugate-invariant residual ring the whole batch is switched by one RealToComplex,
+    pairs (2 j, 2 j + 1) are folded into c_2j + i c_2j+1 (the last one alone when n is odd: the nil arm), bootstrapped, unfolded to
+    [x_j, -i x_j] and switched back by one ComplexToReal.
+
+    The pack tables are made at the residual ring's full level and read at the input's level (the reference makes them at level 0 only, :77,
+    :80, so its pack serves level-0 inputs; at level 0 the words are the reference's).
+
+    fused: None what FUSED_BOOTSTRAP_MANY (and, for the inner evaluator, mod1.Evaluator.FUSED_BOOTSTRAP) says, else True / False for every choice:
+      pack, unpack             rh_ckks_bootstrap_pack / _unpack, or MulCoeffsMontgomeryThenAdd per pair and level / CopyLvl + MulCoeffsMontgomery
+      pair_fold, pair_unfold   the same kernels with a group of 2 and the one row NTT(X^(N/2)) (its negation), or Mul(ct, +-1i) and Add
+    -- the same bits either way.
+
+    Refused by name: IterationsParameters (META-BTS) and PREC128, the DecodeThenModUp and Custom orders, missing switch keys (the reference's
+    text), and what the inner evaluator refuses."""
+
+    def __init__(self, parameters, keys, fused=None):
+        p = self.Parameters = parameters
+        who = "cannot NewBootstrapper"
+        if p.IterationsParameters is not None:
+            raise RingHipError("%s: IterationsParameters (META-BTS iterations, the reserved prime) are not built on the device path" % who)
+        if p.PrecisionMode != PREC64:
+            raise RingHipError("%s: PREC128 residual parameters are not built on the device path" % who)
+        self.N2, self.N1, self.ci = p.ringQ.N, p.ResidualN, p.ResidualRingType == ConjugateInvariant
+        if p.ResidualRingType not in (Standard, ConjugateInvariant) or p.ringQ.kind != Standard:
+            raise RingHipError("%s: a standard bootstrapping ring and a standard or conjugate-invariant residual ring" % who)
+        missing = "%s: evk.(BootstrappingKeys) is missing EvkN1ToN2 and EvkN2ToN1" % who                  # :55-63, both arms with this text
+        if self.ci:
+            if keys.EvkCmplxToReal is None or keys.EvkRealToCmplx is None:
+                raise RingHipError(missing)
+            if 2 * self.N1 != self.N2:
+                raise RingHipError("%s: a conjugate-invariant residual ring has degree N2 / 2 = %d, not %d" % (who, self.N2 // 2, self.N1))
+        elif self.N1 != self.N2 and (keys.EvkN1ToN2 is None or keys.EvkN2ToN1 is None):
+            raise RingHipError(missing)
+        if self.N1 != self.N2 and p.ResidualRingQ is None:
+            raise RingHipError("%s: ResidualParameters.N = %d != BootstrappingParameters.N = %d needs Parameters.ResidualRingQ, the ring of degree N1"
+                               % (who, self.N1, self.N2))
+        if self.N1 > self.N2:
+            raise RingHipError("%s: ResidualParameters.N = %d > BootstrappingParameters.N = %d" % (who, self.N1, self.N2))
+        self.fused = dict(FUSED_BOOTSTRAP_MANY) if fused is None else {k: bool(fused) for k in FUSED_BOOTSTRAP_MANY}
+        s2c = p.SlotsToCoeffsParameters
+        if self.ci:                                                                                       # the switch to the conjugate-invariant ring doubles the scale (:70-71)
+            s2c = dft.MatrixLiteral(s2c.Type, s2c.LogSlots, s2c.LevelQ, s2c.LevelP, s2c.Levels, s2c.Format, 0.5, s2c.BitReversed, s2c.LogBSGSRatio)
+        inner = Parameters(p.ringQ, p.ringP, p.ResidualMaxLevel, p.ResidualDefaultScale, s2c, p.Mod1ParametersLiteral, p.CoeffsToSlotsParameters,
+                           EphemeralSecretWeight=p.EphemeralSecretWeight, BootstrappingDefaultScale=p.BootstrappingDefaultScale, CircuitOrder=p.CircuitOrder)
+        self.Evaluator = Evaluator(inner, keys, fused=fused)
+        self.EvaluationKeys = keys
+        res = p.ResidualMaxLevel
+        self.ringN2 = p.ringQ.AtLevel(res)
+        self.ringN1 = p.ResidualRingQ if self.N1 != self.N2 else None
+        logN2 = self.N2.bit_length() - 1
+        self.xPow2N2, self.xPow2InvN2 = rlwe.GenXPow2NTT(self.ringN2, logN2, False), rlwe.GenXPow2NTT(self.ringN2, logN2, True)
+        self.xPow2N1 = self.xPow2InvN1 = None
+        if self.ringN1 is not None and not self.ci:
+            logN1 = self.N1.bit_length() - 1
+            self.xPow2N1, self.xPow2InvN1 = rlwe.GenXPow2NTT(self.ringN1, logN1, False), rlwe.GenXPow2NTT(self.ringN1, logN1, True)
+        self._tables = {}
+        self.DomainSwitcher = self._switch_eval = self._switch_ring = None
+        if self.ci:
+            # the ring-swap keys are made at the secrets' common level, the residual one: the switch runs on an evaluator over Q[:ResidualMaxLevel + 1]
+            from .ringhip import Ring
+            self._switch_ring = Ring(self.N2, [int(q) for q in p.ringQ.moduli[:res + 1]], device=p.ringQ.device)
+            self._switch_eval = CkksEvaluator(self._switch_ring, p.ringP)
+            self.DomainSwitcher = DomainSwitcher(_SwitcherParameters(self._switch_ring), keys.EvkCmplxToReal, keys.EvkRealToCmplx)
+            self._i = pack_table(self.ringN2, self.xPow2N2, logN2 - 1, 1)                               # NTT(X^(N/2)), Montgomery form: i
+            self._minus_i = self.ringN2.NewPoly(1)
+            self.ringN2.Neg(self._i, self._minus_i)
+
+    def close(self):
+        self.Evaluator.close()
+        if self.DomainSwitcher is not None:
+            self.DomainSwitcher.close()
+            self._switch_eval.close()
+            self._switch_ring.close()
+
+    def Depth(self):
+        return self.Evaluator.Depth()
+
+    def OutputLevel(self):
+        return self.Evaluator.OutputLevel()
+
+    def MinimumInputLevel(self):
+        return self.Evaluator.MinimumInputLevel()
+
+    # ---- Bootstrap :249-256, BootstrapMany :259-314 ----
+    def Bootstrap(self, ct):
+        return self.BootstrapMany(ct)
+
+    def BootstrapMany(self, cts):
+        who = "cannot BootstrapMany"
+        if getattr(cts, "LogDimensions", None) is None:
+            raise RingHipError("%s: a ciphertext carries no LogDimensions" % who)
+        try:
+            if self.ci:
+                out = self.EvaluateConjugateInvariant(cts)
+            else:
+                packed, ctxt1, ctxt2 = self.PackAndSwitchN1ToN2(cts)
+                out = self.UnpackAndSwitchN2ToN1(self.Evaluator.Evaluate(packed), ctxt1, ctxt2)
+        except RingHipError as e:
+            if str(e).startswith(who):
+                raise
+            raise RingHipError("%s: %s" % (who, e)) from e
+        out.Scale = self.Parameters.ResidualDefaultScale
+        return out
+
+    # ---- the tables ----
+    def _table(self, ring, powers, logGap, g, tag):
+        key = (tag, logGap, g)
+        if key not in self._tables:
+            self._tables[key] = pack_table(ring, powers, logGap, g)
+        return self._tables[key]
+
+    @staticmethod
+    def _like(ct, value):
+        out = Ciphertext(value, is_ntt=ct.IsNTT)
+        out.Scale, out.LogDimensions = ct.Scale if isinstance(ct.Scale, Scale) else Scale(ct.Scale), getattr(ct, "LogDimensions", None)
+        for name in ("IsBatched", "IsMontgomery"):
+            if hasattr(ct, name):
+                setattr(out, name, getattr(ct, name))
+        return out
+
+    # ---- pack :1008-1065, unpack :965-1004 on a batch ----
+    def pack(self, cts, ctxt, powers, tag):
+        logSlots, logMaxSlots = ctxt.LogSlots, ctxt.LogMaxDimensions
+        if logSlots > logMaxSlots:
+            raise RingHipError("cannot Pack: cts[0].LogSlots()=%d > logMaxSlots=%d" % (logSlots, logMaxSlots))
+        if cts.Value[0].ring.N != ctxt.ring.N:
+            raise RingHipError("cannot Pack: cts[0].Value[0].N()=%d != params.N()=%d" % (cts.Value[0].ring.N, ctxt.ring.N))
+        g = logMaxSlots - logSlots
+        if g == 0:
+            return cts
+        if not cts.IsNTT or cts.Degree() != 1:
+            raise RingHipError("cannot Pack: degree-1 ciphertexts in the NTT domain")
+        logGap = ctxt.ParamsLogMaxSlots - logSlots - 1
+        n, level = cts.Value[0].npoly, cts.Level()
+        if level > ctxt.ring.level:
+            raise RingHipError("cannot Pack: the ciphertexts are at level %d, above the residual level %d" % (level, ctxt.ring.level))
+        ring = ctxt.ring.AtLevel(level)
+        xp = self._table(ctxt.ring, powers, logGap, g, tag)
+        outs = [ring.NewPoly(-(-n >> g)) for _ in (0, 1)]
+        (bootstrap_pack if self.fused["pack"] else pack_composed)(ring, g, cts.Value, outs, xp)
+        out = self._like(cts, outs)
+        out.LogDimensions = logMaxSlots                                                                # :1060-1062
+        return out
+
+    def unpack(self, cts, ctxt, powers, tag):
+        """every packed ciphertext of the batch (:922-931): NbPackedCTs ciphertexts come out, min(what is left, 2^logPackCTs) of each"""
+        g = ctxt.LogMaxDimensions - ctxt.LogSlots
+        if g == 0:
+            ctxt.NbPackedCTs -= cts.Value[0].npoly
+            return cts
+        n, level = ctxt.NbPackedCTs, cts.Level()
+        if cts.Value[0].npoly != -(-n >> g):
+            raise RingHipError("cannot Unpack: %d ciphertexts of 2^%d each do not hold %d" % (cts.Value[0].npoly, g, n))
+        logGap = ctxt.ParamsLogMaxSlots - ctxt.LogSlots - 1
+        ring = ctxt.ring.AtLevel(level)
+        xinv = self._table(ctxt.ring, powers, logGap, g, tag)
+        outs = [ring.NewPoly(n) for _ in (0, 1)]
+        if self.fused["unpack"]:
+            bootstrap_unpack(ring, g, n, cts.Value, outs, xinv)
+        else:
+            unpack_composed(ring, g, n, cts.Value, outs, xinv)
+        ctxt.NbPackedCTs -= n
+        return self._like(cts, outs)
+
+    # ---- :826-846 ----
+    def _switch_degree(self, ct, evk, ring):
+        out = self._like(ct, [ring.AtLevel(ct.Level()).NewPoly(ct.Value[0].npoly) for _ in (0, 1)])
+        self.Evaluator.Evaluator.ks.ApplyEvaluationKey(ct, evk, out)
+        out.Scale, out.LogDimensions = ct.Scale, ct.LogDimensions
+        return out
+
+    # ---- PackAndSwitchN1ToN2 :880-911, UnpackAndSwitchN2ToN1 :915-961 ----
+    def PackAndSwitchN1ToN2(self, cts):
+        p = self.Parameters
+        packN1 = None
+        n = cts.Value[0].npoly
+        if self.N1 != self.N2:
+            logMaxN1 = self.N1.bit_length() - 2
+            packN1 = _PackingContext(self.ringN1, logMaxN1, min(logMaxN1, p.LogMaxSlots()), cts.LogDimensions, n)
+            try:
+                cts = self.pack(cts, packN1, self.xPow2N1, "N1")
+            except RingHipError as e:
+                raise RingHipError("cannot PackAndSwitchN1ToN2: PackN1: %s" % e) from e
+            cts = self._switch_degree(cts, self.EvaluationKeys.EvkN1ToN2, p.ringQ)
+        packN2 = _PackingContext(self.ringN2, self.N2.bit_length() - 2, p.LogMaxSlots(), cts.LogDimensions, cts.Value[0].npoly)
+        try:
+            cts = self.pack(cts, packN2, self.xPow2N2, "N2")
+        except RingHipError as e:
+            raise RingHipError("cannot PackAndSwitchN1ToN2: PackN1: %s" % e) from e                     # the reference's text, as written (:907)
+        return cts, packN1, packN2
+
+    def UnpackAndSwitchN2ToN1(self, cts, ctxtN1, ctxtN2):
+        logSlots = ctxtN2.LogSlots
+        out = self.unpack(cts, ctxtN2, self.xPow2InvN2, "N2inv")
+        if ctxtN1 is not None:
+            logSlots = ctxtN1.LogSlots
+            out = self._switch_degree(out, self.EvaluationKeys.EvkN2ToN1, self.ringN1)
+            out = self.unpack(out, ctxtN1, self.xPow2InvN1, "N1inv")
+        if out is cts:
+            out = self._like(cts, cts.Value)
+        out.LogDimensions = logSlots                                                                   # :956-958
+        return out
+
+    # ---- :848-868 ----
+    def _rewrap(self, ct, ring):
+        """the same device blocks as polys of `ring` (the switcher works over its own handles of the same degree and moduli)"""
+        out = self._like(ct, [DevicePoly(ring.AtLevel(v.limbs - 1), v.npoly, v.limbs, ptr=v.ptr, owner=v) for v in ct.Value])
+        return out
+
+    def RealToComplexNew(self, ctReal):
+        if self.DomainSwitcher is None:
+            raise RingHipError("cannot RealToComplex: the residual parameters are not conjugate-invariant")
+        out = self.DomainSwitcher.RealToComplexNew(self._switch_eval, ctReal)
+        return self._rewrap(out, self.Parameters.ringQ)
+
+    def ComplexToRealNew(self, ctCmplx):
+        if self.DomainSwitcher is None:
+            raise RingHipError("cannot ComplexToReal: the residual parameters are not conjugate-invariant")
+        out = self.DomainSwitcher.ComplexToRealNew(self._switch_eval, self._rewrap(ctCmplx, self._switch_ring))
+        return self._rewrap(out, self.Parameters.ResidualRingQ)
+
+    # ---- EvaluateConjugateInvariant :493-538 on a batch: pairs (2 j, 2 j + 1) ----
+    def _views(self, ct, first, count=1):
+        return self._like(ct, [rlwe._view(v, first, count) for v in ct.Value])
+
+    def pair_fold(self, std):
+        """:502-514 for every pair of the batch: c_2j + i c_2j+1; the last one alone when the batch is odd"""
+        n, level = std.Value[0].npoly, std.Level()
+        ring = self.Parameters.ringQ.AtLevel(level)
+        outs = [ring.NewPoly((n + 1) >> 1) for _ in (0, 1)]
+        out = self._like(std, outs)
+        if self.fused["pair_fold"]:
+            bootstrap_pack(ring, 1, std.Value, outs, self._i)
+            return out
+        ev = self.Evaluator.Evaluator
+        for j in range(n >> 1):
+            right = ev.MulNew(self._views(std, 2 * j + 1), 1j)
+            ev.Add(self._views(std, 2 * j), right, self._views(out, j))
+        if n & 1:
+            for c in (0, 1):
+                ring.CopyLvl(rlwe._view(std.Value[c], n - 1, 1), rlwe._view(outs[c], n >> 1, 1))
+        return out
+
+    def pair_unfold(self, std, n):
+        """:527-535: [x_j, -i x_j] for every bootstrapped pair, the absent last right-hand one dropped"""
+        level = std.Level()
+        ring = self.Parameters.ringQ.AtLevel(level)
+        outs = [ring.NewPoly(n) for _ in (0, 1)]
+        out = self._like(std, outs)
+        if self.fused["pair_unfold"]:
+            bootstrap_unpack(ring, 1, n, std.Value, outs, self._minus_i)
+            return out
+        ev = self.Evaluator.Evaluator
+        for j in range(std.Value[0].npoly):
+            for c in (0, 1):
+                ring.CopyLvl(rlwe._view(std.Value[c], j, 1), rlwe._view(outs[c], 2 * j, 1))
+            if 2 * j + 1 < n:
+                ev.Mul(self._views(std, j), -1j, self._views(out, 2 * j + 1))
+        return out
+
+    def EvaluateConjugateInvariant(self, cts):
+        """a batch over the conjugate-invariant ring of degree N2 / 2 -> the batch bootstrapped, at OutputLevel()"""
+        if cts is None:
+            raise RingHipError("ctLeftN1Q0 cannot be nil")
+        if not self.ci:
+            raise RingHipError("cannot EvaluateConjugateInvariant: the residual parameters are not conjugate-invariant")
+        if cts.Value[0].ring.N != self.N1:
+            raise RingHipError("cannot EvaluateConjugateInvariant: the ciphertexts have ring degree %d, the residual parameters %d" % (cts.Value[0].ring.N, self.N1))
+        n = cts.Value[0].npoly
+        std = self.RealToComplexNew(cts)
+        std.LogDimensions = cts.LogDimensions
+        both = self.Evaluator.Evaluate(self.pair_fold(std))
+        both.Scale = both.Scale.Mul(Scale(Fraction(1, 2)))                                              # :524
+        out = self.ComplexToRealNew(self.pair_unfold(both, n))
+        out.LogDimensions = cts.LogDimensions
+        return out
 
 
 class SecretKeyBootstrapper:

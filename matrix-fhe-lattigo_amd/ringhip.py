@@ -170,6 +170,9 @@ def lib():
         "rh_ckks_dft_merge_level": (i, [vp, C.c_uint, i, vp, vp, i, C.POINTER(i), i, vp, vp, sz]),
         "rh_ckks_dft_finish": (i, [vp, C.c_uint, i, vp, vp, C.c_double, i, C.POINTER(i), vp, sz]),
         "rh_ckks_bootstrap_modup": (i, [vp, vp, i, i, vp, vp, i, vp, vp, vp, vp, i, U64P, U64P]), "rh_ckks_double_angle": (i, [vp, i, vp, vp, i, U64P, U64P]),
+        "rh_ckks_bootstrap_pack_scratch_words": (sz, [i, i, i, i]),
+        "rh_ckks_bootstrap_pack": (i, [vp, i, i, i, vp, vp, i, vp, vp, i, vp, i, vp, sz]),
+        "rh_ckks_bootstrap_unpack": (i, [vp, i, i, i, vp, vp, i, vp, vp, i, vp, i, vp, sz]),
         "rh_ckks_encoder_create": (i, [C.POINTER(vp), vp, C.POINTER(C.c_double), sz, C.c_uint]), "rh_ckks_encoder_destroy": (None, [vp]),
         "rh_ckks_encoder_create_real": (i, [C.POINTER(vp), vp, C.POINTER(C.c_double), sz, C.c_uint]),
         "rh_ckks_encoder_reserve": (i, [vp, i]), "rh_ckks_encoder_set_tuning": (i, [vp, C.c_char_p, C.c_long]),
